@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- particle-scans/sec of the MI355X PFSlam2D path on the seeded synthetic corridor log.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_total]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_total] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one PFSlam2D::update() (predict, scan-match, normalise, resample if due, map update) of ALL particles
@@ -400,6 +400,52 @@ def single_pose_rows(F, with_cpu):
     return out
 
 
+DUMP_BUDGET_B = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload in all
+
+
+def _split_u64(a):
+    """uint64 values as float64 pairs (high 32 bits, low 32 bits): exact, unlike a plain cast"""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(F, pf, shards, out_dir):
+    """--dump-outputs: what a caller of PFSlam2D::update() holds after the last timed step, as DIR/<name>.npy (float64 / float32).
+    `shards` = [(first particle, HipContext)] covering the pool.  Every particle's poses, weights and device-side map checksums are
+    written whole; of the maps themselves the best particle's (the one getOccupancyMap() / getDistanceMap() hand out), patches in
+    ascending id order -- and, should they outgrow the byte budget, a fixed seeded sample of those patches."""
+    os.makedirs(out_dir, exist_ok=True)
+    w, nw, ws = pf.weights()
+    best = int(pf.best())
+    out = {"poses": pf.poses(), "weight": w, "normalized_weight": nw, "weight_sum": ws, "best_pose_xyr": pf.best_pose_xyr(),
+           "state": np.array([best, pf.neff(), pf.num_resamples()], dtype=np.float64),
+           "map_checksums_distance": _split_u64(np.concatenate([c.map_checksums(F.MAP_DISTANCE) for _, c in shards])),
+           "map_checksums_occupancy": _split_u64(np.concatenate([c.map_checksums(F.MAP_OCCUPANCY) for _, c in shards]))}
+    lo, ctx = [s for s in shards if s[0] <= best][-1]
+    maps = {}
+    for name, kind, dtype, fields in (("distance", F.MAP_DISTANCE, F.DIST_T, ("obstacle", "sqdist", "valid", "queued")),
+                                      ("occupancy", F.MAP_OCCUPANCY, F.FREQ_T, ("occupied", "visited"))):
+        m = ctx.download_map(best - lo, kind)
+        ids = np.array(sorted(m), dtype=np.uint64)
+        cells = np.stack([m[int(i)][0] for i in ids]) if len(ids) else np.zeros((0, 1024), dtype=dtype)
+        masks = np.stack([m[int(i)][1] for i in ids]) if len(ids) else np.zeros((0, 16), dtype=np.uint64)
+        # one float32 column per scalar of the cell record: (patches, 1024 cells, columns)
+        cols = [cells[f].reshape(len(ids), 1024, -1).astype(np.float32) for f in fields]
+        maps[name] = (ids, np.concatenate(cols, axis=2), masks)
+    # bytes one patch costs in the dump (cells + split masks + split id), per map
+    per_patch = sum(1024 * cells.shape[2] * 4 + 16 * 2 * 8 + 2 * 8 for _, cells, _ in maps.values())
+    keep = max(DUMP_BUDGET_B - (1 << 16) - sum(a.nbytes for a in out.values()), 0) // per_patch      # (64 KB: the .npy headers)
+    for name, (ids, cells, masks) in maps.items():
+        if len(ids) > keep:
+            sel = np.sort(np.random.default_rng(0).choice(len(ids), size=keep, replace=False))
+            ids, cells, masks = ids[sel], cells[sel], masks[sel]
+        out[f"{name}_map_patch_ids"] = _split_u64(ids)
+        out[f"{name}_map_cells"] = cells
+        out[f"{name}_map_masks"] = _split_u64(masks)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -415,6 +461,8 @@ def main():
     ap.add_argument("--particles", type=int, default=0, help="particles of the whole pool (default: 30 on one GPU, 3000 sharded over several)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--sweep", type=str, default="300,375,3000", help="extra single-GPU particle counts (N=1 only), '' to skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the run behind `value` computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.particles <= 0:
         args.particles = 30 if args.gpus == 1 else 3000
@@ -452,7 +500,7 @@ def main():
     P_total = args.particles
     pts, odom, truth = F.corridor_log(W + K, 1080)
 
-    def run(P, updates, warm, profile=True, brushfire_mode=0, gain=None, summary=False, sharded=True):
+    def run(P, updates, warm, profile=True, brushfire_mode=0, gain=None, summary=False, sharded=True, dump=None):
         # summary=True: PFSlam2D::Summary buckets (each update then waits for its map kernels); False: the map update of scan t
         # overlaps with the host part (motion sampling) of scan t+1, the default of the host class
         kw = {} if gain is None else {"meas_sigma_gain": gain}
@@ -484,6 +532,8 @@ def main():
         dt = pf.max_over_ranks(time.perf_counter() - t0)
         c = ctx.counters()
         err = float(np.linalg.norm(pf.pf.best_pose_xyr()[:2] - truth[warm + updates][:2])) if pf.owns_best() else None
+        if dump:                                             # (one unsharded context)
+            dump_outputs(F, pf.pf, [(0, ctx)], dump)
         out = dict(P=P, seconds=dt, updates=done, value=P * done / dt, ms_per_step=1e3 * dt / max(done, 1), counters=c,
                    resamples=pf.pf.num_resamples() - r0, pose_err_m=err,
                    shipped_particles=pf.shipped_particles - ship0[0], shipped_bytes=pf.shipped_bytes - ship0[1],
@@ -499,7 +549,7 @@ def main():
         pf.close()
         return out
 
-    def run_cpp_multi(P, gpus, updates, warm, gain=None):
+    def run_cpp_multi(P, gpus, updates, warm, gain=None, dump=None):
         """The same pool as ONE lama::PFSlam2D object with Options::gpus = N: the sharded step entirely in C++ (a host thread and a
         device context per GPU, host-side gather of the log-likelihoods, peer copies of the clones) -- no Python, no process group."""
         kw = {} if gain is None else {"meas_sigma_gain": gain}
@@ -519,6 +569,8 @@ def main():
         for r in range(gpus):                                   # the map kernels of the last update are still in flight
             pf.shard_context(r).sync()
         dt = time.perf_counter() - t0
+        if dump:
+            dump_outputs(F, pf, [((r * P + gpus - 1) // gpus, pf.shard_context(r)) for r in range(gpus)], dump)
         res = pf.num_resamples() - r0
         ships = [x for x in xs if x["shipped_particles"] > 0]
         out = dict(value=P * done / dt, ms_per_step=1e3 * dt / max(done, 1), resamples=res,
@@ -551,7 +603,7 @@ def main():
     # `value` comes from a pass WITHOUT the per-kernel hipEvent brackets (they cost two extra device-to-host copies and four
     # event records per step); the kernel breakdown and the roofline durations come from a second pass of the same K steps
     # with the brackets on.
-    main_run = run(P_total, K, W, profile=False)
+    main_run = run(P_total, K, W, profile=False, dump=args.dump_outputs if world == 1 else None)
     assert main_run["updates"] == K, "every scan of the log must pass the motion gate"
     # `value` is only ever the EXACT brushfire (bit-identical to the reference): what ran is read back from the library
     assert main_run["counters"]["brushfire_mode"] == 0, main_run["counters"]
@@ -574,7 +626,7 @@ def main():
             # one GPU's share of the pool alone on one GPU: the step time no amount of sharding can beat (the brushfire chain of a
             # particle does not shrink with the shard) -> predicted ceiling of the strong-scaling curve
             share = run(max(P_total // world, 1), K, W, profile=False, sharded=False)
-            cpp_multi = run_cpp_multi(P_total, world, K, W)
+            cpp_multi = run_cpp_multi(P_total, world, K, W, dump=args.dump_outputs)
             cpp_multi_forced = run_cpp_multi(P_total, world, K, W, gain=forced_gain)
             assert cpp_multi_forced["resamples"] > 0 and cpp_multi_forced["shipped_particles"] > 0, cpp_multi_forced
             # weak scaling: the single-GPU pool (3000 particles) on EVERY GPU (one device for all shards: its share instead)

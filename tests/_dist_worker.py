@@ -30,7 +30,8 @@ def run(rank, world, port, backend, engine_path, P, steps, beams, gain, out_dir,
     pts, odom, _ = F.corridor_log(steps, beams)
     more = {"l2_max": float(os.environ["LAMA_TEST_L2_MAX"])} if os.environ.get("LAMA_TEST_L2_MAX") else {}     # (the wide device library)
     opts = F.pf_options(particles=P, seed=42, meas_sigma_gain=gain, shard_rank=rank, shard_world=world, gpu_device=gpu, **more)
-    pf = ShardedPF(opts, device=torch.device("cpu") if backend == "gloo" else None)
+    # (a world of one rank takes the collective path as well: all-gather, resample planning, barrier)
+    pf = ShardedPF(opts, device=torch.device("cpu") if backend == "gloo" else None, force_collectives=True)
     pf.set_prior(*odom[0])
     hist = []
     for k in range(steps + 1):

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Repeats tests/test_gpu_parity.py::test_config3_split_partition_invariance (G processes on ONE device against one context) and counts
 # the runs that diverge: bash tools/flake_partition.sh <runs> <G> [<G> ...]   (on the GPU box)
+# G is 4 or 5 (tests/test_gpu_parity.py: at most MAX_RANKS ranks beside the test process on the GPU)
 cd "${GRAFT_REPO_ROOT:-.}"
-export LAMA_TEST_EXTRA_WORLDS=5,10,12
 N=${1:-20}; shift
 for w in "$@"; do
   fails=0
