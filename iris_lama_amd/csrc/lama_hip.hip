@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -21,18 +22,60 @@ using namespace lama_dev;
 
 namespace {
 
+// Device array that frees itself: n elements at p (none after a failed allocation).  Nothing is zeroed implicitly.
+template <class T>
+struct DevBuf {
+    T* p = nullptr; size_t n = 0;
+    DevBuf() {}
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf& operator=(DevBuf&&) = delete;
+    ~DevBuf() { reset(); }
+    void reset() { (void)hipFree(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t m)                                      // (on an empty buffer)
+    {
+        const hipError_t e = hipMalloc(&p, m * sizeof(T));
+        if (e == hipSuccess) n = m; else p = nullptr;
+        return e;
+    }
+    // at least `need` elements: a smaller buffer is freed BEFORE the new one (of max(need, floor) elements) is allocated
+    hipError_t grow(size_t need, size_t floor = 0)
+    {
+        if (need <= n) return hipSuccess;
+        reset();
+        return alloc(std::max(need, floor));
+    }
+    size_t bytes() const { return n * sizeof(T); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
+    operator T*() const { return p; }
+};
+
+// A stream or an event that destroys itself.
+template <class H, hipError_t (*Destroy)(H)>
+struct HipHandle {
+    H h = nullptr;
+    HipHandle() {}
+    HipHandle(HipHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    HipHandle& operator=(HipHandle&&) = delete;
+    ~HipHandle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = HipHandle<hipStream_t, hipStreamDestroy>;
+using Event = HipHandle<hipEvent_t, hipEventDestroy>;
+// the deleter of the handles' unique_ptrs (a type of this file: those instantiations stay out of the library's exported symbols)
+struct Delete { template <class T> void operator()(T* q) const { delete q; } };
+
 // The maps of all particles of a context: two directories per HOME (P homes), pooled planes in which every particle owns one
 // contiguous region per map kind (lama_dev.h).  A pool is a list of CHUNKS: it grows by another chunk (never by copying), a region
 // lies inside one chunk.  The reference's patches are heap objects shared through cow_ptr (include/lama/cow_ptr.h:86-118); here
 // memory follows use through per-particle region capacities, and a resample moves nothing that survives.
 struct RegionAlloc;
 struct PoolChunk {
-    uint8_t* plane[4] = {nullptr, nullptr, nullptr, nullptr};      // dm: sv, obs, mask, - ; occ: occ, occ_mask, occ_hit, rev
+    DevBuf<uint8_t> plane[4];                                       // dm: sv, obs, mask, - ; occ: occ, occ_mask, occ_hit, rev
     uint32_t patches = 0;
 };
 struct MapStore {
-    int16_t* dm_dir = nullptr; int16_t* occ_dir = nullptr;          // [P homes][W*W]
-    int32_t* counts = nullptr;                                      // [P][2] logical particle
+    DevBuf<int16_t> dm_dir, occ_dir;                                // [P homes][W*W]
+    int32_t* counts = nullptr;                                      // [P][2] logical particle (a view into lama_hip_ctx::d_results)
     std::vector<PoolChunk> dm_chunks, occ_chunks;
 };
 constexpr size_t DM_PLANE_B[3] = {SV_PATCH_BYTES, 4096, 128};                 // dm_sv, dm_obs, dm_mask bytes per patch
@@ -113,10 +156,10 @@ struct PinVec {
 struct lama_hip_ctx {
     lama_hip_cfg cfg;
     std::string error;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream stream;
+    Event ev0, ev1;
     struct PendingTimer { hipEvent_t a, b; double* acc; uint64_t* launches; };
-    std::vector<hipEvent_t> ev_pool;            // pairs handed out by Timer, resolved after the call's final sync
+    std::vector<Event> ev_pool;                 // pairs handed out by Timer, resolved after the call's final sync
     std::vector<PendingTimer> pending;
     size_t ev_used = 0;
     bool initialised = false;   // first scan done
@@ -129,63 +172,65 @@ struct lama_hip_ctx {
     MapStore ms;
     std::vector<RegionAlloc> ra_dm, ra_occ;     // one allocator per chunk
     std::vector<HostPart> h_part;     // logical particle -> home / regions (host truth) ...
-    PartRec* d_part = nullptr;        // ... and its device copy
+    DevBuf<PartRec> d_part;           // ... and its device copy
     PinVec<PartRec> h_part_stage;     // (page-locked staging of the upload)
-    PinVec<CloneJob> h_jobs; CloneJob* d_jobs = nullptr; uint32_t jobs_cap = 0;
-    PinVec<ZeroJob> h_zjobs; ZeroJob* d_zjobs = nullptr; uint32_t zjobs_cap = 0;
+    PinVec<CloneJob> h_jobs; DevBuf<CloneJob> d_jobs;
+    PinVec<ZeroJob> h_zjobs; DevBuf<ZeroJob> d_zjobs;
     uint32_t floor_dm = 128, floor_occ = 128;      // smallest region a particle gets (cfg.dm_patch_capacity / occ_patch_capacity)
     PinVec<uint32_t> h_guard;         // the guard's per-particle bound of the last map update
     uint64_t clone_bytes = 0;         // bytes the particle copies of the last resample moved (counters)
-    double* d_poses = nullptr;
-    uint64_t* d_qlower = nullptr; uint64_t* d_qraise = nullptr;
-    uint64_t* d_stats = nullptr;
-    uint32_t* d_qsizes = nullptr;
-    uint64_t* d_dbg = nullptr;
-    uint32_t* d_slow = nullptr;
-    uint32_t* d_slow_list = nullptr; uint32_t* d_slow_n = nullptr;      // hand-over list of the brushfire's first stage
+    double* d_poses = nullptr;        // (a view into d_results)
+    DevBuf<uint64_t> d_qlower, d_qraise;
+    uint64_t* d_stats = nullptr;      // (a view into d_results)
+    DevBuf<uint32_t> d_qsizes;
+    DevBuf<uint64_t> d_dbg;
+    DevBuf<uint32_t> d_slow;
+    DevBuf<uint32_t> d_slow_list; uint32_t* d_slow_n = nullptr;      // hand-over list of the brushfire's first stage (d_slow_n: a view into d_results)
     // routing of the long brushfire chains (k_bf_route): second stream + events for the big-queue stage that runs beside the first one
-    uint8_t* d_heavy = nullptr;
+    DevBuf<uint8_t> d_heavy;
     // early lane: the particles routed in the previous update (d_heavy still holds them; valid while the particle set is unchanged)
-    uint8_t* d_early = nullptr; uint32_t* d_elist = nullptr;
-    hipStream_t stream3 = nullptr; hipEvent_t ev_alloc = nullptr, ev_go = nullptr, ev_early = nullptr;
+    DevBuf<uint8_t> d_early; DevBuf<uint32_t> d_elist;
+    Stream stream3; Event ev_alloc, ev_go, ev_early;
     bool early_ok = false;            // the last map update routed over the whole pool and nothing has permuted the particles since
     uint32_t early_candidates = 0;    // routed + early-lane particles of the last map update (none: the early lane is not even launched)
     std::vector<double> h_ll; bool ll_valid = false;   // log-likelihoods of the last scan match, in the current particle order
-    PinVec<uint32_t> h_hlist; uint32_t* d_hlist = nullptr;   // the worst-fitting particles of that scan match (early lane)
+    PinVec<uint32_t> h_hlist; DevBuf<uint32_t> d_hlist;   // the worst-fitting particles of that scan match (early lane)
     uint32_t early_on = 1;            // LAMA_HIP_BF_ROUTE's fifth number (0: no early lane)
     uint32_t early_min_count = 1024;  // below ~4 workgroups per CU everybody else's ray-cast is too short to be worth overtaking (an override sets 0)
-    hipStream_t stream2 = nullptr; hipEvent_t ev_route = nullptr, ev_heavy = nullptr;
+    Stream stream2; Event ev_route, ev_heavy;
     uint32_t route_min_count = 64, route_min_events = 48, route_percent = 150, route_cap = 64;     // LAMA_HIP_BF_ROUTE overrides (tests)
     bool route_forced = false; uint32_t num_cus = 256;
     bool debug_tail = false, debug_window = false;      // LAMA_HIP_DEBUG_TAIL / LAMA_HIP_DEBUG_WINDOW, read at creation
     uint32_t big_stage_pad = 0;                         // dynamic LDS added to the early lane's big-queue workgroups (a FULL chip) so that a long chain has its CU to itself
-    uint64_t* d_act = nullptr; uint32_t* d_act_count = nullptr;
+    DevBuf<uint64_t> d_act; DevBuf<uint32_t> d_act_count;
     // patch-centric ray-cast (lama_raycast_patch.h): ray records / bounding boxes of the scan's beams, arena slot -> directory position
-    lama_dev::RayRec* d_rrec = nullptr; uint64_t* d_rbbox = nullptr; lama_dev::RayChunk* d_rchunk = nullptr; size_t rrec_cap = 0;
-    int32_t* d_err = nullptr;
-    double* d_pts = nullptr; uint32_t pts_cap = 0; uint32_t last_n = 0;
+    // (the three grow together: d_rrec's count is their capacity, in beams of the whole pool)
+    DevBuf<lama_dev::RayRec> d_rrec; DevBuf<uint64_t> d_rbbox; DevBuf<lama_dev::RayChunk> d_rchunk;
+    int32_t* d_err = nullptr;         // (a view into d_results)
+    DevBuf<double> d_pts; uint32_t last_n = 0;
     PinVec<uint64_t> h_stats;
     PinVec<double> h_tfs, h_pts;
     PinVec<int32_t> h_err;
     PinVec<uint32_t> h_slow_n;        // hand-over counts of the last map update (brushfire, ordered replay)
-    double* d_tfs = nullptr;
+    DevBuf<double> d_tfs;
     double* d_loglik = nullptr; int32_t* d_iters = nullptr;
     // d_poses | d_loglik | d_iters | d_err are carved out of ONE allocation so that a scan match brings all of its results
-    // (and the error word) back with a single device-to-host copy
-    uint8_t* d_results = nullptr;
+    // (and the error word) back with a single device-to-host copy; those pointers (and d_slow_n, d_stats, d_guard, ms.counts) are
+    // views into it, not owners
+    DevBuf<uint8_t> d_results;
     size_t results_bytes = 0, status_off = 0, status_bytes = 0;
     PinVec<uint8_t> h_status;
     PinVec<uint8_t> h_results;
-    int32_t* d_oldcounts = nullptr;
-    double* d_bposes = nullptr; double* d_bout = nullptr; uint32_t b_cap = 0;
+    DevBuf<int32_t> d_oldcounts;
+    DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
 
     double scan_reach = 0.0;          // largest point distance of the resident scan (sensor frame, metres)
     uint32_t visit_bound = 0;         // upper bound of the largest `visited` counter of any frequency cell (see k_occ_max_visited)
-    uint32_t* d_scalar = nullptr;
+    DevBuf<uint32_t> d_scalar;
     // particle shipping: descriptors / gathered blob heads of one batch
-    lama_dev::ShipDesc* d_ship_desc = nullptr; uint8_t* d_ship_heads = nullptr; uint32_t ship_cap = 0;
+    DevBuf<lama_dev::ShipDesc> d_ship_desc; DevBuf<uint8_t> d_ship_heads;
     PinVec<lama_dev::ShipDesc> h_ship_desc; PinVec<uint8_t> h_ship_heads;
-    uint32_t* d_guard = nullptr;      // [P][2] bound on the distance-map patches an update may still allocate + block ticket (k_occ_reverse_dir)
+    uint32_t* d_guard = nullptr;      // (a view into d_results) [P][2] bound on the distance-map patches an update may still allocate + block ticket (k_occ_reverse_dir)
     // what the last run_update_maps was asked to do: a cleanly aborted update (ERR_CLEAN_ABORT) is run again after the arenas grew
     Affine last_mtf; uint32_t last_first = 0, last_count = 0;
     bool last_guarded = false;        // the update went through the parallel ray-cast (its allocation phase precedes every modification)
@@ -199,17 +244,29 @@ struct lama_hip_ctx {
     PinVec<double> h_poses;           // host mirror of the particle poses (source of truth between calls)
     PinVec<int32_t> h_counts;         // host mirror of counts of the current set (refreshed after map updates)
     lama_hip_counters ctr;
+
+    // nothing may still run on the stream when the members release themselves
+    ~lama_hip_ctx()
+    {
+        (void)hipSetDevice(cfg.device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
 
+// A failed HIP call: the error is recorded, and the call returns only once the stream has finished what it queued (copies from host
+// memory that is released on the way out -- staging vectors, the caller's buffers, page-locked job lists -- may still be in flight).
+int32_t hip_fail(lama_hip_ctx* ctx, hipError_t e, const char* what)
+{
+    ctx->error = std::string(what) + ": " + hipGetErrorString(e);
+    (void)hipStreamSynchronize(ctx->stream);
+    return LAMA_HIP_E_HIP;
+}
 #define HIPCHK(ctx, call)                                                                              \
     do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            (ctx)->error = std::string(#call) + ": " + hipGetErrorString(e_);                           \
-            return LAMA_HIP_E_HIP;                                                                     \
-        }                                                                                              \
+        const hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess) return hip_fail((ctx), e_, #call);                                       \
     } while (0)
 
 int32_t fail(lama_hip_ctx* ctx, int32_t code, const std::string& msg)
@@ -280,12 +337,7 @@ int32_t upload_scan(lama_hip_ctx* c, const double* pts, uint32_t n)
         return LAMA_HIP_OK;
     }
     c->last_n = n;
-    if (n > c->pts_cap) {
-        if (c->d_pts) HIPCHK(c, hipFree(c->d_pts));
-        c->d_pts = nullptr;
-        c->pts_cap = std::max<uint32_t>(n, 2048);
-        HIPCHK(c, hipMalloc(&c->d_pts, sizeof(double) * 3 * c->pts_cap));
-    }
+    HIPCHK(c, c->d_pts.grow((size_t)3 * n, (size_t)3 * 2048));
     c->h_pts.resize((size_t)3 * n);                       // the caller's buffer is only borrowed for the call
     std::memcpy(c->h_pts.data(), pts, sizeof(double) * 3 * n);
     double r2 = 0.0;
@@ -294,6 +346,18 @@ int32_t upload_scan(lama_hip_ctx* c, const double* pts, uint32_t n)
     if (!std::isfinite(r2)) { c->last_n = 0; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
     c->scan_reach = std::sqrt(r2);
     HIPCHK(c, hipMemcpyAsync(c->d_pts, c->h_pts.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    return LAMA_HIP_OK;
+}
+
+// the batch buffers hold at least `entries` results (d_bout, whose count is their capacity) and four pose doubles per entry
+// (d_bposes); both are freed before the larger pair is allocated
+int32_t ensure_batch(lama_hip_ctx* c, size_t entries, size_t floor = 0)
+{
+    if (entries <= c->d_bout.n) return LAMA_HIP_OK;
+    c->d_bposes.reset(); c->d_bout.reset();
+    const size_t cap = std::max(entries, floor);
+    HIPCHK(c, c->d_bposes.alloc(4 * cap));
+    HIPCHK(c, c->d_bout.alloc(cap));
     return LAMA_HIP_OK;
 }
 
@@ -459,22 +523,21 @@ int32_t add_chunk(lama_hip_ctx* c, bool dm, uint32_t min_patches)
             return fail(c, LAMA_HIP_E_CAPACITY, std::string(dm ? "distance-map" : "occupancy") + " pool: the device has no room for " + std::to_string(min_patches) + " more patches");
     }
     if (want > 0xFFFFFFF0ull) want = 0xFFFFFFF0ull;
-    PoolChunk k;
+    PoolChunk k;                                                    // (its planes free themselves if a later one fails)
     k.patches = (uint32_t)want;
     const int nplanes = dm ? 3 : 4;
     for (int i = 0; i < nplanes; ++i) {
         const size_t bytes = (size_t)k.patches * (dm ? DM_PLANE_B[i] : OCC_PLANE_B[i]);
-        hipError_t e = hipMalloc(&k.plane[i], bytes);
+        hipError_t e = k.plane[i].alloc(bytes);
         if (e == hipSuccess && !(!dm && i == 3)) e = hipMemsetAsync(k.plane[i], 0, bytes, c->stream);     // (rev is rebuilt per scan)
         if (e != hipSuccess) {
-            for (int j = 0; j <= i; ++j) (void)hipFree(k.plane[j]);
             (void)hipGetLastError();
             return fail(c, LAMA_HIP_E_CAPACITY, std::string(dm ? "distance-map" : "occupancy") + " pool: " + hipGetErrorString(e));
         }
     }
-    chunks.push_back(k);
+    chunks.push_back(std::move(k));
     (dm ? c->ra_dm : c->ra_occ).emplace_back();
-    (dm ? c->ra_dm : c->ra_occ).back().reset(k.patches);
+    (dm ? c->ra_dm : c->ra_occ).back().reset(chunks.back().patches);
     c->ctr.pool_growths += 1;
     return LAMA_HIP_OK;
 }
@@ -499,23 +562,6 @@ static void region_ptrs(const lama_hip_ctx* c, const HostPart& h, void* out[5])
     out[0] = r.dm_sv; out[1] = r.dm_obs; out[2] = r.dm_mask; out[3] = r.occ; out[4] = r.occ_mask;
 }
 
-static int32_t ensure_job_buffers(lama_hip_ctx* c, uint32_t nj, uint32_t nz)
-{
-    if (nj > c->jobs_cap) {
-        (void)hipFree(c->d_jobs); c->d_jobs = nullptr; c->jobs_cap = 0;
-        const uint32_t cap = std::max<uint32_t>(nj, 256u);
-        HIPCHK(c, hipMalloc(&c->d_jobs, sizeof(CloneJob) * cap));
-        c->jobs_cap = cap;
-    }
-    if (nz > c->zjobs_cap) {
-        (void)hipFree(c->d_zjobs); c->d_zjobs = nullptr; c->zjobs_cap = 0;
-        const uint32_t cap = std::max<uint32_t>(nz, 256u);
-        HIPCHK(c, hipMalloc(&c->d_zjobs, sizeof(ZeroJob) * cap));
-        c->zjobs_cap = cap;
-    }
-    return LAMA_HIP_OK;
-}
-
 // run the jobs in c->h_jobs / c->h_zjobs: `zero_first` = the zero jobs free regions no job reads (resample); else they free the jobs'
 // own sources (growth) and run behind the copies
 // (j0 / z0: the jobs from these positions of the staging lists on -- set_capacities queues group after group without a host round
@@ -524,8 +570,8 @@ static int32_t run_jobs(lama_hip_ctx* c, bool zero_first, size_t j0 = 0, size_t 
 {
     const uint32_t nj = (uint32_t)(c->h_jobs.size() - j0), nz = (uint32_t)(c->h_zjobs.size() - z0);
     if (nj == 0 && nz == 0) return LAMA_HIP_OK;
-    const int32_t rb = ensure_job_buffers(c, nj, nz);
-    if (rb) return rb;
+    HIPCHK(c, c->d_jobs.grow(nj, 256));
+    HIPCHK(c, c->d_zjobs.grow(nz, 256));
     const DevParams prm = make_params(c);
     if (nj) HIPCHK(c, hipMemcpyAsync(c->d_jobs, c->h_jobs.data() + j0, sizeof(CloneJob) * nj, hipMemcpyHostToDevice, c->stream));
     if (nz) HIPCHK(c, hipMemcpyAsync(c->d_zjobs, c->h_zjobs.data() + z0, sizeof(ZeroJob) * nz, hipMemcpyHostToDevice, c->stream));
@@ -701,11 +747,8 @@ struct Timer {
     Timer(lama_hip_ctx* c_, double* acc_, uint64_t* l_) : c(c_), acc(acc_), launches(l_)
     {
         if (!c->cfg.profile) return;
-        if (c->ev_used + 2 > c->ev_pool.size()) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-            c->ev_pool.push_back(e0); c->ev_pool.push_back(e1);
-        }
+        if (c->ev_used + 2 > c->ev_pool.size())
+            for (int i = 0; i < 2; ++i) { c->ev_pool.emplace_back(); (void)hipEventCreate(&c->ev_pool.back().h); }
         a = c->ev_pool[c->ev_used++]; b = c->ev_pool[c->ev_used++];
         (void)hipEventRecord(a, c->stream);
     }
@@ -749,28 +792,27 @@ int32_t regrid_window(lama_hip_ctx* c, uint32_t newW, int64_t nox, int64_t noy)
     if (!c->initialised && newW == c->W) { c->wx0 = (uint32_t)(nox * 32); c->wy0 = (uint32_t)(noy * 32); return LAMA_HIP_OK; }   // nothing mapped yet
     // both directories of every home are re-tiled into fresh arrays (same side: a permutation; larger side: the window grew), then the
     // old arrays are released.  A failed allocation leaves the window as it was (nothing leaks).
-    MapStore& m = c->ms;
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && 2 * P * nWW * 2 + (1ull << 28) > free_b)
             return fail(c, LAMA_HIP_E_WINDOW, "not enough device memory to re-tile the window directories (" + std::to_string(2 * P * nWW * 2 >> 20) + " MB for a " + std::to_string(newW) + "-patch window)");
     }
-    int16_t* nd[2] = {nullptr, nullptr};
+    DevBuf<int16_t> nd[2];
     for (int k = 0; k < 2; ++k) {
-        hipError_t e = hipMalloc(&nd[k], P * nWW * 2);
+        hipError_t e = nd[k].alloc(P * nWW);
         if (e == hipSuccess && newW != c->W) e = hipMemsetAsync(nd[k], 0xFF, P * nWW * 2, c->stream);
-        if (e != hipSuccess) { (void)hipFree(nd[0]); (void)hipFree(nd[1]); c->error = std::string("window directories: ") + hipGetErrorString(e); return LAMA_HIP_E_HIP; }
+        if (e != hipSuccess) return hip_fail(c, e, "window directories");
     }
     const dim3 grid((unsigned)P, (unsigned)((std::max(WW, nWW) + 255) / 256));
-    hipLaunchKernelGGL(k_shift_window, grid, dim3(256), 0, c->stream, m.dm_dir, nd[0], c->W, newW, dx, dy, WW, nWW, c->d_err);
-    hipLaunchKernelGGL(k_shift_window, grid, dim3(256), 0, c->stream, m.occ_dir, nd[1], c->W, newW, dx, dy, WW, nWW, c->d_err);
+    int16_t* const to_dm = nd[0]; int16_t* const to_occ = nd[1];   // (launch arguments are plain pointers: the owners are not copied)
+    hipLaunchKernelGGL(k_shift_window, grid, dim3(256), 0, c->stream, c->ms.dm_dir, to_dm, c->W, newW, dx, dy, WW, nWW, c->d_err);
+    hipLaunchKernelGGL(k_shift_window, grid, dim3(256), 0, c->stream, c->ms.occ_dir, to_occ, c->W, newW, dx, dy, WW, nWW, c->d_err);
     {
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { (void)hipFree(nd[0]); (void)hipFree(nd[1]); c->error = std::string("k_shift_window: ") + hipGetErrorString(e); return LAMA_HIP_E_HIP; }
+        if (e != hipSuccess) return hip_fail(c, e, "k_shift_window");
     }
-    (void)hipFree(m.dm_dir); (void)hipFree(m.occ_dir);
-    m.dm_dir = nd[0]; m.occ_dir = nd[1];
+    c->ms.dm_dir.swap(nd[0]); c->ms.occ_dir.swap(nd[1]);           // (the old directories are released with nd)
     if (newW != c->W) {
         c->W = newW; c->WC = newW * 32; c->cfg.window_patches = newW;
         c->ctr.window_growths += 1;
@@ -843,12 +885,12 @@ static unsigned xcd_grid(const lama_hip_ctx* c, uint32_t first, uint32_t count)
 int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only)
 {
     const size_t need = (size_t)c->P * n;
-    if (need > c->rrec_cap) {
-        (void)hipFree(c->d_rrec); (void)hipFree(c->d_rbbox); (void)hipFree(c->d_rchunk); c->d_rrec = nullptr; c->d_rbbox = nullptr; c->d_rchunk = nullptr; c->rrec_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_rrec, need * sizeof(lama_dev::RayRec)));
-        HIPCHK(c, hipMalloc(&c->d_rbbox, need * sizeof(uint64_t)));
-        HIPCHK(c, hipMalloc(&c->d_rchunk, (size_t)c->P * ((n + 63) / 64) * sizeof(lama_dev::RayChunk)));     // per 64 beams of a particle
-        c->rrec_cap = need;
+    if (need > c->d_rrec.n) {                                       // all three are freed before any is allocated
+        c->d_rrec.reset(); c->d_rbbox.reset(); c->d_rchunk.reset();
+        hipError_t e = c->d_rrec.alloc(need);
+        if (e == hipSuccess) e = c->d_rbbox.alloc(need);
+        if (e == hipSuccess) e = c->d_rchunk.alloc((size_t)c->P * ((n + 63) / 64));     // per 64 beams of a particle
+        if (e != hipSuccess) { c->d_rrec.reset(); return hip_fail(c, e, "ray buffers"); }
     }
     hipLaunchKernelGGL(k_ray_hits, dim3(xcd_grid(c, first, count), (n + 255) / 256), dim3(256), 0, c->stream, prm, c->d_pts, (int)n, c->d_tfs, (int)first,
                        c->d_rrec, c->d_rbbox, alloc_only, c->d_rchunk);
@@ -1198,7 +1240,8 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg_in, lama_hip_ctx** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg.device < 0 || cfg.device >= ndev) return LAMA_HIP_E_HIP;
 
-    lama_hip_ctx* c = new lama_hip_ctx();
+    std::unique_ptr<lama_hip_ctx, Delete> owner(new lama_hip_ctx());       // (released into *out on success only)
+    lama_hip_ctx* c = owner.get();
     c->cfg = cfg;
     std::memset(&c->ctr, 0, sizeof(c->ctr));
     c->P = cfg.particles; c->W = cfg.window_patches; c->WC = c->W * 32;
@@ -1229,37 +1272,35 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg_in, lama_hip_ctx** out)
     c->max_sqdist = md * md;
     // this build's queue entries carry obstacle offsets up to MAX_OFFSET_CELLS and its distance plane that range squared: 127 cells
     // in liblama_hip.so, 255 -- all that the reference's uint16_t sqdist can hold -- in liblama_hip_wide.so (lama_dev.h)
-    if (c->max_sqdist == 0 || md > MAX_OFFSET_CELLS) { delete c; return LAMA_HIP_E_INVALID; }
+    if (c->max_sqdist == 0 || md > MAX_OFFSET_CELLS) return LAMA_HIP_E_INVALID;
 
-#define CHK(call) do { if ((call) != hipSuccess) { lama_hip_ctx_destroy(c); return LAMA_HIP_E_HIP; } } while (0)
-    CHK(hipSetDevice(cfg.device));
+    // (hipSuccess is 0: each condition below stops at its first failing call)
+    if (hipSetDevice(cfg.device)) return LAMA_HIP_E_HIP;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) c->num_cus = (uint32_t)prop.multiProcessorCount; }
-    CHK(hipStreamCreate(&c->stream));
-    CHK(hipEventCreate(&c->ev0));
-    CHK(hipEventCreate(&c->ev1));
+    if (hipStreamCreate(&c->stream.h) || hipEventCreate(&c->ev0.h) || hipEventCreate(&c->ev1.h)) return LAMA_HIP_E_HIP;
     const size_t P = c->P, WW = (size_t)c->W * c->W, dc = cfg.dm_patch_capacity, oc = cfg.occ_patch_capacity;
     {
         // one particle set: directories per home, pooled planes with one region per particle and map kind (lama_dev.h).  The pools
         // start at P x the configured capacities and grow with the maps.
         MapStore& m = c->ms;
         c->floor_dm = (uint32_t)dc; c->floor_occ = (uint32_t)oc;
-        if (P * dc > 0xFFFFFFF0ull || P * oc > 0xFFFFFFF0ull) { lama_hip_ctx_destroy(c); return LAMA_HIP_E_INVALID; }
-        CHK(hipMalloc(&m.dm_dir, P * WW * 2));                 CHK(hipMemset(m.dm_dir, 0xFF, P * WW * 2));
-        CHK(hipMalloc(&m.occ_dir, P * WW * 2));                CHK(hipMemset(m.occ_dir, 0xFF, P * WW * 2));
+        if (P * dc > 0xFFFFFFF0ull || P * oc > 0xFFFFFFF0ull) return LAMA_HIP_E_INVALID;
+        if (m.dm_dir.alloc(P * WW) || hipMemset(m.dm_dir, 0xFF, P * WW * 2)) return LAMA_HIP_E_HIP;
+        if (m.occ_dir.alloc(P * WW) || hipMemset(m.occ_dir, 0xFF, P * WW * 2)) return LAMA_HIP_E_HIP;
         // (m.counts lives in the results / status block below: one copy brings a map update's counters back)
         // first chunk of each pool: P regions of the configured capacity
-        if (add_chunk(c, true, (uint32_t)(P * dc)) != LAMA_HIP_OK || add_chunk(c, false, (uint32_t)(P * oc)) != LAMA_HIP_OK) { lama_hip_ctx_destroy(c); return LAMA_HIP_E_HIP; }
+        if (add_chunk(c, true, (uint32_t)(P * dc)) != LAMA_HIP_OK || add_chunk(c, false, (uint32_t)(P * oc)) != LAMA_HIP_OK) return LAMA_HIP_E_HIP;
         c->ctr.pool_growths = 0;
         c->h_part.resize(P);
         for (size_t p = 0; p < P; ++p) {
             HostPart r{};
             r.home = (uint32_t)p; r.dm_cap = (uint32_t)dc; r.occ_cap = (uint32_t)oc;
-            if (region_alloc(c, true, (uint32_t)dc, r.dm_chunk, r.dm_off) != LAMA_HIP_OK || region_alloc(c, false, (uint32_t)oc, r.occ_chunk, r.occ_off) != LAMA_HIP_OK) { lama_hip_ctx_destroy(c); return LAMA_HIP_E_HIP; }
+            if (region_alloc(c, true, (uint32_t)dc, r.dm_chunk, r.dm_off) != LAMA_HIP_OK || region_alloc(c, false, (uint32_t)oc, r.occ_chunk, r.occ_off) != LAMA_HIP_OK) return LAMA_HIP_E_HIP;
             c->h_part[p] = r;
         }
-        CHK(hipMalloc(&c->d_part, P * sizeof(PartRec)));
-        if (upload_part(c) != LAMA_HIP_OK) { lama_hip_ctx_destroy(c); return LAMA_HIP_E_HIP; }
-        CHK(hipStreamSynchronize(c->stream));
+        if (c->d_part.alloc(P)) return LAMA_HIP_E_HIP;
+        if (upload_part(c) != LAMA_HIP_OK) return LAMA_HIP_E_HIP;
+        if (hipStreamSynchronize(c->stream)) return LAMA_HIP_E_HIP;
     }
     // ONE allocation: [poses | loglik | iters | err]   what a scan match brings back (results_bytes, one copy) ...
     //                 [err | slow_n | stats | guard | counts]   ... and what a map update brings back (status_bytes from status_off, one
@@ -1269,8 +1310,8 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg_in, lama_hip_ctx** out)
     c->status_off = P * 4 * 8 + P * 8 + P * 4;                                  // the error word: last of the results, first of the status
     const size_t slow_off = (c->results_bytes + 7) / 8 * 8;
     c->status_bytes = (slow_off - c->status_off) + 32 + P * 4 * 8 + P * 2 * 4 + P * 2 * 4;
-    CHK(hipMalloc(&c->d_results, c->status_off + c->status_bytes));   CHK(hipMemset(c->d_results, 0, c->status_off + c->status_bytes));
-    c->d_poses = reinterpret_cast<double*>(c->d_results);
+    if (c->d_results.alloc(c->status_off + c->status_bytes) || hipMemset(c->d_results, 0, c->status_off + c->status_bytes)) return LAMA_HIP_E_HIP;
+    c->d_poses = reinterpret_cast<double*>(c->d_results.p);
     c->d_loglik = c->d_poses + P * 4;
     c->d_iters = reinterpret_cast<int32_t*>(c->d_loglik + P);
     c->d_err = c->d_iters + P;
@@ -1278,63 +1319,32 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg_in, lama_hip_ctx** out)
     c->d_stats = reinterpret_cast<uint64_t*>(c->d_results + slow_off + 32);
     c->d_guard = reinterpret_cast<uint32_t*>(c->d_stats + P * 4);
     c->ms.counts = reinterpret_cast<int32_t*>(c->d_guard + P * 2);
-    CHK(hipMalloc(&c->d_qlower, P * (size_t)cfg.queue_capacity * 8));
-    CHK(hipMalloc(&c->d_qraise, P * (size_t)cfg.queue_capacity * 8));
-    CHK(hipMalloc(&c->d_qsizes, P * 2 * 4));         CHK(hipMemset(c->d_qsizes, 0, P * 2 * 4));
-    CHK(hipMalloc(&c->d_dbg, P * 16 * 8 + (1u << 20)));   CHK(hipMemset(c->d_dbg, 0, P * 16 * 8 + (1u << 20)));   // + 1 MiB developer event log
-    CHK(hipMalloc(&c->d_slow, P * 4));               CHK(hipMemset(c->d_slow, 0, P * 4));
-    CHK(hipMalloc(&c->d_slow_list, 4 * P * 4));      CHK(hipMemset(c->d_slow_list, 0, 4 * P * 4));
-    CHK(hipMalloc(&c->d_heavy, P));                  CHK(hipMemset(c->d_heavy, 0, P));
-    CHK(hipMalloc(&c->d_early, P));                  CHK(hipMemset(c->d_early, 0, P));
-    CHK(hipMalloc(&c->d_elist, 256 * 4));            CHK(hipMemset(c->d_elist, 0, 256 * 4));
-    CHK(hipMalloc(&c->d_hlist, 256 * 4));            CHK(hipMemset(c->d_hlist, 0, 256 * 4));
-    CHK(hipStreamCreate(&c->stream2));
-    CHK(hipStreamCreate(&c->stream3));
-    CHK(hipEventCreateWithFlags(&c->ev_alloc, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&c->ev_early, hipEventDisableTiming));
-    CHK(hipEventCreateWithFlags(&c->ev_go, hipEventDisableTiming));
-    CHK(hipEventCreateWithFlags(&c->ev_route, hipEventDisableTiming)); CHK(hipEventCreateWithFlags(&c->ev_heavy, hipEventDisableTiming));
-    CHK(hipMalloc(&c->d_scalar, 16));                CHK(hipMemset(c->d_scalar, 0, 16));
-    CHK(hipMalloc(&c->d_act, P * (size_t)cfg.active_capacity * 8));
-    CHK(hipMalloc(&c->d_act_count, P * 4));          CHK(hipMemset(c->d_act_count, 0, P * 4));
-    CHK(hipMalloc(&c->d_tfs, P * 12 * 8));
-    CHK(hipMalloc(&c->d_oldcounts, P * 2 * 4));
-    CHK(hipDeviceSynchronize());
-#undef CHK
+    if (c->d_qlower.alloc(P * (size_t)cfg.queue_capacity) || c->d_qraise.alloc(P * (size_t)cfg.queue_capacity)) return LAMA_HIP_E_HIP;
+    if (c->d_qsizes.alloc(P * 2) || hipMemset(c->d_qsizes, 0, P * 2 * 4)) return LAMA_HIP_E_HIP;
+    if (c->d_dbg.alloc(P * 16 + (1u << 20) / 8) || hipMemset(c->d_dbg, 0, P * 16 * 8 + (1u << 20))) return LAMA_HIP_E_HIP;   // + 1 MiB developer event log
+    if (c->d_slow.alloc(P) || hipMemset(c->d_slow, 0, P * 4)) return LAMA_HIP_E_HIP;
+    if (c->d_slow_list.alloc(4 * P) || hipMemset(c->d_slow_list, 0, 4 * P * 4)) return LAMA_HIP_E_HIP;
+    if (c->d_heavy.alloc(P) || hipMemset(c->d_heavy, 0, P)) return LAMA_HIP_E_HIP;
+    if (c->d_early.alloc(P) || hipMemset(c->d_early, 0, P)) return LAMA_HIP_E_HIP;
+    if (c->d_elist.alloc(256) || hipMemset(c->d_elist, 0, 256 * 4)) return LAMA_HIP_E_HIP;
+    if (c->d_hlist.alloc(256) || hipMemset(c->d_hlist, 0, 256 * 4)) return LAMA_HIP_E_HIP;
+    if (hipStreamCreate(&c->stream2.h) || hipStreamCreate(&c->stream3.h)) return LAMA_HIP_E_HIP;
+    if (hipEventCreateWithFlags(&c->ev_alloc.h, hipEventDisableTiming) || hipEventCreateWithFlags(&c->ev_early.h, hipEventDisableTiming) ||
+        hipEventCreateWithFlags(&c->ev_go.h, hipEventDisableTiming) ||
+        hipEventCreateWithFlags(&c->ev_route.h, hipEventDisableTiming) || hipEventCreateWithFlags(&c->ev_heavy.h, hipEventDisableTiming))
+        return LAMA_HIP_E_HIP;
+    if (c->d_scalar.alloc(4) || hipMemset(c->d_scalar, 0, 16)) return LAMA_HIP_E_HIP;
+    if (c->d_act.alloc(P * (size_t)cfg.active_capacity)) return LAMA_HIP_E_HIP;
+    if (c->d_act_count.alloc(P) || hipMemset(c->d_act_count, 0, P * 4)) return LAMA_HIP_E_HIP;
+    if (c->d_tfs.alloc(P * 12) || c->d_oldcounts.alloc(P * 2)) return LAMA_HIP_E_HIP;
+    if (hipDeviceSynchronize()) return LAMA_HIP_E_HIP;
     c->h_poses.assign(P * 4, 0.0);
     c->h_counts.assign(P * 2, 0);
-    *out = c;
+    *out = owner.release();
     return LAMA_HIP_OK;
 }
 
-void lama_hip_ctx_destroy(lama_hip_ctx* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->cfg.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    {
-        MapStore& m = c->ms;
-        (void)hipFree(m.dm_dir); (void)hipFree(m.occ_dir);
-        for (PoolChunk& k : m.dm_chunks) for (int i = 0; i < 4; ++i) (void)hipFree(k.plane[i]);
-        for (PoolChunk& k : m.occ_chunks) for (int i = 0; i < 4; ++i) (void)hipFree(k.plane[i]);
-        (void)hipFree(c->d_part); (void)hipFree(c->d_jobs); (void)hipFree(c->d_zjobs);
-    }
-    (void)hipFree(c->d_results); (void)hipFree(c->d_qlower); (void)hipFree(c->d_qraise); (void)hipFree(c->d_qsizes); (void)hipFree(c->d_dbg); (void)hipFree(c->d_slow); (void)hipFree(c->d_slow_list); (void)hipFree(c->d_heavy); (void)hipFree(c->d_early); (void)hipFree(c->d_elist); (void)hipFree(c->d_hlist); (void)hipFree(c->d_scalar);  (void)hipFree(c->d_ship_desc); (void)hipFree(c->d_ship_heads); (void)hipFree(c->d_act); (void)hipFree(c->d_act_count); (void)hipFree(c->d_rrec); (void)hipFree(c->d_rbbox); (void)hipFree(c->d_rchunk);
-    (void)hipFree(c->d_pts); (void)hipFree(c->d_tfs);
-    (void)hipFree(c->d_oldcounts);
-    (void)hipFree(c->d_bposes); (void)hipFree(c->d_bout);
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream3) (void)hipStreamDestroy(c->stream3);
-    if (c->ev_alloc) (void)hipEventDestroy(c->ev_alloc);
-    if (c->ev_early) (void)hipEventDestroy(c->ev_early);
-    if (c->ev_go) (void)hipEventDestroy(c->ev_go);
-    if (c->ev_route) (void)hipEventDestroy(c->ev_route);
-    if (c->ev_heavy) (void)hipEventDestroy(c->ev_heavy);
-    delete c;
-}
+void lama_hip_ctx_destroy(lama_hip_ctx* c) { delete c; }
 
 int32_t lama_hip_pf_set_poses(lama_hip_ctx* c, const double* poses)
 {
@@ -1497,15 +1507,14 @@ int32_t lama_hip_pf_map_checksums(lama_hip_ctx* c, int32_t kind, uint64_t* out)
     ENTER(c);
     if (c->cfg.occupancy_policy != 0 && kind == LAMA_HIP_MAP_OCCUPANCY) return fail(c, LAMA_HIP_E_INVALID, "map checksums cover the frequency occupancy policy");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    uint64_t* d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_out, sizeof(uint64_t) * c->P));
+    DevBuf<uint64_t> sums;
+    HIPCHK(c, sums.alloc(c->P));
+    uint64_t* const d_out = sums;                                   // (launch arguments are plain pointers: the owners are not copied)
     DevParams prm = make_params(c);
     hipLaunchKernelGGL(k_map_checksum, dim3(c->P), dim3(256), 0, c->stream, prm, kind == LAMA_HIP_MAP_DISTANCE ? 0 : 1, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(uint64_t) * c->P, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
-    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(uint64_t) * c->P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LAMA_HIP_OK;
 }
 
@@ -1748,13 +1757,8 @@ int32_t lama_hip_match_batch(lama_hip_ctx* c, uint32_t particle, const double* p
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
-    if (B > c->b_cap) {
-        (void)hipFree(c->d_bposes); (void)hipFree(c->d_bout);
-        c->d_bposes = nullptr; c->d_bout = nullptr; c->b_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_bposes, sizeof(double) * 4 * B));
-        HIPCHK(c, hipMalloc(&c->d_bout, sizeof(double) * B));
-        c->b_cap = B;
-    }
+    rc = ensure_batch(c, B);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bposes, poses, sizeof(double) * 4 * B, hipMemcpyHostToDevice, c->stream));
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
@@ -1775,13 +1779,8 @@ int32_t lama_hip_eval_batch(lama_hip_ctx* c, uint32_t particle, const double* pt
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
-    if (2 * B > c->b_cap) {
-        (void)hipFree(c->d_bposes); (void)hipFree(c->d_bout);
-        c->d_bposes = nullptr; c->d_bout = nullptr; c->b_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_bposes, sizeof(double) * 4 * 2 * B));
-        HIPCHK(c, hipMalloc(&c->d_bout, sizeof(double) * 2 * B));
-        c->b_cap = 2 * B;
-    }
+    rc = ensure_batch(c, 2 * (size_t)B);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bposes, poses, sizeof(double) * 4 * B, hipMemcpyHostToDevice, c->stream));
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
@@ -1809,13 +1808,8 @@ int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
-    if (2 * K > c->b_cap) {
-        (void)hipFree(c->d_bposes); (void)hipFree(c->d_bout);
-        c->d_bposes = nullptr; c->d_bout = nullptr; c->b_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_bposes, sizeof(double) * 4 * 2 * K));
-        HIPCHK(c, hipMalloc(&c->d_bout, sizeof(double) * 2 * K));
-        c->b_cap = 2 * K;
-    }
+    rc = ensure_batch(c, 2 * (size_t)K);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bposes, xy, sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream));
     // (Translation(x, y, 0) * AngleAxis(yaw, Z)) * moving_tf without the per-sample translation (src/loc2d.cpp:211-224)
     const Affine mtf = moving_tf(origin3, quat);
@@ -1843,19 +1837,18 @@ int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const
 struct lama_hip_pgo {
     int32_t device = 0;
     uint32_t N = 0, F = 0, blocksF = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double *d_poses = nullptr, *d_meas = nullptr, *d_sqrt = nullptr, *d_err = nullptr, *d_hoff = nullptr, *d_fdi = nullptr, *d_fdj = nullptr,
-           *d_fg = nullptr, *d_hdiag = nullptr, *d_b = nullptr, *d_chi = nullptr;
-    int32_t *d_fi = nullptr, *d_fj = nullptr, *d_incptr = nullptr, *d_inc = nullptr;
+    Stream stream;
+    Event ev0, ev1;
+    DevBuf<double> d_poses, d_meas, d_sqrt, d_err, d_hoff, d_fdi, d_fdj, d_fg, d_hdiag, d_b, d_chi;
+    DevBuf<int32_t> d_fi, d_fj, d_incptr, d_inc;
     std::vector<double> h_chi;
     std::string error;
+
+    __attribute__((visibility("hidden"))) ~lama_hip_pgo() { (void)hipSetDevice(device); }     // (not exported: the C-ABI is)
 };
 
 #define PGOCHK(g, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (g)->error = std::string(#call) + ": " + hipGetErrorString(e_); return LAMA_HIP_E_HIP; } } while (0)
 
-void lama_hip_pgo_destroy(lama_hip_pgo* g);
-#define PGOCHK_C(call) do { if ((call) != hipSuccess) { lama_hip_pgo_destroy(p); return LAMA_HIP_E_HIP; } } while (0)
 int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const int32_t* fj, const double* meas4, const double* sqrt_info3,
                             uint32_t F, lama_hip_pgo** out)
 {
@@ -1866,7 +1859,7 @@ int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device || device < 0) return LAMA_HIP_E_HIP;
     if (hipSetDevice(device) != hipSuccess) return LAMA_HIP_E_HIP;
-    lama_hip_pgo* p = new lama_hip_pgo;
+    std::unique_ptr<lama_hip_pgo, Delete> p(new lama_hip_pgo);             // (released into *out on success only)
     p->device = device; p->N = N; p->F = F; p->blocksF = (F + PGO_BLOCK - 1) / PGO_BLOCK;
     // incidence lists in factor order (counting sort): what the reference's sequential loop over the factors adds to a variable
     std::vector<int32_t> ptr(N + 1, 0), inc;
@@ -1875,38 +1868,25 @@ int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const
     inc.resize(ptr[N]);
     std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
     for (uint32_t k = 0; k < F; ++k) { inc[fill[fi[k]]++] = (int32_t)(2 * k); if (fj[k] >= 0) inc[fill[fj[k]]++] = (int32_t)(2 * k + 1); }
-    PGOCHK_C(hipStreamCreate(&p->stream));
-    PGOCHK_C(hipEventCreate(&p->ev0)); PGOCHK_C(hipEventCreate(&p->ev1));
-    PGOCHK_C(hipMalloc(&p->d_poses, sizeof(double) * 4 * N)); PGOCHK_C(hipMalloc(&p->d_meas, sizeof(double) * 4 * F));
-    PGOCHK_C(hipMalloc(&p->d_sqrt, sizeof(double) * 3 * F)); PGOCHK_C(hipMalloc(&p->d_err, sizeof(double) * 3 * F));
-    PGOCHK_C(hipMalloc(&p->d_hoff, sizeof(double) * 9 * F)); PGOCHK_C(hipMalloc(&p->d_fdi, sizeof(double) * 9 * F));
-    PGOCHK_C(hipMalloc(&p->d_fdj, sizeof(double) * 9 * F)); PGOCHK_C(hipMalloc(&p->d_fg, sizeof(double) * 6 * F));
-    PGOCHK_C(hipMalloc(&p->d_hdiag, sizeof(double) * 9 * N)); PGOCHK_C(hipMalloc(&p->d_b, sizeof(double) * 3 * N));
-    PGOCHK_C(hipMalloc(&p->d_chi, sizeof(double) * p->blocksF));
-    PGOCHK_C(hipMalloc(&p->d_fi, sizeof(int32_t) * F)); PGOCHK_C(hipMalloc(&p->d_fj, sizeof(int32_t) * F));
-    PGOCHK_C(hipMalloc(&p->d_incptr, sizeof(int32_t) * (N + 1))); PGOCHK_C(hipMalloc(&p->d_inc, sizeof(int32_t) * std::max<size_t>(inc.size(), 1)));
-    PGOCHK_C(hipMemcpy(p->d_fi, fi, sizeof(int32_t) * F, hipMemcpyHostToDevice)); PGOCHK_C(hipMemcpy(p->d_fj, fj, sizeof(int32_t) * F, hipMemcpyHostToDevice));
-    PGOCHK_C(hipMemcpy(p->d_meas, meas4, sizeof(double) * 4 * F, hipMemcpyHostToDevice));
-    PGOCHK_C(hipMemcpy(p->d_sqrt, sqrt_info3, sizeof(double) * 3 * F, hipMemcpyHostToDevice));
-    PGOCHK_C(hipMemcpy(p->d_incptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice));
-    PGOCHK_C(hipMemcpy(p->d_inc, inc.data(), sizeof(int32_t) * inc.size(), hipMemcpyHostToDevice));
+    // (hipSuccess is 0: each condition below stops at its first failing call)
+    if (hipStreamCreate(&p->stream.h) || hipEventCreate(&p->ev0.h) || hipEventCreate(&p->ev1.h)) return LAMA_HIP_E_HIP;
+    if (p->d_poses.alloc(4 * (size_t)N) || p->d_meas.alloc(4 * (size_t)F) || p->d_sqrt.alloc(3 * (size_t)F) || p->d_err.alloc(3 * (size_t)F) ||
+        p->d_hoff.alloc(9 * (size_t)F) || p->d_fdi.alloc(9 * (size_t)F) || p->d_fdj.alloc(9 * (size_t)F) || p->d_fg.alloc(6 * (size_t)F) ||
+        p->d_hdiag.alloc(9 * (size_t)N) || p->d_b.alloc(3 * (size_t)N) || p->d_chi.alloc(p->blocksF) ||
+        p->d_fi.alloc(F) || p->d_fj.alloc(F) || p->d_incptr.alloc((size_t)N + 1) || p->d_inc.alloc(std::max<size_t>(inc.size(), 1)))
+        return LAMA_HIP_E_HIP;
+    if (hipMemcpy(p->d_fi, fi, sizeof(int32_t) * F, hipMemcpyHostToDevice) || hipMemcpy(p->d_fj, fj, sizeof(int32_t) * F, hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_meas, meas4, sizeof(double) * 4 * F, hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_sqrt, sqrt_info3, sizeof(double) * 3 * F, hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_incptr, ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_inc, inc.data(), sizeof(int32_t) * inc.size(), hipMemcpyHostToDevice))
+        return LAMA_HIP_E_HIP;
     p->h_chi.resize(p->blocksF);
-    *out = p;
+    *out = p.release();
     return LAMA_HIP_OK;
 }
 
-void lama_hip_pgo_destroy(lama_hip_pgo* g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    void* ptrs[] = {g->d_poses, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_hdiag, g->d_b, g->d_chi,
-                    g->d_fi, g->d_fj, g->d_incptr, g->d_inc};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-}
+void lama_hip_pgo_destroy(lama_hip_pgo* g) { delete g; }
 
 const char* lama_hip_pgo_last_error(const lama_hip_pgo* g) { return g ? g->error.c_str() : "null handle"; }
 
@@ -1979,23 +1959,22 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
         }
         c->last_guarded = false;
     }
-    uint32_t* d_cells = nullptr;
-    HIPCHK(c, hipMalloc(&d_cells, sizeof(uint32_t) * 2 * (size_t)n));
+    DevBuf<uint32_t> cells;
+    HIPCHK(c, cells.alloc(2 * (size_t)n));
+    uint32_t* const d_cells = cells;                                // (launch arguments are plain pointers: the owners are not copied)
     HIPCHK(c, hipMemcpyAsync(d_cells, cells_xy, sizeof(uint32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     DevParams prm = make_params(c);
     // queue capacity bounds one batch of additions; larger lists go in slices (each followed by dm->update(): adding
     // obstacles then updating in slices yields the same distance map only if no slice boundary matters -- so a list
     // longer than the queue is rejected instead)
-    if (n > c->cfg.queue_capacity) { (void)hipFree(d_cells); return fail(c, LAMA_HIP_E_CAPACITY, "more obstacle cells than cfg.queue_capacity"); }
+    if (n > c->cfg.queue_capacity) return fail(c, LAMA_HIP_E_CAPACITY, "more obstacle cells than cfg.queue_capacity");
     HIPCHK(c, hipMemsetAsync(c->d_slow_n, 0, 5 * sizeof(uint32_t), c->stream));    // all five: check_device_errors(maps) adds every word to the counters
     hipLaunchKernelGGL(k_dm_add_obstacles, dim3(1), dim3(UM_BLOCK), 0, c->stream, prm, (int)particle, d_cells, n);
     hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(1), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)particle, 0);
     hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(1), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)particle, 0);
     hipLaunchKernelGGL(k_brushfire_slow, dim3(1), dim3(UM_BLOCK), 0, c->stream, prm, (int)particle);
     HIPCHK(c, hipGetLastError());
-    int32_t rc = check_device_errors(c, true, false);
-    (void)hipFree(d_cells);
-    return rc;
+    return check_device_errors(c, true, false);
 }
 
 static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
@@ -2035,22 +2014,19 @@ static int32_t match_eval_impl(lama_hip_ctx* c, uint32_t particle, const double*
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
-    double *d_pose = nullptr, *d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_pose, sizeof(double) * 4));
-    hipError_t e = hipMalloc(&d_out, sizeof(double) * 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pose, pose, sizeof(double) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        const Affine mtf = moving_tf(origin3, quat);
-        DevParams prm = make_params(c);
-        hipLaunchKernelGGL(k_match_eval, dim3((n + 255) / 256), dim3(256), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, d_pose, d_out,
-                           jacobian ? d_out + n : nullptr, cell_mode);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(residuals, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && jacobian) e = hipMemcpyAsync(jacobian, d_out + n, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_pose); (void)hipFree(d_out);
-    HIPCHK(c, e);
+    DevBuf<double> out, pose_in;                                    // (released in this order: pose_in, then out)
+    HIPCHK(c, pose_in.alloc(4));
+    HIPCHK(c, out.alloc(4 * (size_t)n));
+    double* const d_pose = pose_in; double* const d_out = out;      // (launch arguments are plain pointers: the owners are not copied)
+    HIPCHK(c, hipMemcpyAsync(d_pose, pose, sizeof(double) * 4, hipMemcpyHostToDevice, c->stream));
+    const Affine mtf = moving_tf(origin3, quat);
+    DevParams prm = make_params(c);
+    hipLaunchKernelGGL(k_match_eval, dim3((n + 255) / 256), dim3(256), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, d_pose, d_out,
+                       jacobian ? d_out + n : nullptr, cell_mode);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(residuals, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    if (jacobian) HIPCHK(c, hipMemcpyAsync(jacobian, d_out + n, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LAMA_HIP_OK;
 }
 
@@ -2063,13 +2039,8 @@ static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
-    if (c->b_cap < 4) {
-        (void)hipFree(c->d_bposes); (void)hipFree(c->d_bout);
-        c->d_bposes = nullptr; c->d_bout = nullptr; c->b_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_bposes, sizeof(double) * 4 * 16));
-        HIPCHK(c, hipMalloc(&c->d_bout, sizeof(double) * 16));
-        c->b_cap = 16;
-    }
+    rc = ensure_batch(c, 7, 16);                                     // (a pose in, seven results out)
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_bposes, pose_inout, sizeof(double) * 4, hipMemcpyHostToDevice, c->stream));
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
@@ -2113,13 +2084,11 @@ static int32_t mapped_box_rel(const lama_hip_ctx* c, int axis)
 // ---- particle shipping: all outgoing / incoming particles of a resample in one launch each (k_export_particles / k_import_particles)
 static int32_t upload_ship_desc(lama_hip_ctx* c, uint32_t n)
 {
-    if (n > c->ship_cap) {
-        (void)hipFree(c->d_ship_desc); (void)hipFree(c->d_ship_heads);
-        c->d_ship_desc = nullptr; c->d_ship_heads = nullptr; c->ship_cap = 0;
-        const uint32_t cap = std::max<uint32_t>(n, 64u);
-        HIPCHK(c, hipMalloc(&c->d_ship_desc, sizeof(ShipDesc) * cap));
-        HIPCHK(c, hipMalloc(&c->d_ship_heads, (size_t)BLOB_HEAD * cap));
-        c->ship_cap = cap;
+    if ((size_t)BLOB_HEAD * n > c->d_ship_heads.n) {               // (allocated last: its count is the capacity of both)
+        c->d_ship_desc.reset(); c->d_ship_heads.reset();
+        const size_t cap = std::max<uint32_t>(n, 64u);
+        HIPCHK(c, c->d_ship_desc.alloc(cap));
+        HIPCHK(c, c->d_ship_heads.alloc((size_t)BLOB_HEAD * cap));
     }
     HIPCHK(c, hipMemcpyAsync(c->d_ship_desc, c->h_ship_desc.data(), sizeof(ShipDesc) * n, hipMemcpyHostToDevice, c->stream));
     return LAMA_HIP_OK;
@@ -2365,8 +2334,8 @@ static void memory_figures(const lama_hip_ctx* c, lama_hip_counters* o)
     for (const PoolChunk& k : m.occ_chunks) occ_pool += k.patches;
     o->hbm_bytes_allocated = dirs + dm_pool * (SV_PATCH_BYTES + 4096 + 128) + occ_pool * (4096 + 128 + 128 + 4);
     o->hbm_bytes_used = dirs + dm_used * (SV_PATCH_BYTES + 4096 + 128) + occ_used * (4096 + 128 + 128 + 4);
-    const uint64_t other = 2 * P * (uint64_t)c->cfg.queue_capacity * 8 + P * (uint64_t)c->cfg.active_capacity * 8 + (uint64_t)c->rrec_cap * (sizeof(lama_dev::RayRec) + 8) +
-                           P * (16 * 8 + 12 * 8 + 4 * 8 + 64) + (1u << 20) + (uint64_t)c->pts_cap * 24;
+    const uint64_t other = 2 * P * (uint64_t)c->cfg.queue_capacity * 8 + P * (uint64_t)c->cfg.active_capacity * 8 + (uint64_t)c->d_rrec.n * (sizeof(lama_dev::RayRec) + 8) +
+                           P * (16 * 8 + 12 * 8 + 4 * 8 + 64) + (1u << 20) + (uint64_t)c->d_pts.bytes();
     o->hbm_bytes_total = o->hbm_bytes_allocated + other;
 }
 

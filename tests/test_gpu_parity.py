@@ -1698,6 +1698,53 @@ def test_limits_fail_loudly_with_status_codes(F):
     a.close(); b.close()
 
 
+def test_destroyed_contexts_give_back_their_device_memory(F):
+    """Every buffer, stream and event a context or a pose graph holds is released when it is destroyed -- after rejected calls and
+    after a creation refused half-way, too: ten cycles of a 300-particle context (several hundred MB each) leave the device's free
+    memory where it was."""
+    import torch
+    pts, odom, truth = F.corridor_log(2, 1080)
+    pose0 = O.se2(*odom[0])
+    P, N = 300, 100
+    rng = np.random.default_rng(5)
+    poses = _perturbed(rng, O.se2(*truth[1]), P)
+    c0 = O.w2m([0.0, 0.0, 0.0])
+    qcap = F.default_cfg().queue_capacity
+    k = np.arange(qcap + 1)
+    too_many = np.stack([c0[0] + k % 200, c0[1] + k // 200], axis=1).astype(np.uint32)     # one more obstacle cell than the queue holds
+    ids = np.array([5, 5], dtype=np.uint64)                                                  # a patch given twice
+    cells, masks = np.zeros((2, 1024), dtype=F.DIST_T), np.zeros((2, 16), dtype=np.uint64)
+    fi, fj = np.arange(N - 1), np.arange(1, N)
+    meas, sq = np.tile([1.0, 0.0, 0.1, 0.0], (N - 1, 1)), np.ones((N - 1, 3))
+
+    def cycle():
+        ctx = F.HipContext(F.default_cfg(particles=P))
+        ctx.init(pts[0], pose0)
+        ctx.set_poses(poses)
+        ctx.update_maps(pts[1])
+        footprint = ctx.counters()["hbm_bytes_total"]
+        with pytest.raises(F.LamaError, match="queue_capacity"):
+            ctx.add_obstacles(0, too_many)
+        rc = ctx.L.lama_hip_pf_upload_map(ctx.h, 1, F.MAP_DISTANCE, 2, ids.ctypes.data, cells.ctypes.data, masks.ctypes.data)
+        assert rc != 0 and b"twice" in ctx.L.lama_hip_last_error(ctx.h)
+        ctx.close()
+        # refused after its streams and events exist: particles x dm_patch_capacity does not fit the pool's 32-bit patch index
+        with pytest.raises(F.LamaError, match="lama_hip_ctx_create failed"):
+            F.HipContext(F.default_cfg(particles=200000, dm_patch_capacity=32767))
+        g = F.PoseGraph(N, fi, fj, meas, sq)
+        g.close()
+        return footprint
+
+    cycle()                                                          # (whatever the runtime keeps after its first use)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    footprints = [cycle() for _ in range(10)]
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    assert min(footprints) >= 400 << 20, footprints
+    assert free1 >= free0 - (256 << 20), f"{(free0 - free1) >> 20} MB of device memory not given back after 10 cycles"
+
+
 def test_slam2d_transient_map_gpu_vs_oracle(F):
     """Slam2D with transient_map (src/slam2d.cpp:322-379) on the device: patch deletion keeps both maps bit-exact."""
     steps = 30
