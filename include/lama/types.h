@@ -11,6 +11,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <deque>
 #include <memory>
 #include <vector>
 
@@ -125,6 +126,7 @@ struct Quaterniond {
 namespace lama {
 
 template <class T> using DynamicArray = std::vector<T>;
+template <class T> using List = std::deque<T>;             // include/lama/types.h:80 of the reference
 
 // include/lama/types.h:111-120 of the reference
 struct PointCloudXYZ {

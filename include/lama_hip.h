@@ -276,6 +276,26 @@ const char* lama_hip_pgo_last_error(const lama_hip_pgo* g);
 int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* err, double* Hdiag, double* Hoff, double* b,
                                double* chi2, double* kernel_ms);
 
+/* The device-resident Levenberg-Marquardt loop of lama::SimplePGO (include/lama/simple_pgo.h).  The graph holds two pose buffers on the
+ * device, the current state and a candidate; lama_hip_pgo_linearize above also sets the current state.
+ *   pattern          : the lower block-CSR pattern of the Hessian, fixed at create: row r holds its diagonal block first, then the
+ *                      distinct columns c < r that share a factor with r, ascending.  row_ptr [N+1], cols [nnzb]; either may be NULL
+ *                      (ask for nnzb first).
+ *   set_poses / get_poses : the current state {c, s, tx, ty} [N][4].
+ *   linearize_system : at the current state: blocks [nnzb][9] (row-major 3x3, the order of `cols`; the factors on one pair add up in
+ *                      factor order), b [N][3] = -J^T e, diag [N][3] = the undamped Hessian diagonal, half_chi2 = 0.5 sum ||e||^2.
+ *                      Outputs may be NULL.  (Bit for bit: blocks are the scatter of lama_hip_pgo_linearize's Hdiag / Hoff.)
+ *   try_step         : candidate = current * exp(dx) per pose (dx [N][3], the right-multiplicative retract of minisam's Sophus
+ *                      traits) and its 0.5 sum ||e||^2; only dx goes up and one scalar comes back.
+ *   accept           : the candidate becomes the current state (no copy).
+ * kernel_ms: device time of the call's kernels (may be NULL). */
+int32_t lama_hip_pgo_pattern(const lama_hip_pgo* g, int32_t* row_ptr, int32_t* cols, uint32_t* nnzb);
+int32_t lama_hip_pgo_set_poses(lama_hip_pgo* g, const double* poses4);
+int32_t lama_hip_pgo_get_poses(lama_hip_pgo* g, double* poses4);
+int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b, double* diag, double* half_chi2, double* kernel_ms);
+int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_chi2, double* kernel_ms);
+int32_t lama_hip_pgo_accept(lama_hip_pgo* g);
+
 /* Accumulated per-kernel device time (hipEvent elapsed, on the stream the kernels run on) and work
  * counters since the last reset; valid when cfg.profile != 0. */
 typedef struct lama_hip_counters {

@@ -211,6 +211,21 @@ int lama_sdm_export_png(int kind, double resolution, uint32_t max_sqdist, uint32
  * lama_dm_build_fetch copies the records out (ids n, cells n x 10240 B, masks n x 16 words). */
 int64_t lama_dm_build(const uint32_t* cells_xy, uint64_t n, uint32_t max_sqdist, uint32_t* processed);
 int lama_dm_build_fetch(uint64_t* ids, uint8_t* cells, uint64_t* masks);
+/* ---- lama::SimplePGO (include/lama/simple_pgo.h) flattened: poses {c, s, tx, ty}.  nodes4 [n][4] = node_list; loop closures
+ * k < ne: edge_from[k] -> edge_to[k] with measurement edge4[k] (edge_list); fixed nodes k < nf: fixed_idx[k] at fixed4[k] (fixed_list).
+ * Returns 1 when optimize() returned true (out4 [n][4] = the optimised node_list), 0 when it returned false (out4 = nodes4), -1 on an
+ * error (no device library / HIP device: the message goes to err).  report and trace (one entry per LM try: 1 accepted, 0 rejected,
+ * 2 rank deficient; at most trace_cap written) may be NULL. */
+typedef struct lama_pgo_report {
+    int32_t status;                 /* minisam NonlinearOptimizationStatus: 0 SUCCESS, 1 MAX_ITERATION, 2 ERROR_INCREASE, 3 RANK_DEFICIENCY */
+    uint32_t iterations, tries;
+    double initial_error, final_error;   /* 0.5 * sum of squared whitened errors */
+    uint64_t nnz_L;
+    double ms_device_linearize, ms_device_try, ms_analyze, ms_factorize, ms_total;
+} lama_pgo_report;
+int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4, uint32_t ne,
+                      const int32_t* fixed_idx, const double* fixed4, uint32_t nf, int32_t device, double* out4, lama_pgo_report* report,
+                      int8_t* trace, uint32_t trace_cap, char* err, int errcap);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

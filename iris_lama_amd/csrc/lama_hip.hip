@@ -17,6 +17,7 @@
 
 #include "lama_kernels.h"
 #include "lama_pgo.h"
+#include "../host/pgo_pattern.hpp"
 
 using namespace lama_dev;
 
@@ -1843,6 +1844,11 @@ struct lama_hip_pgo {
     DevBuf<int32_t> d_fi, d_fj, d_incptr, d_inc;
     std::vector<double> h_chi;
     std::string error;
+    // the Levenberg-Marquardt loop (lama_hip_pgo_set_poses .. _accept): d_poses is the current state, d_cand the candidate
+    uint32_t nnzb = 0;
+    std::vector<int32_t> h_rowptr, h_cols;
+    DevBuf<double> d_cand, d_dx, d_blocks, d_diag, d_half;
+    DevBuf<int32_t> d_brow, d_bcol, d_cptr, d_contrib;
 
     __attribute__((visibility("hidden"))) ~lama_hip_pgo() { (void)hipSetDevice(device); }     // (not exported: the C-ABI is)
 };
@@ -1882,6 +1888,20 @@ int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const
         hipMemcpy(p->d_inc, inc.data(), sizeof(int32_t) * inc.size(), hipMemcpyHostToDevice))
         return LAMA_HIP_E_HIP;
     p->h_chi.resize(p->blocksF);
+    const lama::pgo::BlockPattern bp = lama::pgo::lowerBlockPattern(N, fi, fj, F);    // (host/pgo_pattern.hpp)
+    const std::vector<int32_t>&brow = bp.rows, &bcol = bp.cols, &cptr = bp.cptr, &contrib = bp.contrib;
+    p->nnzb = (uint32_t)bcol.size();
+    p->h_rowptr = bp.row_ptr;
+    p->h_cols = bcol;
+    if (p->d_cand.alloc(4 * (size_t)N) || p->d_dx.alloc(3 * (size_t)N) || p->d_blocks.alloc(9 * (size_t)p->nnzb) ||
+        p->d_diag.alloc(3 * (size_t)N) || p->d_half.alloc(1) || p->d_brow.alloc(p->nnzb) || p->d_bcol.alloc(p->nnzb) ||
+        p->d_cptr.alloc((size_t)p->nnzb + 1) || p->d_contrib.alloc(std::max<size_t>(contrib.size(), 1)))
+        return LAMA_HIP_E_HIP;
+    if (hipMemcpy(p->d_brow, brow.data(), sizeof(int32_t) * p->nnzb, hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_bcol, bcol.data(), sizeof(int32_t) * p->nnzb, hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_cptr, cptr.data(), sizeof(int32_t) * cptr.size(), hipMemcpyHostToDevice) ||
+        (!contrib.empty() && hipMemcpy(p->d_contrib, contrib.data(), sizeof(int32_t) * contrib.size(), hipMemcpyHostToDevice)))
+        return LAMA_HIP_E_HIP;
     *out = p.release();
     return LAMA_HIP_OK;
 }
@@ -1911,6 +1931,87 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
     PGOCHK(g, hipStreamSynchronize(g->stream));
     if (chi2) { double t = 0; for (double x : g->h_chi) t += x; *chi2 = t; }
     if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_pattern(const lama_hip_pgo* g, int32_t* row_ptr, int32_t* cols, uint32_t* nnzb)
+{
+    if (!g || !nnzb) return LAMA_HIP_E_INVALID;
+    *nnzb = g->nnzb;
+    if (row_ptr) std::copy(g->h_rowptr.begin(), g->h_rowptr.end(), row_ptr);
+    if (cols) std::copy(g->h_cols.begin(), g->h_cols.end(), cols);
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_set_poses(lama_hip_pgo* g, const double* poses4)
+{
+    if (!g || !poses4) return LAMA_HIP_E_INVALID;
+    PGOCHK(g, hipSetDevice(g->device));
+    PGOCHK(g, hipMemcpyAsync(g->d_poses, poses4, sizeof(double) * 4 * g->N, hipMemcpyHostToDevice, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_get_poses(lama_hip_pgo* g, double* poses4)
+{
+    if (!g || !poses4) return LAMA_HIP_E_INVALID;
+    PGOCHK(g, hipSetDevice(g->device));
+    PGOCHK(g, hipMemcpyAsync(poses4, g->d_poses, sizeof(double) * 4 * g->N, hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b, double* diag, double* half_chi2, double* kernel_ms)
+{
+    if (!g) return LAMA_HIP_E_INVALID;
+    PGOCHK(g, hipSetDevice(g->device));
+    PgoPtrs p{g->d_poses, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
+              g->d_hdiag, g->d_b, g->d_chi};
+    PgoSysPtrs s{g->d_hdiag, g->d_hoff, g->d_brow, g->d_bcol, g->d_cptr, g->d_contrib, g->d_blocks, g->d_diag};
+    PGOCHK(g, hipEventRecord(g->ev0, g->stream));
+    hipLaunchKernelGGL(k_pgo_factors, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, g->F);
+    hipLaunchKernelGGL(k_pgo_reduce, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, p, g->N);
+    hipLaunchKernelGGL(k_pgo_assemble, dim3((g->nnzb + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, s, g->nnzb);
+    hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
+    PGOCHK(g, hipEventRecord(g->ev1, g->stream));
+    PGOCHK(g, hipGetLastError());
+    if (blocks) PGOCHK(g, hipMemcpyAsync(blocks, g->d_blocks, sizeof(double) * 9 * g->nnzb, hipMemcpyDeviceToHost, g->stream));
+    if (b) PGOCHK(g, hipMemcpyAsync(b, g->d_b, sizeof(double) * 3 * g->N, hipMemcpyDeviceToHost, g->stream));
+    if (diag) PGOCHK(g, hipMemcpyAsync(diag, g->d_diag, sizeof(double) * 3 * g->N, hipMemcpyDeviceToHost, g->stream));
+    double h = 0.0;
+    PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    if (half_chi2) *half_chi2 = h;
+    if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_chi2, double* kernel_ms)
+{
+    if (!g || !dx || !half_chi2) return LAMA_HIP_E_INVALID;
+    PGOCHK(g, hipSetDevice(g->device));
+    PgoPtrs p{g->d_cand, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
+              g->d_hdiag, g->d_b, g->d_chi};
+    PGOCHK(g, hipMemcpyAsync(g->d_dx, dx, sizeof(double) * 3 * g->N, hipMemcpyHostToDevice, g->stream));
+    PGOCHK(g, hipEventRecord(g->ev0, g->stream));
+    hipLaunchKernelGGL(k_pgo_retract, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, (const double*)g->d_poses,
+                       (const double*)g->d_dx, (double*)g->d_cand, g->N);
+    hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
+    hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
+    PGOCHK(g, hipEventRecord(g->ev1, g->stream));
+    PGOCHK(g, hipGetLastError());
+    double h = 0.0;
+    PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    *half_chi2 = h;
+    if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_accept(lama_hip_pgo* g)
+{
+    if (!g) return LAMA_HIP_E_INVALID;
+    g->d_poses.swap(g->d_cand);            // (the stream is idle: try_step synchronised it)
     return LAMA_HIP_OK;
 }
 

@@ -140,4 +140,114 @@ __global__ __launch_bounds__(PGO_BLOCK) void k_pgo_reduce(PgoPtrs g, uint32_t N)
     for (int t = 0; t < 3; ++t) g.b[3 * (size_t)v + t] = bb[t];
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Device-resident Levenberg-Marquardt loop (lama::SimplePGO, iris_lama_amd/host/simple_pgo.cpp).  The poses stay on the device
+// for a whole optimize(), in a current and a candidate buffer; per try only dx goes up and one scalar error comes back.
+//
+//   k_pgo_assemble : one thread per 3x3 block of the lower block-CSR Hessian (pattern fixed at create: each row is its diagonal
+//                    block, then the distinct lower neighbours in ascending order).  A diagonal block is Hdiag of k_pgo_reduce
+//                    (and its diagonal the undamped hessian_diag of LevenbergMarquardtOptimizer.cpp:81-85); an off-diagonal
+//                    block sums J_i^T J_j (or its transpose when the factor's i is the block's column) of the factors on that
+//                    pair IN FACTOR ORDER through a per-block contribution list -- no floating-point atomics.
+//   k_pgo_retract  : candidate_v = current_v * exp(dx_v)  (Sophus.h:52-56, right-multiplicative; se2.hpp:389-411 and the
+//                    renormalising product se2.hpp:154-157,262-265 -- the host mirror is SE2d::exp / operator*).
+//   k_pgo_error    : whitened errors only (the bodies of k_pgo_factors without Jacobians), per-block partial sums of ||e||^2.
+//   k_pgo_sum      : one wave sums the partials in a fixed order: 0.5 * chi2.
+// ------------------------------------------------------------------------------------------------
+struct PgoSysPtrs {
+    const double* hdiag;      // [N][9]  (k_pgo_reduce)
+    const double* hoff;       // [F][9]  (k_pgo_factors)
+    const int32_t* brow;      // [nnzb]  block row
+    const int32_t* bcol;      // [nnzb]  block column (<= row)
+    const int32_t* cptr;      // [nnzb+1]
+    const int32_t* contrib;   // factor index * 2 + transpose flag, factor order within a block
+    double* blocks;           // [nnzb][9] row-major
+    double* diag;             // [N][3]
+};
+
+__global__ __launch_bounds__(PGO_BLOCK) void k_pgo_assemble(PgoSysPtrs s, uint32_t nnzb)
+{
+    const uint32_t q = blockIdx.x * PGO_BLOCK + threadIdx.x;
+    if (q >= nnzb) return;
+    const int32_t r = s.brow[q], c = s.bcol[q];
+    double B[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (r == c) {
+        for (int t = 0; t < 9; ++t) B[t] = s.hdiag[9 * (size_t)r + t];
+        for (int t = 0; t < 3; ++t) s.diag[3 * (size_t)r + t] = B[4 * t];
+    } else {
+        for (int32_t p = s.cptr[q]; p < s.cptr[q + 1]; ++p) {
+            const int32_t code = s.contrib[p];
+            const double* H = s.hoff + 9 * (size_t)(code >> 1);
+            if (code & 1) { for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) B[3 * a + b] += H[3 * b + a]; }
+            else { for (int t = 0; t < 9; ++t) B[t] += H[t]; }
+        }
+    }
+    for (int t = 0; t < 9; ++t) s.blocks[9 * (size_t)q + t] = B[t];
+}
+
+__device__ inline SE2 pgo_exp(double vx, double vy, double theta)  // se2.hpp:389-411 (so2.hpp exp normalises)
+{
+    SE2 r;
+    r.c = cos(theta); r.s = sin(theta);
+    so2_normalize(r.c, r.s);
+    double a, b;                                                   // sin(theta) / theta, (1 - cos(theta)) / theta
+    if (fabs(theta) < 1e-10) {
+        const double theta_sq = theta * theta;
+        a = 1. - (1. / 6.) * theta_sq;
+        b = 0.5 * theta - (1. / 24.) * theta * theta_sq;
+    } else {
+        a = r.s / theta;
+        b = (1. - r.c) / theta;
+    }
+    r.tx = a * vx - b * vy;
+    r.ty = b * vx + a * vy;
+    return r;
+}
+
+__global__ __launch_bounds__(PGO_BLOCK) void k_pgo_retract(const double* __restrict__ cur, const double* __restrict__ dx,
+                                                           double* __restrict__ cand, uint32_t N)
+{
+    const uint32_t v = blockIdx.x * PGO_BLOCK + threadIdx.x;
+    if (v >= N) return;
+    const SE2 x{cur[4 * v], cur[4 * v + 1], cur[4 * v + 2], cur[4 * v + 3]};
+    const SE2 r = pgo_mul(x, pgo_exp(dx[3 * v], dx[3 * v + 1], dx[3 * v + 2]));
+    cand[4 * v] = r.c; cand[4 * v + 1] = r.s; cand[4 * v + 2] = r.tx; cand[4 * v + 3] = r.ty;
+}
+
+__global__ __launch_bounds__(PGO_BLOCK) void k_pgo_error(PgoPtrs g, const double* __restrict__ poses, uint32_t F)
+{
+    __shared__ double red[PGO_BLOCK / 64];
+    const uint32_t k = blockIdx.x * PGO_BLOCK + threadIdx.x;
+    double c2 = 0.0;
+    if (k < F) {
+        const int i = g.fi[k], j = g.fj[k];
+        const SE2 z{g.meas[4 * k], g.meas[4 * k + 1], g.meas[4 * k + 2], g.meas[4 * k + 3]};
+        const SE2 v1{poses[4 * i], poses[4 * i + 1], poses[4 * i + 2], poses[4 * i + 3]};
+        double e[3];
+        if (j < 0) {
+            pgo_log(pgo_mul(pgo_inverse(z), v1), e);
+        } else {
+            const SE2 v2{poses[4 * j], poses[4 * j + 1], poses[4 * j + 2], poses[4 * j + 3]};
+            pgo_log(pgo_mul(pgo_inverse(z), pgo_mul(pgo_inverse(v1), v2)), e);
+        }
+        for (int r = 0; r < 3; ++r) {
+            const double w = e[r] * g.sqrt_info[3 * k + r];
+            c2 += w * w;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) c2 += __shfl_xor(c2, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c2;
+    __syncthreads();
+    if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < PGO_BLOCK / 64; ++w) t += red[w]; g.chi2_part[blockIdx.x] = t; }
+}
+
+__global__ __launch_bounds__(64) void k_pgo_sum(const double* __restrict__ part, uint32_t n, double* __restrict__ half_chi2)
+{
+    double t = 0.0;
+    for (uint32_t q = threadIdx.x; q < n; q += 64) t += part[q];
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if (threadIdx.x == 0) *half_chi2 = 0.5 * t;
+}
+
 } // namespace lama_dev

@@ -67,6 +67,8 @@ HIP_SYMBOLS = [
     "lama_hip_pf_patch_ids", "lama_hip_pf_delete_patches", "lama_hip_pf_update_maps_begin", "lama_hip_sync", "lama_hip_ctx_device",
     "lama_hip_pf_map_checksums", "lama_hip_match_eval", "lama_hip_match_cell_distances", "lama_hip_match_solve_with",
     "lama_hip_blob_alloc", "lama_hip_blob_free", "lama_hip_blob_copy", "lama_hip_pf_export_particles", "lama_hip_pf_import_particles",
+    "lama_hip_pgo_pattern", "lama_hip_pgo_set_poses", "lama_hip_pgo_get_poses", "lama_hip_pgo_linearize_system",
+    "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
 ]
 
 _hip = None
@@ -190,6 +192,12 @@ def _bind_hip(L):
             L.lama_hip_pgo_last_error.argtypes = [vp]
             L.lama_hip_pgo_last_error.restype = C.c_char_p
             L.lama_hip_pgo_linearize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+            L.lama_hip_pgo_pattern.argtypes = [vp, vp, vp, vp]
+            L.lama_hip_pgo_set_poses.argtypes = [vp, vp]
+            L.lama_hip_pgo_get_poses.argtypes = [vp, vp]
+            L.lama_hip_pgo_linearize_system.argtypes = [vp, vp, vp, vp, vp, vp]
+            L.lama_hip_pgo_try_step.argtypes = [vp, vp, vp, vp]
+            L.lama_hip_pgo_accept.argtypes = [vp]
         for s in HIP_SYMBOLS:
             if s.startswith("lama_hip_pgo_") and not has_pgo:
                 continue
@@ -486,6 +494,7 @@ HOST_SYMBOLS = [
     "lama_sdm_write", "lama_sdm_read", "lama_sdm_image", "lama_sdm_export_png", "lama_dm_build", "lama_dm_build_fetch",
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
+    "lama_pgo_optimize",
 ]
 
 
@@ -539,6 +548,7 @@ def _bind_host(L):
         "lama_sdm_image": (i32, [i32, d, u32, u32, vp, vp, vp, vp, vp, vp, C.c_uint64]),
         "lama_sdm_export_png": (i32, [i32, d, u32, u32, vp, vp, vp, C.c_char_p]),
         "lama_dm_build": (C.c_int64, [vp, C.c_uint64, u32, vp]), "lama_dm_build_fetch": (i32, [vp, vp, vp]),
+        "lama_pgo_optimize": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, u32, vp, i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1096,6 +1106,86 @@ class PoseGraph:
         if rc != 0:
             raise LamaError(self.L.lama_hip_pgo_last_error(self.h).decode())
         return {"err": err, "Hdiag": hd, "Hoff": hoff, "b": b, "chi2": chi2.value, "kernel_ms": ms.value}
+
+    def _check(self, rc):
+        if rc != 0:
+            raise LamaError(self.L.lama_hip_pgo_last_error(self.h).decode())
+
+    def pattern(self):
+        """-> (row_ptr [N+1], cols [nnzb]): the lower block-CSR pattern of the Hessian (diagonal block first in each row)."""
+        n = C.c_uint32(0)
+        self._check(self.L.lama_hip_pgo_pattern(self.h, None, None, C.byref(n)))
+        row_ptr, cols = np.zeros(self.N + 1, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        self._check(self.L.lama_hip_pgo_pattern(self.h, _p(row_ptr), _p(cols), C.byref(n)))
+        return row_ptr, cols
+
+    def set_poses(self, poses):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(self.N, 4)
+        self._check(self.L.lama_hip_pgo_set_poses(self.h, _p(poses)))
+
+    def get_poses(self):
+        out = np.zeros((self.N, 4))
+        self._check(self.L.lama_hip_pgo_get_poses(self.h, _p(out)))
+        return out
+
+    def linearize_system(self):
+        """At the current poses -> dict(blocks [nnzb,3,3], b [N,3], diag [N,3], half_chi2, kernel_ms)"""
+        nnzb = C.c_uint32(0)
+        self._check(self.L.lama_hip_pgo_pattern(self.h, None, None, C.byref(nnzb)))
+        blocks, b, diag = np.zeros((nnzb.value, 3, 3)), np.zeros((self.N, 3)), np.zeros((self.N, 3))
+        half, ms = C.c_double(0), C.c_double(0)
+        self._check(self.L.lama_hip_pgo_linearize_system(self.h, _p(blocks), _p(b), _p(diag), C.byref(half), C.byref(ms)))
+        return {"blocks": blocks, "b": b, "diag": diag, "half_chi2": half.value, "kernel_ms": ms.value}
+
+    def try_step(self, dx):
+        """Candidate = current * exp(dx) per pose -> (0.5 * chi2 at the candidate, kernel_ms)."""
+        dx = np.ascontiguousarray(dx, dtype=np.float64).reshape(self.N, 3)
+        half, ms = C.c_double(0), C.c_double(0)
+        self._check(self.L.lama_hip_pgo_try_step(self.h, _p(dx), C.byref(half), C.byref(ms)))
+        return half.value, ms.value
+
+    def accept(self):
+        self._check(self.L.lama_hip_pgo_accept(self.h))
+
+
+class PgoReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_uint32), ("tries", C.c_uint32),
+                ("initial_error", C.c_double), ("final_error", C.c_double), ("nnz_L", C.c_uint64),
+                ("ms_device_linearize", C.c_double), ("ms_device_try", C.c_double), ("ms_analyze", C.c_double),
+                ("ms_factorize", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+PGO_STATUS = {0: "SUCCESS", 1: "MAX_ITERATION", 2: "ERROR_INCREASE", 3: "RANK_DEFICIENCY", 4: "INVALID", -1: "NOT_RUN"}
+
+
+def simple_pgo(nodes, edges=(), fixed=(), device=0):
+    """lama::SimplePGO::optimize (include/lama/simple_pgo.h) on the device.  nodes [n,4] {c, s, tx, ty} (node_list); edges: iterable of
+    (from, to, pose4) (edge_list); fixed: iterable of (index, pose4) (fixed_list).
+    -> (ok, poses [n,4], report dict with the try trace under "trace": 1 accepted, 0 rejected, 2 rank deficient)."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 4)
+    n = len(nodes)
+    edges, fixed = list(edges), list(fixed)
+    ef = np.array([e[0] for e in edges], dtype=np.int32)
+    et = np.array([e[1] for e in edges], dtype=np.int32)
+    e4 = np.ascontiguousarray(np.array([e[2] for e in edges], dtype=np.float64).reshape(-1, 4))
+    fx = np.array([f[0] for f in fixed], dtype=np.int32)
+    f4 = np.ascontiguousarray(np.array([f[1] for f in fixed], dtype=np.float64).reshape(-1, 4))
+    out = np.zeros((n, 4))
+    rep = PgoReport()
+    cap = 1 << 16
+    trace = np.zeros(cap, dtype=np.int8)
+    err = C.create_string_buffer(512)
+    rc = _hostlib().lama_pgo_optimize(_p(nodes) if n else None, n, _p(ef), _p(et), _p(e4), len(edges), _p(fx), _p(f4), len(fixed),
+                                     device, _p(out) if n else None, C.byref(rep), _p(trace), cap, err, 512)
+    if rc < 0:
+        raise LamaError(err.value.decode())
+    r = rep.as_dict()
+    r["status_name"] = PGO_STATUS.get(r["status"], str(r["status"]))
+    r["trace"] = trace[:min(rep.tries, cap)].copy()
+    return rc == 1, out, r
 
 
 class LidarOdometry2D:

@@ -16,6 +16,7 @@
 #include "lama/sdm_io.h"
 #include "dm_builder.hpp"
 #include "lama/slam2d.h"
+#include "lama/simple_pgo.h"
 
 using namespace lama;
 
@@ -699,5 +700,32 @@ int lama_dm_build_fetch(uint64_t* ids, uint8_t* cells, uint64_t* masks)
 }
 void lama_random_set_seed(uint32_t seed) { lama::random::setSeed(seed); }
 double lama_random_uniform(void) { return lama::random::uniform(); }
+
+int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4, uint32_t ne,
+                      const int32_t* fixed_idx, const double* fixed4, uint32_t nf, int32_t device, double* out4, lama_pgo_report* report,
+                      int8_t* trace, uint32_t trace_cap, char* err, int errcap)
+{
+    try {
+        SimplePGO p;
+        p.device = device;
+        for (uint32_t i = 0; i < n; ++i) p.node_list.push_back(Pose2D(SE2d::fromArray(nodes4 + 4 * i)));
+        for (uint32_t k = 0; k < ne; ++k) p.edge_list.push_back({edge_from[k], {edge_to[k], Pose2D(SE2d::fromArray(edge4 + 4 * k))}});
+        for (uint32_t k = 0; k < nf; ++k) p.fixed_list.push_back({fixed_idx[k], Pose2D(SE2d::fromArray(fixed4 + 4 * k))});
+        const bool ok = p.optimize();
+        if (out4) for (uint32_t i = 0; i < n; ++i) p.node_list[i].state.toArray(out4 + 4 * i);
+        if (report) {
+            const SimplePGO::Report& r = p.report;
+            report->status = r.status; report->iterations = r.iterations; report->tries = r.tries;
+            report->initial_error = r.initial_error; report->final_error = r.final_error; report->nnz_L = r.nnz_L;
+            report->ms_device_linearize = r.ms_device_linearize; report->ms_device_try = r.ms_device_try;
+            report->ms_analyze = r.ms_analyze; report->ms_factorize = r.ms_factorize; report->ms_total = r.ms_total;
+        }
+        if (trace) for (size_t q = 0; q < p.report.trace.size() && q < trace_cap; ++q) trace[q] = p.report.trace[q];
+        return ok ? 1 : 0;
+    } catch (const std::exception& e) {
+        if (err && errcap > 0) { std::strncpy(err, e.what(), (size_t)errcap - 1); err[errcap - 1] = 0; }
+        return -1;
+    }
+}
 
 } // extern "C"
