@@ -201,8 +201,10 @@ int32_t lama_hip_eval_batch(lama_hip_ctx* ctx, uint32_t particle, const double* 
                             const double* poses, uint32_t num_poses, double* sqnorm_out, double* loglik_out);
 
 /* Loc2D::addSamplingCovariance's likelihood samples (src/loc2d.cpp:199-234): for each of the K world positions
- * xy[k] the scan is placed there with heading `yaw`; every `point_step`-th point (0, step, 2 step, ...; at most 128
- * of them) looks up the NON-interpolated distance d and l_out[k] = sum exp(-d^2 / 0.01)^3, summed in point order. */
+ * xy[k] the scan is placed there with heading `yaw`; every `point_step`-th point (0, step, 2 step, ...; at most
+ * LAMA_HIP_SAMPLE_MAX_TERMS of them, which covers Loc2D's step = max(n / 100, 1) for every n; more is refused with
+ * LAMA_HIP_E_INVALID) looks up the NON-interpolated distance d and l_out[k] = sum exp(-d^2 / 0.01)^3, summed in point order. */
+#define LAMA_HIP_SAMPLE_MAX_TERMS 256
 int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* ctx, uint32_t particle, const double* pts_xyz, uint32_t n,
                                        const double* sensor_origin3, const double* sensor_quat_wxyz, double yaw,
                                        const double* xy, uint32_t num_samples, uint32_t point_step, double* l_out);

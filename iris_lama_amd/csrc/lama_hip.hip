@@ -1805,7 +1805,8 @@ int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const
     if (!c || !xy || !l_out || n == 0 || K == 0 || point_step == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
     ENTER(c);
     if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_map_sample_likelihood before the map exists");
-    if ((n + point_step - 1) / point_step > (uint32_t)SL_MAX_TERMS) return fail(c, LAMA_HIP_E_INVALID, "more than 128 sampled points per pose");
+    if ((n + point_step - 1) / point_step > (uint32_t)SL_MAX_TERMS)
+        return fail(c, LAMA_HIP_E_INVALID, "more than " + std::to_string(SL_MAX_TERMS) + " sampled points per pose");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;

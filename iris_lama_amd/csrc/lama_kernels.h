@@ -244,7 +244,11 @@ struct SMShared {
     Affine tf;
     SE2 state;
     double h[3];
-    int ctl;      // 0 = continue, 1 = stop
+    // 0 = continue, 1 = stop: [0] from the step (2.), [1] from the validation (3.).  Two words because after an accepted step
+    // the loop goes from the read of [1] to thread 0's next write of the step's decision without a barrier in between: one
+    // word written there could reach threads that have not read the validation's decision yet, and they would leave the loop
+    // without the others (the lane simulator deadlocked on that with a one-point scan).
+    int ctl[2];
     // LevenbergMarquard state (src/nlls/levenberg_marquardt.cpp:49-54) and the sums of the last accepted linearisation
     double mu, v, keep[NJ];
     int reuse;    // 1 = the last step was rejected: step again from `keep` without re-evaluating (solver.cpp:69)
@@ -324,11 +328,11 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
                     sh.lin_is_final = 0;
                 }
             }
-            sh.ctl = stop;
+            sh.ctl[0] = stop;
         }
         __syncthreads();
         SMT(2);
-        if (sh.ctl) break;
+        if (sh.ctl[0]) break;
         // 3. validation: the problem at the updated state (chi2 decides; the other sums are next iteration's linearisation)
         double acc2[NJ];
         {
@@ -371,12 +375,12 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
                 sh.have_lin = 1;
                 sh.lin_is_final = 1;                        // if the loop ends here (max_iter), tot is at the returned state
             }
-            sh.ctl = stop;
+            sh.ctl[1] = stop;
         }
         ++iter;
         __syncthreads();
         SMT(3);
-        if (sh.ctl) break;
+        if (sh.ctl[1]) break;
     }
 #ifdef LAMA_PROFILE_SM
     if (threadIdx.x == 0) for (int k = 0; k < 4; ++k) prm.dbg[8 * blockIdx.x + k] = smp[k];
@@ -403,7 +407,7 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
         const double* q = prm.poses + 4 * p;
         sh.state = SE2{cload_f64(q), cload_f64(q + 1), cload_f64(q + 2), cload_f64(q + 3)};
         sh.tf = scan_tf(sh.state, mtf);
-        sh.ctl = 0;
+        sh.ctl[0] = 0; sh.ctl[1] = 0;
     }
     sm_build_lut(prm, sh.lut);
     __syncthreads();
@@ -452,7 +456,7 @@ __global__ __launch_bounds__(SM_BLOCK) void k_match_solve(DevParams prm, int par
     if (threadIdx.x == 0) {
         sh.state = SE2{cload_f64(pose_io), cload_f64(pose_io + 1), cload_f64(pose_io + 2), cload_f64(pose_io + 3)};
         sh.tf = scan_tf(sh.state, mtf);
-        sh.ctl = 0;
+        sh.ctl[0] = 0; sh.ctl[1] = 0;
     }
     sm_build_lut(prm, sh.lut);
     __syncthreads();
@@ -570,9 +574,10 @@ __global__ __launch_bounds__(SM_BLOCK) void k_eval_batch(DevParams prm, int part
 
 // Loc2D::addSamplingCovariance's inner loop (src/loc2d.cpp:217-234): for sample translation k the scan is placed at
 // `base` (rotation and sensor offset, computed on the host) shifted by xy[k]; every `step`-th point looks up the
-// NON-interpolated distance and contributes exp(-d^2/0.01)^3.  One wave per sample; the <= 128 terms are summed in
-// point order by one lane (the reference's sequential sum).
-constexpr int SL_MAX_TERMS = 128;
+// NON-interpolated distance and contributes exp(-d^2/0.01)^3.  One wave per sample; the <= SL_MAX_TERMS terms are summed
+// in point order by one lane (the reference's sequential sum).  Loc2D's step = max(n / 100, 1) asks for ceil(n / step)
+// terms, at most 199 (n = 199); 256 terms are 2 KiB of LDS and four passes of the wave.
+constexpr int SL_MAX_TERMS = LAMA_HIP_SAMPLE_MAX_TERMS;
 __global__ __launch_bounds__(64) void k_sample_likelihood(DevParams prm, int particle, const double* __restrict__ pts, int n, int step,
                                                           Affine base, const double* __restrict__ xy, double* __restrict__ l_out)
 {

@@ -386,6 +386,24 @@ class HipContext:
                                               C.byref(it), 1 if solve else 0))
         return pose, out[:6].copy(), float(out[6]), it.value
 
+    def match_eval(self, particle, pts, pose4, origin=None, quat=None, jac=True):
+        """-> (residuals[n], Jacobian n x 3 or None): MatchSurface2D::eval on the particle's distance map, no robust weight"""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        n = len(pts)
+        pose = np.ascontiguousarray(pose4, dtype=np.float64)
+        r, J = np.zeros(n), (np.zeros((3, n)) if jac else None)
+        self._chk(self.L.lama_hip_match_eval(self.h, particle, _p(pts), n, _p(origin), _p(quat), _p(pose), _p(r), _p(J)))
+        return r, (J.T.copy() if jac else None)
+
+    def cell_distances(self, particle, pts, pose4, origin=None, quat=None):
+        """-> distance of the cell w2m(tf * p_i) of every point, no interpolation (MatchSurface2D::error's terms)"""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        n = len(pts)
+        pose = np.ascontiguousarray(pose4, dtype=np.float64)
+        d = np.zeros(n)
+        self._chk(self.L.lama_hip_match_cell_distances(self.h, particle, _p(pts), n, _p(origin), _p(quat), _p(pose), _p(d)))
+        return d
+
     def export_bytes(self, particle):
         n = C.c_uint64(0)
         self._chk(self.L.lama_hip_pf_export_particle(self.h, particle, None, 0, C.byref(n)))

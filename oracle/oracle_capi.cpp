@@ -231,6 +231,13 @@ double orc_match_error(void* dm, const double* pts, int n, const double* origin3
     MatchSurface2D ms((const DynamicDistanceMap*)dm, &s, se2_of(pose4));
     return ms.error();
 }
+// its per-beam terms: distance of the cell w2m(tf * p_i), no interpolation
+void orc_match_cell_distances(void* dm, const double* pts, int n, const double* origin3, const double* quat4, const double* pose4, double* out)
+{
+    Scan s = make_scan(pts, n, origin3, quat4);
+    MatchSurface2D ms((const DynamicDistanceMap*)dm, &s, se2_of(pose4));
+    ms.cell_distances(out);
+}
 // PFSlam2D::calculateLikelihood (pf_slam2d.cpp:393-414)
 double orc_loglik(void* dm, const double* pts, int n, const double* origin3, const double* quat4,
                   const double* pose4, double meas_sigma)

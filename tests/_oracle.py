@@ -383,6 +383,17 @@ def match_error(dm, pts, pose, origin=ZERO3, quat=IDENT_Q):
     return L.orc_match_error(dm.h, _p(pts), len(pts), _p(origin), _p(quat), _p(np.ascontiguousarray(pose, dtype=np.float64)))
 
 
+def cell_distances(dm, pts, pose, origin=ZERO3, quat=IDENT_Q):
+    """MatchSurface2D::error()'s per-beam terms: distance of the cell w2m(tf * p_i), no interpolation."""
+    L = lib()
+    L.orc_match_cell_distances.restype = None
+    L.orc_match_cell_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    out = np.zeros(len(pts))
+    L.orc_match_cell_distances(dm.h, _p(pts), len(pts), _p(origin), _p(quat), _p(np.ascontiguousarray(pose, dtype=np.float64)), _p(out))
+    return out
+
+
 def loglik(dm, pts, pose, sigma=0.05, origin=ZERO3, quat=IDENT_Q):
     pts = np.ascontiguousarray(pts, dtype=np.float64)
     return lib().orc_loglik(dm.h, _p(pts), len(pts), _p(origin), _p(quat), _p(np.ascontiguousarray(pose)), sigma)

@@ -469,6 +469,11 @@ int32_t lama_hip_eval_batch(lama_hip_ctx* c, uint32_t particle, const double* pt
 int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin,
                                        const double* quat, double yaw, const double* xy, uint32_t K, uint32_t point_step, double* l_out)
 {
+    // the device's contract: at most LAMA_HIP_SAMPLE_MAX_TERMS sampled points per pose
+    if (point_step == 0 || (n + point_step - 1) / point_step > (uint32_t)LAMA_HIP_SAMPLE_MAX_TERMS) {
+        c->error = "more than " + std::to_string(LAMA_HIP_SAMPLE_MAX_TERMS) + " sampled points per pose";
+        return LAMA_HIP_E_INVALID;
+    }
     Scan s = pts ? make_scan(pts, n, origin, quat) : c->last_scan;
     c->last_scan = s;
     const Affine3 mtf = moving_tf(s);

@@ -308,3 +308,29 @@ def test_wide_build_randomized_small_rooms(Fsim_wide, seed, l2_max):
     from _stress import random_rooms_case
     assert Fsim_wide.needs_wide(l2_max, 0.05)
     random_rooms_case(Fsim_wide, seed, small=True, l2_max=l2_max)
+
+
+def test_single_map_matching_kernels_at_small_scan_sizes_on_the_simulator(Fsim):
+    """k_match_eval (and its cell mode), k_match_solve, k_eval_batch / k_loglik_batch and k_sample_likelihood on one static map
+    (tests/_match_checks.py): scans shorter than a wave, than a block, with a tail past the 256-thread block, and the point
+    counts for which Loc2D's sampling step asks for more than 128 terms (180, 257, 390).  The simulator links the host's libm,
+    so every per-beam value and the sampled sums are bit-equal to the oracle's; summed outputs are within the fsum bound."""
+    import _match_checks as M
+    ctx, dm = M.build_world(Fsim, 1.0, half_len=12.0)
+    rng = np.random.default_rng(5)
+    x, y, yaw = M.SCAN_POSE
+    for n in (1, 65, 180, 257, 390):
+        pts = M.scan_of(n)
+        for pose in M.eval_poses()[:2] + M.eval_poses()[-1:]:
+            M.check_eval(ctx, dm, pts, pose, same_libm=True, what=n)
+        M.check_batch(ctx, dm, pts, M.batch_poses(rng, 4), what=n)
+        M.check_solve(ctx, dm, pts, O.se2(x, y + 0.06, yaw - 0.02), same_libm=True, what=n)
+        nterms = M.check_sampling(ctx, dm, pts, yaw, [(x, y), (x + 0.05, y - 0.1)], same_libm=True, what=n)
+        assert nterms == -(-n // max(n // 100, 1))
+    # a C-ABI caller's own step may still ask for more than the kernel's 256 terms: refused, not truncated
+    with pytest.raises(Fsim.LamaError, match="more than 256 sampled points"):
+        ctx.sample_likelihood(0, M.scan_of(257), yaw, [(x, y)], 1)
+    pts, pose = M.edge_scan()
+    M.check_eval(ctx, dm, pts, pose, same_libm=True, what="mu = 0")
+    M.check_solve(ctx, dm, pts, pose, same_libm=True, what="mu = 0")
+    ctx.close()
