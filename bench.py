@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- particle-scans/sec of the MI355X PFSlam2D path on the seeded synthetic corridor log.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_total] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P_total] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one PFSlam2D::update() (predict, scan-match, normalise, resample if due, map update) of ALL particles
@@ -9,16 +9,21 @@ on one 1080-beam scan.  N = 1: BASELINE.json configs[1] (PFSlam2D, 30 particles,
 N > 1: BASELINE.json configs[2] -- the 3000 particles of configs[2] sharded in contiguous blocks over the N GPUs (STRONG scaling:
 the pool is fixed, 3000 / N particles per GPU).  `value` of such a line is the PRODUCT path of a multi-GPU node: ONE
 lama::PFSlam2D object with Options::gpus = N (C++: a host thread and a device context per GPU, the log-likelihoods gathered in
-host memory, clones shipped GPU to GPU with peer copies), run by rank 0 while the other ranks have released their devices.  The
+host memory, clones shipped GPU to GPU with peer copies), run by rank 0 while the other ranks have released their devices.
+
+A plain run measures `value` alone: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+Everything else the line can carry is measured only with --full.  There the N = 1 line adds the per-kernel breakdown (a second
+pass with hipEvent brackets), the forced-resample variant, the Summary buckets, the CPU baselines (--no-cpu skips them), the
+roofline, other particle counts (--sweep), the canonical brushfire mode and the rows of SURVEY 8(f).  The N > 1 line adds the
 one-process-per-GPU driver (iris_lama_amd/distributed.py over torch.distributed: an RCCL all-gather of the log-likelihoods plus
-particle shipping over xGMI), timed with the barrier / max-over-ranks bracket, is reported beside it ("torch_distributed_ranks"),
-and so are: the same pool unsharded on one GPU ("single_gpu_same_pool", the base of the curve), one GPU's share alone on one GPU
+particle shipping over xGMI), timed with the barrier / max-over-ranks bracket ("torch_distributed_ranks"),
+and: the same pool unsharded on one GPU ("single_gpu_same_pool", the base of the curve), one GPU's share alone on one GPU
 ("strong_scaling_ceiling": what no sharding can beat -- a particle's exact brushfire is a serial chain; "longest_chain_bound": the
 longest chain of the pool, which bounds the step at ANY number of GPUs), the WEAK-scaling run (the
 3000-particle pool on every GPU, "weak_scaling"), and a variant whose measurement gain makes the filter resample
 (meas_sigma_gain = 1e-4, SURVEY 8(d): it must resample and ship particles -- asserted -- and reports the exchange times).
 The N = 1 line carries the single-GPU rate at 3000 particles ("other_particle_counts").
-Launched as plain `python bench.py --gpus N` (no WORLD_SIZE in the environment) it spawns the N ranks itself
+Launched as `python bench.py --gpus N` (no WORLD_SIZE in the environment) it spawns the N ranks itself
 (torch.distributed.run, rendezvous on 127.0.0.1).  Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -459,10 +464,12 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--particles", type=int, default=0, help="particles of the whole pool (default: 30 on one GPU, 3000 sharded over several)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--sweep", type=str, default="300,375,3000", help="extra single-GPU particle counts (N=1 only), '' to skip")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (--full)")
+    ap.add_argument("--sweep", type=str, default="300,375,3000", help="extra single-GPU particle counts (--full, N=1 only), '' to skip")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the run behind `value` computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside `value` too: kernel breakdown, variants, baselines, sweeps, scaling figures")
     args = ap.parse_args()
     if args.particles <= 0:
         args.particles = 30 if args.gpus == 1 else 3000
@@ -601,38 +608,44 @@ def main():
                 "brushfire_routed": c["brushfire_routed"]}
 
     # `value` comes from a pass WITHOUT the per-kernel hipEvent brackets (they cost two extra device-to-host copies and four
-    # event records per step); the kernel breakdown and the roofline durations come from a second pass of the same K steps
-    # with the brackets on.
-    main_run = run(P_total, K, W, profile=False, dump=args.dump_outputs if world == 1 else None)
-    assert main_run["updates"] == K, "every scan of the log must pass the motion gate"
-    # `value` is only ever the EXACT brushfire (bit-identical to the reference): what ran is read back from the library
-    assert main_run["counters"]["brushfire_mode"] == 0, main_run["counters"]
-    prof_run = run(P_total, K, W, profile=True)
+    # event records per step); with --full the kernel breakdown and the roofline durations come from a second pass of the same
+    # K steps with the brackets on.  N > 1: `value` is rank 0's C++ object below, and the torch.distributed ranks run only
+    # with --full.
+    main_run, prof_run, resample_run = None, None, None
+    if world == 1 or args.full:
+        main_run = run(P_total, K, W, profile=False, dump=args.dump_outputs if world == 1 else None)
+        assert main_run["updates"] == K, "every scan of the log must pass the motion gate"
+        # `value` is only ever the EXACT brushfire (bit-identical to the reference): what ran is read back from the library
+        assert main_run["counters"]["brushfire_mode"] == 0, main_run["counters"]
     # with the default gain (1 / (3 P)) resampling is rare; a variant with a smaller measurement gain makes the
-    # filter resample (and, sharded, ship particles between GPUs): always run, on one GPU and sharded.  0.01 resamples at 30
+    # filter resample (and, sharded, ship particles between GPUs): run by --full, on one GPU and sharded.  0.01 resamples at 30
     # particles; 3000 particles need 1e-4 (at 0.01 they never resample on this log).
     forced_gain = 0.01 if P_total < 1000 else 1e-4
-    resample_run = run(P_total, K, W, gain=forced_gain)
-    if world > 1:
-        assert resample_run["resamples"] > 0, "the forced-resample variant did not resample"
-        assert resample_run["shipped_particles"] > 0 and resample_run["shipped_bytes"] > 0, "no particle crossed a shard boundary"
+    if args.full:
+        prof_run = run(P_total, K, W, profile=True)
+        resample_run = run(P_total, K, W, gain=forced_gain)
+        if world > 1:
+            assert resample_run["resamples"] > 0, "the forced-resample variant did not resample"
+            assert resample_run["shipped_particles"] > 0 and resample_run["shipped_bytes"] > 0, "no particle crossed a shard boundary"
     single, cpp_multi, cpp_multi_forced, weak, share = None, None, None, None, None
     if world > 1:
         # base of the strong-scaling figure: the same pool on ONE GPU (rank 0's), unsharded; then the same pool as one C++ object
         # over all N devices (lama::PFSlam2D, Options::gpus = N: the PRODUCT path of a multi-GPU node -- it is what `value` reports);
         # the other ranks have released their contexts and wait
         if rank == 0:
-            single = run(P_total, K, W, profile=False, sharded=False)
-            # one GPU's share of the pool alone on one GPU: the step time no amount of sharding can beat (the brushfire chain of a
-            # particle does not shrink with the shard) -> predicted ceiling of the strong-scaling curve
-            share = run(max(P_total // world, 1), K, W, profile=False, sharded=False)
+            if args.full:
+                single = run(P_total, K, W, profile=False, sharded=False)
+                # one GPU's share of the pool alone on one GPU: the step time no amount of sharding can beat (the brushfire chain
+                # of a particle does not shrink with the shard) -> predicted ceiling of the strong-scaling curve
+                share = run(max(P_total // world, 1), K, W, profile=False, sharded=False)
             cpp_multi = run_cpp_multi(P_total, world, K, W, dump=args.dump_outputs)
-            cpp_multi_forced = run_cpp_multi(P_total, world, K, W, gain=forced_gain)
-            assert cpp_multi_forced["resamples"] > 0 and cpp_multi_forced["shipped_particles"] > 0, cpp_multi_forced
-            # weak scaling: the single-GPU pool (3000 particles) on EVERY GPU (one device for all shards: its share instead)
-            per_gpu = P_total if torch.cuda.device_count() >= world else max(P_total // world, 1)
-            weak = run_cpp_multi(per_gpu * world, world, K, W)
-            weak["particles_per_gpu"] = per_gpu
+            if args.full:
+                cpp_multi_forced = run_cpp_multi(P_total, world, K, W, gain=forced_gain)
+                assert cpp_multi_forced["resamples"] > 0 and cpp_multi_forced["shipped_particles"] > 0, cpp_multi_forced
+                # weak scaling: the single-GPU pool (3000 particles) on EVERY GPU (one device for all shards: its share instead)
+                per_gpu = P_total if torch.cuda.device_count() >= world else max(P_total // world, 1)
+                weak = run_cpp_multi(per_gpu * world, world, K, W)
+                weak["particles_per_gpu"] = per_gpu
         # the other ranks wait on the rendezvous store (a blocking socket read): a process-group barrier here would park an RCCL
         # kernel on every other GPU -- or spin on the host with gloo -- underneath the object that rank 0 is timing
         store = torch.distributed.distributed_c10d._get_default_store()
@@ -643,29 +656,48 @@ def main():
 
     if rank != 0:
         return
-    c = prof_run["counters"]
+    head = main_run if world == 1 else cpp_multi
     result = {
-        "metric": "particle-scans/sec", "value": main_run["value"], "unit": "particle-scans/s",
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": main_run["ms_per_step"],
+        "metric": "particle-scans/sec", "value": head["value"], "unit": "particle-scans/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": head["ms_per_step"],
         "higher_is_better": True, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": f"PFSlam2D {P_total} particles" + (f" ({P_total // world}/GPU, fixed pool sharded over {world} GPUs)" if world > 1 else "") +
                                ", 1080-beam synthetic corridor log "
                                f"(SURVEY.md 8(d)), res 0.05 m, patch 32, l2_max 0.5, GN+Cauchy(0.15), seed 42",
-                   "particles": P_total, "beams": 1080, "parallelism": f"particle-shard x{world}" + (" (all ranks on GPU 0, gloo)" if one_device and world > 1 else ""),
-                   "resamples_in_timed_region": main_run["resamples"], "best_pose_error_m": main_run["pose_err_m"],
-                   "kernels_that_ran": effective_modes(main_run["counters"])},
-        "kernel_ms_per_step": {"scan_match": c["ms_scan_match"] / max(c["launches_scan_match"], 1),
-                               "update_maps": c["ms_update_maps"] / max(c["launches_update_maps"], 1),
-                               "raycast": c["ms_raycast"] / max(c["launches_raycast"], 1),
-                               "brushfire": c["ms_brushfire"] / max(c["launches_brushfire"], 1),
-                               "resample": c["ms_resample"] / max(c["launches_resample"], 1) if c["launches_resample"] else 0.0,
-                               "measured_in": "second pass of the same steps with hipEvent brackets on (ms_per_step there: %.4f)" % prof_run["ms_per_step"]},
-        "brushfire_chains": chain_spread(c, P_total // world),
-        "memory": memory_block(c),
+                   "particles": P_total, "beams": 1080, "parallelism": f"particle-shard x{world}" + (" (all ranks on GPU 0, gloo)" if one_device and world > 1 else "")},
         "devices_visible": torch.cuda.device_count(), "process_group": {"backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
                                                                         "ranks": world},
         "value_source": "one process, one context (lama::PFSlam2D on one GPU)",
     }
+    if main_run is not None:
+        result["config"].update({"resamples_in_timed_region": main_run["resamples"], "best_pose_error_m": main_run["pose_err_m"],
+                                 "kernels_that_ran": effective_modes(main_run["counters"])})
+    if world > 1:
+        # (since round 4 the N > 1 `value` is the C++ object's, not the torch.distributed ranks' -- ADVICE r04: said here, at the top level)
+        result["value_source"] = f"lama::PFSlam2D, Options::gpus = {world} (one process, {cpp_multi['devices']} device(s)), run by rank 0; rounds 1-3 reported torch_distributed_ranks here"
+        if torch.cuda.device_count() < world:
+            result["devices_short"] = f"{torch.cuda.device_count()} device(s) for {world} shards: the shards SHARE devices, this is not a scaling measurement"
+    if args.full:
+        full_report(result, args, run, main_run, prof_run, resample_run, forced_gain, single, share, cpp_multi, cpp_multi_forced, weak,
+                    pts, odom, world)
+    print(json.dumps(result))
+
+
+def full_report(result, args, run, main_run, prof_run, resample_run, forced_gain, single, share, cpp_multi, cpp_multi_forced, weak,
+                pts, odom, world):
+    """--full: what the line reports beside `value` (rank 0; the runs of the N = 1 extras are made here, the others before)."""
+    import torch
+    import iris_lama_amd.ffi as F
+    K, W, P_total = args.steps, args.warmup, args.particles
+    c = prof_run["counters"]
+    result["kernel_ms_per_step"] = {"scan_match": c["ms_scan_match"] / max(c["launches_scan_match"], 1),
+                                    "update_maps": c["ms_update_maps"] / max(c["launches_update_maps"], 1),
+                                    "raycast": c["ms_raycast"] / max(c["launches_raycast"], 1),
+                                    "brushfire": c["ms_brushfire"] / max(c["launches_brushfire"], 1),
+                                    "resample": c["ms_resample"] / max(c["launches_resample"], 1) if c["launches_resample"] else 0.0,
+                                    "measured_in": "second pass of the same steps with hipEvent brackets on (ms_per_step there: %.4f)" % prof_run["ms_per_step"]}
+    result["brushfire_chains"] = chain_spread(c, P_total // world)
+    result["memory"] = memory_block(c)
     if world == 1:
         result["summary_buckets_ms_per_update"] = run(P_total, K, W, summary=True)["buckets_ms"]
         # the N > 1 lines shard BASELINE's config 3 (a FIXED pool of 3000 particles) over the GPUs: strong scaling.  This N = 1 line is
@@ -682,11 +714,6 @@ def main():
         result["torch_distributed_ranks"] = {"value": main_run["value"], "ms_per_step": main_run["ms_per_step"],
                                              "exchange_ms_per_step": main_run["exchange_ms_per_step"],
                                              "note": "one process per GPU, all-gather of the log-likelihoods over the process group, barrier + max over ranks"}
-        result["value"], result["ms_per_step"] = cpp_multi["value"], cpp_multi["ms_per_step"]
-        # (since round 4 the N > 1 `value` is the C++ object's, not the torch.distributed ranks' -- ADVICE r04: said here, at the top level)
-        result["value_source"] = f"lama::PFSlam2D, Options::gpus = {world} (one process, {cpp_multi['devices']} device(s)), run by rank 0; rounds 1-3 reported torch_distributed_ranks here"
-        if torch.cuda.device_count() < world:
-            result["devices_short"] = f"{torch.cuda.device_count()} device(s) for {world} shards: the shards SHARE devices, this is not a scaling measurement"
         result["peer_access"] = cpp_multi_forced.get("peer") if (cpp_multi_forced.get("peer") or {}).get("bytes") else cpp_multi.get("peer")
         result["rccl_ranks"] = world if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else 0
         # what the first real curve can be read against: the clones of a resample cross at most one xGMI link per (source, destination)
@@ -830,7 +857,6 @@ def main():
                              "raycast_ms": cc["ms_raycast"] / max(cc["launches_raycast"], 1)}
         result["canonical_brushfire_mode"] = canon
         result["next_rows"] = next_rows(F, with_cpu=not args.no_cpu)
-    print(json.dumps(result))
 
 
 if __name__ == "__main__":

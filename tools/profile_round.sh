@@ -13,7 +13,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-CMD="python bench.py --steps 20 --warmup 5 --no-cpu --sweep="      # the driver's command (--steps 20 --warmup 5)
+CMD="python bench.py --full --steps 20 --warmup 5 --no-cpu --sweep="      # every pass of the P = 30 line (--steps 20 --warmup 5)
 for w in $WHAT; do
 case $w in
 trace)
@@ -28,14 +28,14 @@ sq)
   A="SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_BUSY_CYCLES"
   B="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU"
   for P in 30 3000; do
-    C8="python bench.py --steps 8 --warmup 3 --no-cpu --sweep= --particles $P"
+    C8="python bench.py --full --steps 8 --warmup 3 --no-cpu --sweep= --particles $P"
     rocprofv3 --kernel-trace --pmc $A -d "$OUT/sqA_$P" -o p -- $C8 > "$OUT/sqA_$P.log" 2>&1
     rocprofv3 --kernel-trace --pmc $B -d "$OUT/sqB_$P" -o p -- $C8 > "$OUT/sqB_$P.log" 2>&1
     (python tools/pmc_kernel.py "$OUT/sqA_$P/p_results.db" "k_brushfire<1024"; python tools/pmc_kernel.py "$OUT/sqB_$P/p_results.db" "k_brushfire<1024") > "$OUT/sq_brushfire_$P.txt" 2>&1
     rm -rf "$OUT"/sq[AB]_$P
   done ;;
 timeline)
-  rocprofv3 --kernel-trace --stats -d "$OUT/tl" -o p -- python bench.py --steps 8 --warmup 3 --no-cpu --sweep= --particles 3000 > "$OUT/tl.log" 2>&1
+  rocprofv3 --kernel-trace --stats -d "$OUT/tl" -o p -- python bench.py --full --steps 8 --warmup 3 --no-cpu --sweep= --particles 3000 > "$OUT/tl.log" 2>&1
   python - "$OUT/tl/p_results.db" > "$OUT/timeline_3000.txt" 2>&1 <<'PY'
 import sqlite3, sys
 rows = sqlite3.connect(sys.argv[1]).cursor().execute("select name, start, end, grid_x from kernels order by start").fetchall()

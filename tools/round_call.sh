@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 timeout 2400 python -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1
 echo "rc=$?" >> "$OUT/gpu_tests.log"
 tail -4 "$OUT/gpu_tests.log"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"
 python - <<PY
 import json

@@ -21,7 +21,7 @@ def q(db, sql):
 
 
 out = [f"# rocprofv3 summary ({tag})", "",
-       f"Command: `rocprofv3 --kernel-trace --stats -- python bench.py --steps {K} --warmup 5 --no-cpu --sweep ''` "
+       f"Command: `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps {K} --warmup 5 --no-cpu --sweep ''` "
        "(MI355X, gfx950, ROCm 7.2).", "",
        f"## All dispatches (rocprofv3 `top_kernels` view: first scan + 5 warm-up + {K} timed updates; bench.py runs the pass four times: value, kernel brackets, forced resampling, Summary)", "",
        "| kernel | calls | total ms | avg ms | % |", "|---|---:|---:|---:|---:|"]
