@@ -4,6 +4,7 @@
 #     cmake -Diris_lama_DIR=<this repo>/cmake ...
 # The imported target is the host library liblama_host.so (it dlopen()s its sibling liblama_hip.so -- liblama_hip_wide.so for an l2_max beyond 127 cells -- at run time);
 # build both first with `make -C iris_lama_amd` (or python -c "import __graft_entry__ as g; g.build()").
+# The target carries every public class under include/lama/ (PFSlam2D, Slam2D, Loc2D, LidarOdometry2D, SimplePGO, MapBuilder2D, ...).
 # Eigen3 is optional here: when it is found the public vector types are Eigen's (include/lama/types.h), otherwise the
 # POD stand-ins are used.
 get_filename_component(_lama_root "${CMAKE_CURRENT_LIST_DIR}/.." ABSOLUTE)

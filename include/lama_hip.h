@@ -238,6 +238,32 @@ int32_t lama_hip_match_cell_distances(lama_hip_ctx* ctx, uint32_t particle, cons
                                       const double* sensor_origin3, const double* sensor_quat_wxyz, const double* pose,
                                       double* distances);
 
+/* Map rebuild from posed key scans (GraphSlam2D::generateOccupancyMap, src/graph_slam2d.cpp:131-164) on `particle`'s FREQUENCY
+ * occupancy map, all scans in one order-free pass (csrc/lama_map_build.h).  Per scan k and point p, the reference's loop:
+ * tf = T(pose_k) * T(sensor_origin_k) * R(sensor_quat_k); hit = tf * p; setOccupied(w2m(hit)); with flags bit 0 ("full") also
+ * computeRay(w2m(tf.translation()), w2m(hit)) -- end points excluded -- with setFree on every cell.  No truncated_ray /
+ * truncated_range (the reference applies none here).  The call ADDS to the map that is there: scans [0, a) then [a, K) in two calls
+ * equal one call (the reference's mapping_keyid increment), and so does any order of the scans -- the uint16 counters commute, each
+ * field modulo 2^16 on its own.  flags bit 1 ("prune") runs FrequencyOccupancyMap::prune afterwards
+ * (src/sdm/frequency_occupancy_map.cpp:149-158: visited == 1 and occupied <= 1 becomes {0, 0}; masks and patches stay).  The
+ * particle's distance map is not touched.
+ *   poses4 [K][4] {c, s, tx, ty};  pts_xyz: the points of all scans, scan k = points scan_offsets[k] .. scan_offsets[k + 1] - 1
+ *   (K + 1 non-decreasing offsets);  sensor_origin3_per_scan [K][3] / sensor_quat_wxyz_per_scan [K][4] (NULL: zero / identity).
+ * Everything that can refuse the call -- LAMA_HIP_E_WINDOW (the scans, together with the map so far, are wider than the largest
+ * window, or a ray is longer than 8191 cells), LAMA_HIP_E_CAPACITY, LAMA_HIP_E_INVALID (a non-finite point or pose) -- is found
+ * BEFORE a patch is allocated or a cell changes.  On a context that has not seen lama_hip_pf_init the call also places the map
+ * window (like lama_hip_map_add_obstacles).  num_scans == 0, or scans without any point, change nothing (prune included). */
+#define LAMA_HIP_MAP_BUILD_FULL 1u
+#define LAMA_HIP_MAP_BUILD_PRUNE 2u
+int32_t lama_hip_map_integrate_scans(lama_hip_ctx* ctx, uint32_t particle, uint32_t num_scans, const double* poses4,
+                                     const double* pts_xyz, const uint32_t* scan_offsets, const double* sensor_origin3_per_scan,
+                                     const double* sensor_quat_wxyz_per_scan, uint32_t flags);
+/* The map coordinates {x, y} of every cell of `particle`'s frequency occupancy map with isOccupied (visited != 0 and
+ * occupied / visited > 0.25 evaluated in double, src/sdm/frequency_occupancy_map.cpp:38-45,132-138), compacted on the device, in
+ * Map::visit_all_cells order: ascending reference patch index (Map::m2p), then the cell index inside the patch.  *n = their number;
+ * up to `cap` of them are written to cells_xy (NULL: only the number is wanted). */
+int32_t lama_hip_map_occupied_cells(lama_hip_ctx* ctx, uint32_t particle, uint32_t cap, uint32_t* cells_xy, uint32_t* n);
+
 /* Particle shipping for multi-GPU resampling (one context per GPU): serialise one particle (pose + both
  * maps, used patches only) into a DEVICE buffer / restore it into slot `particle` of this context.
  * export returns the number of bytes needed in *bytes when buf == NULL. */

@@ -226,6 +226,35 @@ typedef struct lama_pgo_report {
 int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4, uint32_t ne,
                       const int32_t* fixed_idx, const double* fixed4, uint32_t nf, int32_t device, double* out4, lama_pgo_report* report,
                       int8_t* trace, uint32_t trace_cap, char* err, int errcap);
+/* ---- lama::MapBuilder2D (include/lama/map_builder_2d.h), flattened: a map rebuilt from posed key scans ---- */
+typedef struct lama_mapbuilder lama_mapbuilder;
+typedef struct lama_mapbuilder_options {
+    double resolution, l2_max;          /* l2_max 0: no distance map */
+    uint32_t patch_size;
+    int32_t full, prune, gpu_device;
+    uint32_t window_patches, occ_patch_capacity, dm_patch_capacity;
+} lama_mapbuilder_options;
+void lama_mapbuilder_default_options(lama_mapbuilder_options* o);
+lama_mapbuilder* lama_mapbuilder_create(const lama_mapbuilder_options* o, char* err, int errcap);
+void lama_mapbuilder_destroy(lama_mapbuilder* b);
+const char* lama_mapbuilder_last_error(const lama_mapbuilder* b);
+const char* lama_mapbuilder_engine_origin(const lama_mapbuilder* b);
+void* lama_mapbuilder_device_context(const lama_mapbuilder* b);
+/* add: returns the key id (< 0: error); pose4 {c, s, tx, ty}.  set_poses: one pose per key.  build / reset: 0 or < 0. */
+int64_t lama_mapbuilder_add(lama_mapbuilder* b, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz, const double* pose4);
+int lama_mapbuilder_set_pose(lama_mapbuilder* b, uint64_t key, const double* pose4);
+int lama_mapbuilder_set_poses(lama_mapbuilder* b, const double* poses4, uint64_t n);
+int lama_mapbuilder_build(lama_mapbuilder* b);
+int lama_mapbuilder_reset(lama_mapbuilder* b);
+/* the occupied cells the last build found (returns their number; up to cap {x, y} pairs written), and its wall-clock
+ * milliseconds by stage: integrate, occupied list, distance map */
+int64_t lama_mapbuilder_occupied_cells(const lama_mapbuilder* b, uint32_t* xy_out, uint64_t cap);
+int lama_mapbuilder_timing(const lama_mapbuilder* b, double* ms3);
+/* visit_all_cells of getOccupancyMap() (which 0) / getDistanceMap() (which 1): returns the count, < 0 when there is no map */
+int64_t lama_mapbuilder_view_cells(lama_mapbuilder* b, int which, uint32_t* xy_out, uint64_t cap);
+/* lama::Solve(GaussNewton + Cauchy(0.15), MatchSurface2D(getDistanceMap(), scan, pose)): pose4 in / out */
+int lama_mapbuilder_match_solve(lama_mapbuilder* b, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz,
+                                double* pose4, uint32_t max_iterations, uint32_t* iterations);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

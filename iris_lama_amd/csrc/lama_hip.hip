@@ -17,6 +17,7 @@
 
 #include "lama_kernels.h"
 #include "lama_pgo.h"
+#include "lama_map_build.h"
 #include "../host/pgo_pattern.hpp"
 
 using namespace lama_dev;
@@ -223,6 +224,11 @@ struct lama_hip_ctx {
     PinVec<uint8_t> h_status;
     PinVec<uint8_t> h_results;
     DevBuf<int32_t> d_oldcounts;
+    // lama_hip_map_integrate_scans / lama_hip_map_occupied_cells (lama_map_build.h): inputs, ray records, the bin table over the call's
+    // box, offsets, touched-patch list and slots, bins; all grow-only
+    DevBuf<double> d_mb_pts, d_mb_tfs; DevBuf<uint32_t> d_mb_offs; DevBuf<lama_dev::MbRay> d_mb_rays;
+    DevBuf<uint32_t> d_mb_table, d_mb_off, d_mb_list, d_mb_bins; DevBuf<int32_t> d_mb_slot; DevBuf<uint64_t> d_mb_meta;
+    PinVec<double> h_mb_tfs; PinVec<uint32_t> h_mb_offs; PinVec<uint64_t> h_mb_meta;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
 
     double scan_reach = 0.0;          // largest point distance of the resident scan (sensor frame, metres)
@@ -848,6 +854,17 @@ int32_t ensure_window(lama_hip_ctx* c, int64_t x0, int64_t x1, int64_t y0, int64
     const int64_t nox = c->initialised ? place(ox, hx0, hx1) : (hx0 + hx1 + 1) / 2 - newW / 2;
     const int64_t noy = c->initialised ? place(oy, hy0, hy1) : (hy0 + hy1 + 1) / 2 - newW / 2;
     return regrid_window(c, (uint32_t)newW, nox, noy);
+}
+
+// a context whose map is placed by something else than a first scan (an uploaded map, a list of obstacles, integrated key scans):
+// identity poses, and the window has been placed by the caller
+int32_t start_without_first_scan(lama_hip_ctx* c)
+{
+    if (c->initialised) return LAMA_HIP_OK;
+    for (uint32_t p = 0; p < c->P; ++p) { c->h_poses[4 * p] = 1.0; c->h_poses[4 * p + 1] = 0.0; c->h_poses[4 * p + 2] = 0.0; c->h_poses[4 * p + 3] = 0.0; }
+    HIPCHK(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), sizeof(double) * 4 * c->P, hipMemcpyHostToDevice, c->stream));
+    c->initialised = true;
+    return LAMA_HIP_OK;
 }
 
 int32_t fit_window(lama_hip_ctx* c, const Affine& mtf, uint32_t first, uint32_t count)
@@ -1687,11 +1704,7 @@ int32_t lama_hip_pf_upload_map(lama_hip_ctx* c, uint32_t particle, int32_t kind,
         const int32_t rw = ensure_window(c, x0, x1, y0, y1);
         if (rw) return rw;
     }
-    if (!c->initialised) {
-        for (uint32_t p = 0; p < c->P; ++p) { c->h_poses[4 * p] = 1.0; c->h_poses[4 * p + 1] = 0.0; c->h_poses[4 * p + 2] = 0.0; c->h_poses[4 * p + 3] = 0.0; }
-        HIPCHK(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), sizeof(double) * 4 * c->P, hipMemcpyHostToDevice, c->stream));
-        c->initialised = true;
-    }
+    { const int32_t rf = start_without_first_scan(c); if (rf) return rf; }
     {   // room for the patches (the particle's region moves if it must; what it held is replaced below)
         const HostPart& hp = c->h_part[particle];
         const uint32_t cap = dm ? hp.dm_cap : hp.occ_cap;
@@ -2031,11 +2044,7 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
         const int32_t rw = ensure_window(c, x0 - r, x1 + r, y0 - r, y1 + r);
         if (rw) return rw;
     }
-    if (!c->initialised) {
-        for (uint32_t p = 0; p < c->P; ++p) { c->h_poses[4 * p] = 1.0; c->h_poses[4 * p + 1] = 0.0; c->h_poses[4 * p + 2] = 0.0; c->h_poses[4 * p + 3] = 0.0; }
-        HIPCHK(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), sizeof(double) * 4 * c->P, hipMemcpyHostToDevice, c->stream));
-        c->initialised = true;
-    }
+    { const int32_t rf = start_without_first_scan(c); if (rf) return rf; }
     {   // every distance-map patch this call can allocate lies within guard_r patches of a listed cell's patch: make room first
         const int r = (int)(((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u);
         std::vector<uint64_t> keys;
@@ -2077,6 +2086,160 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
     hipLaunchKernelGGL(k_brushfire_slow, dim3(1), dim3(UM_BLOCK), 0, c->stream, prm, (int)particle);
     HIPCHK(c, hipGetLastError());
     return check_device_errors(c, true, false);
+}
+
+// ---- lama_map_build.h: K posed key scans into one occupancy map, and the occupied cells of a map -----------------------------------
+int32_t lama_hip_map_integrate_scans(lama_hip_ctx* c, uint32_t particle, uint32_t K, const double* poses4, const double* pts, const uint32_t* offs,
+                                     const double* origins, const double* quats, uint32_t flags)
+{
+    if (!c || particle >= c->P || (flags & ~3u)) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    if (c->cfg.occupancy_policy != 0) return fail(c, LAMA_HIP_E_INVALID, "key scans are integrated into a frequency occupancy map (cfg.occupancy_policy 0)");
+    if (K == 0) return LAMA_HIP_OK;
+    if (!poses4 || !offs) return fail(c, LAMA_HIP_E_INVALID, "poses4 / scan_offsets missing");
+    for (uint32_t k = 0; k < K; ++k)
+        if (offs[k + 1] < offs[k]) return fail(c, LAMA_HIP_E_INVALID, "scan_offsets must not decrease");
+    const uint64_t total64 = (uint64_t)offs[K] - offs[0];
+    if (total64 == 0) return LAMA_HIP_OK;                           // nothing but empty scans: the reference's loop bodies never run
+    if (!pts || total64 >= (uint64_t)MB_HIT) return fail(c, LAMA_HIP_E_INVALID, "pts_xyz missing, or more than 2^31 - 1 points");
+    const uint32_t total = (uint32_t)total64;
+    const bool full = flags & 1u, prune = flags & 2u;
+    // tf = T(pose) * T(sensor origin) * R(sensor orientation) per scan, on the host like every map update's (host_scan_tf)
+    c->h_mb_tfs.resize((size_t)12 * K); c->h_mb_offs.resize((size_t)K + 1);
+    for (uint32_t k = 0; k < K; ++k) {
+        host_scan_tf(poses4 + 4 * (size_t)k, moving_tf(origins ? origins + 3 * (size_t)k : nullptr, quats ? quats + 4 * (size_t)k : nullptr), &c->h_mb_tfs[12 * (size_t)k]);
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(c->h_mb_tfs[12 * (size_t)k + j])) return fail(c, LAMA_HIP_E_INVALID, "a key pose or sensor transform is not finite");
+    }
+    for (uint32_t k = 0; k <= K; ++k) c->h_mb_offs[k] = offs[k] - offs[0];
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, c->d_mb_pts.grow((size_t)3 * total)); HIPCHK(c, c->d_mb_tfs.grow((size_t)12 * K)); HIPCHK(c, c->d_mb_offs.grow((size_t)K + 1));
+    HIPCHK(c, c->d_mb_rays.grow(total)); HIPCHK(c, c->d_mb_meta.grow(8));
+    c->h_mb_meta.resize(8);
+    MbBounds* const d_bounds = reinterpret_cast<MbBounds*>(c->d_mb_meta.p);
+    MbMeta* const d_meta = reinterpret_cast<MbMeta*>(c->d_mb_meta.p + 4);
+    {
+        MbBounds b0{0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0u, 0u, 0ull};
+        std::memcpy(c->h_mb_meta.data(), &b0, sizeof(b0));
+    }
+    // (all copies on the context's own stream, the one whose kernels read the buffers: DESIGN.md section 8)
+    HIPCHK(c, hipMemcpyAsync(c->d_mb_meta, c->h_mb_meta.data(), sizeof(MbBounds), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_mb_pts, pts + 3 * (size_t)offs[0], sizeof(double) * 3 * total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_mb_tfs, c->h_mb_tfs.data(), sizeof(double) * 12 * K, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_mb_offs, c->h_mb_offs.data(), sizeof(uint32_t) * ((size_t)K + 1), hipMemcpyHostToDevice, c->stream));
+    DevParams prm = make_params(c);
+    prm.trunc_ray = 0.0; prm.trunc_range = 0.0;                     // generateOccupancyMap truncates nothing
+    const unsigned ray_blocks = (total + 255u) / 256u;
+    MbRay* const d_rays = c->d_mb_rays;
+    {
+        Timer t(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
+        hipLaunchKernelGGL(k_mb_geom, dim3(ray_blocks), dim3(256), 0, c->stream, prm, (const double*)c->d_mb_pts, (const uint32_t*)c->d_mb_offs,
+                           (const double*)c->d_mb_tfs, K, total, full ? 1 : 0, d_rays, d_bounds);
+        t.stop();
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_mb_meta.data(), c->d_mb_meta, sizeof(MbBounds), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MbBounds bnd;
+    std::memcpy(&bnd, c->h_mb_meta.data(), sizeof(bnd));
+    // ---- everything that can refuse the call comes before anything of the map changes ----
+    if (bnd.flags & MB_NONFINITE) { resolve_timers(c); return fail(c, LAMA_HIP_E_INVALID, "a key scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)"); }
+    if (bnd.flags & MB_TOO_LONG) { resolve_timers(c); return fail(c, LAMA_HIP_E_WINDOW, "a ray is longer than 8191 cells"); }
+    {
+        const int64_t x0 = bnd.x0, x1 = bnd.x1, y0 = bnd.y0, y1 = bnd.y1;
+        const int64_t ux0 = c->mb_valid ? std::min(c->mbx0, x0) : x0, ux1 = c->mb_valid ? std::max(c->mbx1, x1) : x1;
+        const int64_t uy0 = c->mb_valid ? std::min(c->mby0, y0) : y0, uy1 = c->mb_valid ? std::max(c->mby1, y1) : y1;
+        if (ux1 - ux0 + 1 > LAMA_HIP_MAX_WINDOW || uy1 - uy0 + 1 > LAMA_HIP_MAX_WINDOW) {
+            resolve_timers(c);
+            return fail(c, LAMA_HIP_E_WINDOW, "the key scans and the map so far are wider than the largest device window (1016 patches)");
+        }
+        const int32_t rw = ensure_window(c, x0, x1, y0, y1);
+        if (rw) { resolve_timers(c); return rw; }
+    }
+    { const int32_t rf = start_without_first_scan(c); if (rf) return rf; }
+    const uint32_t bx0 = bnd.x0 - (c->wx0 >> 5), by0 = bnd.y0 - (c->wy0 >> 5), bw = bnd.x1 - bnd.x0 + 1u, bh = bnd.y1 - bnd.y0 + 1u, nb = bw * bh;
+    if (bx0 + bw > c->W || by0 + bh > c->W) { resolve_timers(c); return fail(c, LAMA_HIP_E_WINDOW, "the key scans fell outside the device window"); }
+    HIPCHK(c, c->d_mb_table.grow(nb)); HIPCHK(c, c->d_mb_off.grow((size_t)nb + 1)); HIPCHK(c, c->d_mb_list.grow(nb)); HIPCHK(c, c->d_mb_slot.grow(nb));
+    prm = make_params(c);
+    prm.trunc_ray = 0.0; prm.trunc_range = 0.0;
+    uint32_t* const d_table = c->d_mb_table; uint32_t* const d_off = c->d_mb_off; uint32_t* const d_list = c->d_mb_list; int32_t* const d_slot = c->d_mb_slot;
+    HIPCHK(c, hipMemsetAsync(d_table, 0, sizeof(uint32_t) * nb, c->stream));
+    {
+        Timer t(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
+        hipLaunchKernelGGL(k_mb_bin, dim3(ray_blocks), dim3(256), 0, c->stream, prm, (const MbRay*)d_rays, total, bx0, by0, bw, bh, d_table, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(k_mb_scan, dim3(1), dim3(MB_SCAN_BLOCK), 0, c->stream, prm, (int)particle, bx0, by0, bw, nb, d_table, d_off, d_list, d_meta);
+        t.stop();
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_mb_meta.data() + 4, d_meta, sizeof(MbMeta), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    MbMeta meta;
+    std::memcpy(&meta, c->h_mb_meta.data() + 4, sizeof(meta));
+    const uint64_t want = (uint64_t)c->h_counts[2 * particle + 1] + meta.need;
+    if (want > MAX_PATCHES) { resolve_timers(c); return fail(c, LAMA_HIP_E_CAPACITY, "the particle's occupancy map would exceed 32767 patches"); }
+    if (want > c->h_part[particle].occ_cap) {
+        const int32_t rg = set_capacities(c, {CapRequest{particle, c->h_part[particle].dm_cap, want_capacity(c->floor_occ, (uint32_t)want, 0u)}});
+        if (rg) { resolve_timers(c); return rg; }
+        prm = make_params(c);
+        prm.trunc_ray = 0.0; prm.trunc_range = 0.0;
+    }
+    HIPCHK(c, c->d_mb_bins.grow(meta.items, (size_t)1 << 16));
+    uint32_t* const d_bins = c->d_mb_bins;
+    {
+        Timer t(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
+        hipLaunchKernelGGL(k_mb_alloc, dim3((meta.touched + 255u) / 256u), dim3(256), 0, c->stream, prm, (int)particle, bx0, by0, bw, (const uint32_t*)d_list, meta.touched, d_slot);
+        hipLaunchKernelGGL(k_mb_bin, dim3(ray_blocks), dim3(256), 0, c->stream, prm, (const MbRay*)d_rays, total, bx0, by0, bw, bh, d_table, (const uint32_t*)d_off, d_bins);
+        hipLaunchKernelGGL(k_mb_patches, dim3(meta.touched), dim3(256), 0, c->stream, prm, (int)particle, bx0, by0, bw, (const uint32_t*)d_list, (const int32_t*)d_slot,
+                           (const uint32_t*)d_off, (const uint32_t*)d_bins, (const MbRay*)d_rays);
+        if (prune) hipLaunchKernelGGL(k_mb_prune, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(want, 1), 4096)), dim3(256), 0, c->stream, prm, (int)particle);
+        t.stop();
+    }
+    HIPCHK(c, hipGetLastError());
+    c->h_err.resize(1);
+    HIPCHK(c, hipMemcpyAsync(&c->h_counts[2 * particle], c->ms.counts + 2 * particle, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_err[0], c->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resolve_timers(c);
+    c->ctr.ray_cells += bnd.visits;
+    { uint64_t oc = 0; for (uint32_t p = 0; p < c->P; ++p) oc += (uint64_t)c->h_counts[2 * p + 1]; c->ctr.occ_patches = oc; }
+    c->visit_bound = 65535u;                                      // unknown counters: the wrap guard looks before the next parallel ray-cast
+    if (c->h_err[0] != 0) {                                       // (room was made for every patch: not expected)
+        HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int32_t), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return fail(c, LAMA_HIP_E_CAPACITY, "an occupancy patch could not be allocated while integrating key scans");
+    }
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_map_occupied_cells(lama_hip_ctx* c, uint32_t particle, uint32_t cap, uint32_t* cells_xy, uint32_t* n_out)
+{
+    if (!c || !n_out || particle >= c->P) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    if (c->cfg.occupancy_policy != 0) return fail(c, LAMA_HIP_E_INVALID, "occupied cells are listed for a frequency occupancy map (cfg.occupancy_policy 0)");
+    *n_out = 0;
+    const uint32_t count = (uint32_t)c->h_counts[2 * particle + 1];
+    if (count == 0) return LAMA_HIP_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, c->d_mb_table.grow(count)); HIPCHK(c, c->d_mb_off.grow((size_t)count + 1)); HIPCHK(c, c->d_mb_list.grow(count)); HIPCHK(c, c->d_mb_slot.grow(count));
+    uint32_t* const d_cnt = c->d_mb_table; uint32_t* const d_off = c->d_mb_off; uint32_t* const d_pos = c->d_mb_list; int32_t* const d_slot = c->d_mb_slot;
+    const DevParams prm = make_params(c);
+    hipLaunchKernelGGL(k_mb_order, dim3(1), dim3(MB_SCAN_BLOCK), 0, c->stream, prm, (int)particle, d_slot, d_pos);
+    hipLaunchKernelGGL(k_mb_occupied, dim3(count), dim3(256), 0, c->stream, prm, (int)particle, (const int32_t*)d_slot, (const uint32_t*)d_pos, d_cnt, (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_mb_exscan, dim3(1), dim3(MB_SCAN_BLOCK), 0, c->stream, (const uint32_t*)d_cnt, count, d_off);
+    HIPCHK(c, hipGetLastError());
+    uint32_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, d_off + count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_out = total;
+    const uint32_t m = std::min(cap, total);
+    if (!cells_xy || m == 0) return LAMA_HIP_OK;
+    HIPCHK(c, c->d_mb_bins.grow(2 * (size_t)m, (size_t)1 << 16));
+    uint32_t* const d_out = c->d_mb_bins;
+    hipLaunchKernelGGL(k_mb_occupied, dim3(count), dim3(256), 0, c->stream, prm, (int)particle, (const int32_t*)d_slot, (const uint32_t*)d_pos, d_cnt, (const uint32_t*)d_off, m, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cells_xy, d_out, sizeof(uint32_t) * 2 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LAMA_HIP_OK;
 }
 
 static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,

@@ -69,6 +69,7 @@ HIP_SYMBOLS = [
     "lama_hip_blob_alloc", "lama_hip_blob_free", "lama_hip_blob_copy", "lama_hip_pf_export_particles", "lama_hip_pf_import_particles",
     "lama_hip_pgo_pattern", "lama_hip_pgo_set_poses", "lama_hip_pgo_get_poses", "lama_hip_pgo_linearize_system",
     "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
+    "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
 ]
 
 _hip = None
@@ -181,6 +182,10 @@ def _bind_hip(L):
         L.lama_hip_match_eval.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp]
         L.lama_hip_match_cell_distances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
         L.lama_hip_match_solve_with.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, i32, u32]
+        has_mb = hasattr(L, "lama_hip_map_integrate_scans")   # map rebuild from key scans (absent from the engine test double)
+        if has_mb:
+            L.lama_hip_map_integrate_scans.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32]
+            L.lama_hip_map_occupied_cells.argtypes = [vp, u32, u32, vp, vp]
         has_cks = hasattr(L, "lama_hip_pf_map_checksums")   # device-only diagnostic (absent from the engine test double)
         if has_cks:
             L.lama_hip_pf_map_checksums.argtypes = [vp, i32, vp]
@@ -203,6 +208,8 @@ def _bind_hip(L):
                 continue
             if s == "lama_hip_pf_map_checksums" and not has_cks:
                 continue
+            if s in ("lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells") and not has_mb:
+                continue
             if s not in ("lama_hip_default_cfg", "lama_hip_ctx_destroy", "lama_hip_last_error", "lama_hip_pgo_destroy",
                          "lama_hip_pgo_last_error"):
                 getattr(L, s).restype = i32
@@ -214,6 +221,41 @@ def _p(a):
 
 _IDQ = np.array([1.0, 0.0, 0.0, 0.0])
 _Z3 = np.zeros(3)
+
+
+MAP_BUILD_FULL, MAP_BUILD_PRUNE = 1, 2
+
+
+def pack_scans(scans):
+    """A list of (n_k, 3) point arrays -> (points (N, 3) float64, offsets (K + 1,) uint32); a (points, offsets) tuple is checked and
+    passed on.  Raises ValueError -- before any device is touched -- for offsets that decrease, do not start at 0 or do not end at
+    the number of points, and for point arrays that are not (n, 3)."""
+    if isinstance(scans, tuple) and len(scans) == 2 and not (hasattr(scans[1], "ndim") and np.ndim(scans[1]) == 2):
+        pts = np.ascontiguousarray(scans[0], dtype=np.float64)
+        offs = np.asarray(scans[1])
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must be (N, 3)")
+        if offs.ndim != 1 or len(offs) < 1 or np.any(offs < 0) or np.any(offs > 0xFFFFFFFF):
+            raise ValueError("offsets must be K + 1 non-negative 32-bit numbers")
+        offs = np.ascontiguousarray(offs, dtype=np.uint32)
+        if np.any(np.diff(offs.astype(np.int64)) < 0):
+            raise ValueError("scan offsets must not decrease")
+        if offs[0] != 0 or offs[-1] != len(pts):
+            raise ValueError(f"scan offsets must run from 0 to the number of points ({len(pts)}), got {offs[0]} .. {offs[-1]}")
+        return pts, offs
+    arrs = []
+    for a in scans:
+        a = np.asarray(a, dtype=np.float64)
+        if a.size == 0:
+            a = a.reshape(0, 3)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("every scan must be (n, 3)")
+        arrs.append(a)
+    offs = np.zeros(len(arrs) + 1, dtype=np.uint32)
+    if arrs:
+        offs[1:] = np.cumsum([len(a) for a in arrs])
+    pts = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 3)), dtype=np.float64)
+    return pts, offs
 
 
 def default_cfg(**kw):
@@ -376,6 +418,34 @@ class HipContext:
         cells = np.ascontiguousarray(cells_xy, dtype=np.uint32).reshape(-1, 2)
         self._chk(self.L.lama_hip_map_add_obstacles(self.h, particle, _p(cells), len(cells)))
 
+    def integrate_scans(self, particle, poses4, scans, origins=None, quats=None, full=True, prune=True):
+        """lama_hip_map_integrate_scans: `scans` is a list of (n_k, 3) point arrays -- or a tuple (points, offsets) already
+        concatenated --, poses4 (K, 4) {c, s, tx, ty}, origins (K, 3) / quats (K, 4) per scan (None: zero / identity)."""
+        pts, offs = pack_scans(scans)
+        K = len(offs) - 1
+        poses4 = np.ascontiguousarray(poses4, dtype=np.float64).reshape(-1, 4)
+        if len(poses4) != K:
+            raise ValueError(f"{len(poses4)} poses for {K} scans")
+        if origins is not None:
+            origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+            if len(origins) != K:
+                raise ValueError(f"{len(origins)} sensor origins for {K} scans")
+        if quats is not None:
+            quats = np.ascontiguousarray(quats, dtype=np.float64).reshape(-1, 4)
+            if len(quats) != K:
+                raise ValueError(f"{len(quats)} sensor orientations for {K} scans")
+        flags = (MAP_BUILD_FULL if full else 0) | (MAP_BUILD_PRUNE if prune else 0)
+        self._chk(self.L.lama_hip_map_integrate_scans(self.h, particle, K, _p(poses4), _p(pts), _p(offs), _p(origins), _p(quats), flags))
+
+    def occupied_cells(self, particle):
+        """lama_hip_map_occupied_cells: (n, 2) map coordinates of the occupied cells, in visit_all_cells order."""
+        n = C.c_uint32(0)
+        self._chk(self.L.lama_hip_map_occupied_cells(self.h, particle, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            self._chk(self.L.lama_hip_map_occupied_cells(self.h, particle, n.value, _p(out), C.byref(n)))
+        return out
+
     def match_solve(self, particle, pts, pose4, origin=None, quat=None, solve=True):
         """-> (pose, JtJ lower [00,10,11,20,21,22], sum r^2 (unweighted), iterations)"""
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -513,6 +583,10 @@ HOST_SYMBOLS = [
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
     "lama_pgo_optimize",
+    "lama_mapbuilder_default_options", "lama_mapbuilder_create", "lama_mapbuilder_destroy", "lama_mapbuilder_last_error",
+    "lama_mapbuilder_engine_origin", "lama_mapbuilder_device_context", "lama_mapbuilder_add", "lama_mapbuilder_set_pose",
+    "lama_mapbuilder_set_poses", "lama_mapbuilder_build", "lama_mapbuilder_reset", "lama_mapbuilder_occupied_cells",
+    "lama_mapbuilder_timing", "lama_mapbuilder_view_cells", "lama_mapbuilder_match_solve",
 ]
 
 
@@ -567,6 +641,14 @@ def _bind_host(L):
         "lama_sdm_export_png": (i32, [i32, d, u32, u32, vp, vp, vp, C.c_char_p]),
         "lama_dm_build": (C.c_int64, [vp, C.c_uint64, u32, vp]), "lama_dm_build_fetch": (i32, [vp, vp, vp]),
         "lama_pgo_optimize": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, u32, vp, i32]),
+        "lama_mapbuilder_default_options": (None, [vp]), "lama_mapbuilder_create": (vp, [vp, vp, i32]), "lama_mapbuilder_destroy": (None, [vp]),
+        "lama_mapbuilder_last_error": (C.c_char_p, [vp]), "lama_mapbuilder_engine_origin": (C.c_char_p, [vp]),
+        "lama_mapbuilder_device_context": (vp, [vp]), "lama_mapbuilder_add": (C.c_int64, [vp, vp, u32, vp, vp, vp]),
+        "lama_mapbuilder_set_pose": (i32, [vp, C.c_uint64, vp]), "lama_mapbuilder_set_poses": (i32, [vp, vp, C.c_uint64]),
+        "lama_mapbuilder_build": (i32, [vp]), "lama_mapbuilder_reset": (i32, [vp]),
+        "lama_mapbuilder_occupied_cells": (C.c_int64, [vp, vp, C.c_uint64]), "lama_mapbuilder_timing": (i32, [vp, vp]),
+        "lama_mapbuilder_view_cells": (C.c_int64, [vp, i32, vp, C.c_uint64]),
+        "lama_mapbuilder_match_solve": (i32, [vp, vp, u32, vp, vp, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1253,5 +1335,103 @@ class LidarOdometry2D:
         ctx.cfg = None
         ctx.P = 1
         ctx.h = C.c_void_p(self.L.lama_lo_device_context(self.h))
+        ctx._is_borrowed = True
+        return ctx
+
+
+class MapBuilderOptions(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("l2_max", C.c_double), ("patch_size", C.c_uint32), ("full", C.c_int32), ("prune", C.c_int32),
+                ("gpu_device", C.c_int32), ("window_patches", C.c_uint32), ("occ_patch_capacity", C.c_uint32), ("dm_patch_capacity", C.c_uint32)]
+
+
+class MapBuilder2D:
+    """ctypes view of the host-side lama::MapBuilder2D (include/lama/map_builder_2d.h): a map rebuilt from posed key scans."""
+
+    def __init__(self, **kw):
+        self.L = _hostlib()
+        o = MapBuilderOptions()
+        self.L.lama_mapbuilder_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        err = C.create_string_buffer(512)
+        h = self.L.lama_mapbuilder_create(C.byref(o), err, 512)
+        if not h:
+            raise LamaError(err.value.decode())
+        self.h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lama_mapbuilder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise LamaError(self.L.lama_mapbuilder_last_error(self.h).decode())
+        return rc
+
+    def engine_origin(self):
+        return self.L.lama_mapbuilder_engine_origin(self.h).decode()
+
+    def add(self, pts, pose4, origin=None, quat=None):
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        origin = np.ascontiguousarray(origin if origin is not None else _Z3, dtype=np.float64)
+        quat = np.ascontiguousarray(quat if quat is not None else _IDQ, dtype=np.float64)
+        pose4 = np.ascontiguousarray(pose4, dtype=np.float64)
+        return self._chk(self.L.lama_mapbuilder_add(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose4)))
+
+    def set_pose(self, key, pose4):
+        self._chk(self.L.lama_mapbuilder_set_pose(self.h, int(key), _p(np.ascontiguousarray(pose4, dtype=np.float64))))
+
+    def set_poses(self, poses4):
+        poses4 = np.ascontiguousarray(poses4, dtype=np.float64).reshape(-1, 4)
+        self._chk(self.L.lama_mapbuilder_set_poses(self.h, _p(poses4), len(poses4)))
+
+    def build(self):
+        self._chk(self.L.lama_mapbuilder_build(self.h))
+
+    def reset(self):
+        self._chk(self.L.lama_mapbuilder_reset(self.h))
+
+    def occupied_cells(self):
+        n = self.L.lama_mapbuilder_occupied_cells(self.h, None, 0)
+        out = np.zeros((n, 2), dtype=np.uint32)
+        self.L.lama_mapbuilder_occupied_cells(self.h, _p(out), n)
+        return out
+
+    def timing(self):
+        """wall-clock milliseconds of the last build(): integrate, occupied list, distance map"""
+        ms = np.zeros(3)
+        self.L.lama_mapbuilder_timing(self.h, _p(ms))
+        return {"integrate_ms": ms[0], "occupied_ms": ms[1], "distance_ms": ms[2]}
+
+    def view_cells(self, which):
+        """visit_all_cells of getOccupancyMap() (0) / getDistanceMap() (1), or None when there is no such map"""
+        n = self.L.lama_mapbuilder_view_cells(self.h, which, None, 0)
+        if n < 0:
+            return None
+        out = np.zeros((n, 2), dtype=np.uint32)
+        self._chk(self.L.lama_mapbuilder_view_cells(self.h, which, _p(out), n))
+        return out
+
+    def match_solve(self, pts, pose4, max_iterations=100, origin=None, quat=None):
+        """lama::Solve(GaussNewton + Cauchy(0.15)) of MatchSurface2D on getDistanceMap() -> (pose4, iterations)"""
+        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pose = np.ascontiguousarray(pose4, dtype=np.float64).copy()
+        it = C.c_uint32(0)
+        rc = self.L.lama_mapbuilder_match_solve(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), int(max_iterations), C.byref(it))
+        if rc != 0:
+            raise LamaError(self.L.lama_mapbuilder_last_error(self.h).decode() or "no distance map")
+        return pose, it.value
+
+    def hip_context(self):
+        """Borrowed HipContext view of the device context (map downloads in tests)."""
+        ctx = HipContext.__new__(HipContext)
+        ctx.L = _lib_of_origin(self.engine_origin())
+        ctx.cfg = None
+        ctx.P = 1
+        ctx.h = C.c_void_p(self.L.lama_mapbuilder_device_context(self.h))
         ctx._is_borrowed = True
         return ctx

@@ -1,6 +1,8 @@
 // dm_builder.cpp -- see dm_builder.hpp: the first build of Loc2D's distance map (addObstacle x N on an empty map, one update()).
 #include "dm_builder.hpp"
 
+#include "hip_engine.hpp"
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -142,6 +144,37 @@ bool build_distance_map(const uint32_t* cells_xy, size_t n, uint32_t max_sqdist,
             out.masks.insert(out.masks.end(), mask, mask + 16);
         }
     return true;
+}
+
+int32_t add_obstacles_to_map(const HipEngine& eng, lama_hip_ctx* ctx, const uint32_t* cells_xy, size_t n, double resolution, uint32_t patch_length,
+                             uint32_t max_sqdist, bool& host_built, uint32_t& processed, const char*& what)
+{
+    host_built = false; processed = 0;
+    {   // The FIRST build -- every occupied cell of a static map added to an empty distance map, one update(): src/loc2d.cpp:61-108
+        // with the caller's loop -- is one serial chain of pops with nothing to parallelise over; it is replayed on the host
+        // (build_distance_map: from-scratch code, std::priority_queue for the reference's tie order) and uploaded like a map read
+        // from a file.  Later updates of the map that now exists run on the device.
+        uint32_t have = 0;
+        if (eng.pf_map_patches(ctx, 0, 0 /* distance map */, &have) == 0 && have == 0) {
+            sdm::HostMap m;
+            m.kind = sdm::kDistanceMap; m.resolution = resolution; m.patch_length = patch_length;
+            m.max_sqdist = max_sqdist;
+            if (build_distance_map(cells_xy, n, m.max_sqdist, m, processed)) {
+                what = "lama_hip_pf_upload_map (first build of the distance map)";
+                const int32_t ru = eng.pf_upload_map(ctx, 0, 0, (uint32_t)m.ids.size(), m.ids.data(), m.cells.data(), m.masks.data());
+                if (ru == 0) host_built = true;
+                return ru;
+            }
+        }
+    }
+    lama_hip_counters c0, c1;
+    const bool have0 = eng.get_counters(ctx, &c0) == 0;
+    what = "lama_hip_map_add_obstacles";
+    const int32_t rc = eng.map_add_obstacles(ctx, 0, cells_xy, (uint32_t)n);
+    if (rc) return rc;
+    // DynamicDistanceMap::update returns the cells processed by THIS call (src/sdm/dynamic_distance_map.cpp:196)
+    processed = (have0 && eng.get_counters(ctx, &c1) == 0) ? (uint32_t)(c1.bf_cells - c0.bf_cells) : 0;
+    return 0;
 }
 
 }  // namespace detail

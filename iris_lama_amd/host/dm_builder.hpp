@@ -21,7 +21,10 @@
 
 #include "lama/sdm_io.h"
 
+struct lama_hip_ctx;
+
 namespace lama {
+struct HipEngine;
 namespace detail {
 
 // cells_xy: n (x, y) pairs of map coordinates in addObstacle order.  Fills `out` (kind, resolution, patch_length, max_sqdist must be
@@ -30,6 +33,13 @@ namespace detail {
 // the dense store would exceed `max_store_cells` (a map whose obstacles span more than that many cells is built on the device).
 bool build_distance_map(const uint32_t* cells_xy, size_t n, uint32_t max_sqdist, sdm::HostMap& out, uint32_t& processed,
                         uint64_t max_store_cells = 1ull << 28);
+
+// addObstacle for every listed cell + update() on particle 0's distance map of a one-particle context, by the rule above: a map
+// that is still EMPTY is built on the host and uploaded (host_built = true); a map that exists -- or a build whose dense store
+// would not fit -- goes to the device (lama_hip_map_add_obstacles).  Used by Loc2D and MapBuilder2D.  processed = update()'s return
+// value; on failure the status is returned and `what` names the call that failed.
+int32_t add_obstacles_to_map(const HipEngine& eng, lama_hip_ctx* ctx, const uint32_t* cells_xy, size_t n, double resolution, uint32_t patch_length,
+                             uint32_t max_sqdist, bool& host_built, uint32_t& processed, const char*& what);
 
 }  // namespace detail
 }  // namespace lama

@@ -95,6 +95,8 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     BIND(blob_free, lama_hip_blob_free)
     BIND(blob_copy, lama_hip_blob_copy)
 #undef BIND
+    e->map_integrate_scans = reinterpret_cast<decltype(e->map_integrate_scans)>(dlsym(dl, "lama_hip_map_integrate_scans"));
+    e->map_occupied_cells = reinterpret_cast<decltype(e->map_occupied_cells)>(dlsym(dl, "lama_hip_map_occupied_cells"));
     return e;
 }
 

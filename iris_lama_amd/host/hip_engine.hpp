@@ -49,6 +49,10 @@ struct HipEngine {
     decltype(&lama_hip_blob_alloc) blob_alloc = nullptr;
     decltype(&lama_hip_blob_free) blob_free = nullptr;
     decltype(&lama_hip_blob_copy) blob_copy = nullptr;
+    // map rebuild from key scans (lama::MapBuilder2D); optional: an implementation of the C-ABI without them leaves these null and
+    // MapBuilder2D refuses to start on it
+    decltype(&lama_hip_map_integrate_scans) map_integrate_scans = nullptr;
+    decltype(&lama_hip_map_occupied_cells) map_occupied_cells = nullptr;
     ~HipEngine();
 };
 

@@ -17,6 +17,7 @@
 #include "dm_builder.hpp"
 #include "lama/slam2d.h"
 #include "lama/simple_pgo.h"
+#include "lama/map_builder_2d.h"
 
 using namespace lama;
 
@@ -726,6 +727,98 @@ int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from
         if (err && errcap > 0) { std::strncpy(err, e.what(), (size_t)errcap - 1); err[errcap - 1] = 0; }
         return -1;
     }
+}
+
+// ---- lama::MapBuilder2D ----
+struct lama_mapbuilder {
+    std::unique_ptr<MapBuilder2D> b;
+    std::string error, origin;
+};
+
+void lama_mapbuilder_default_options(lama_mapbuilder_options* o)
+{
+    MapBuilder2D::Options d;
+    o->resolution = d.resolution; o->l2_max = d.l2_max; o->patch_size = d.patch_size; o->full = d.full ? 1 : 0; o->prune = d.prune ? 1 : 0;
+    o->gpu_device = d.gpu_device; o->window_patches = 0; o->occ_patch_capacity = 0; o->dm_patch_capacity = 0;
+}
+
+lama_mapbuilder* lama_mapbuilder_create(const lama_mapbuilder_options* o, char* err, int errcap)
+{
+    auto* h = new lama_mapbuilder;
+    try {
+        MapBuilder2D::Options p;
+        p.resolution = o->resolution; p.l2_max = o->l2_max; p.patch_size = o->patch_size; p.full = o->full != 0; p.prune = o->prune != 0;
+        p.gpu_device = o->gpu_device; p.window_patches = o->window_patches; p.occ_patch_capacity = o->occ_patch_capacity; p.dm_patch_capacity = o->dm_patch_capacity;
+        h->b.reset(new MapBuilder2D(p));
+        h->origin = h->b->engine()->origin;
+        return h;
+    } catch (const std::exception& e) {
+        if (err && errcap > 0) { std::strncpy(err, e.what(), (size_t)errcap - 1); err[errcap - 1] = 0; }
+        delete h;
+        return nullptr;
+    }
+}
+void lama_mapbuilder_destroy(lama_mapbuilder* b) { delete b; }
+const char* lama_mapbuilder_last_error(const lama_mapbuilder* b) { return b ? b->error.c_str() : "null handle"; }
+const char* lama_mapbuilder_engine_origin(const lama_mapbuilder* b) { return b ? b->origin.c_str() : ""; }
+void* lama_mapbuilder_device_context(const lama_mapbuilder* b) { return (void*)b->b->deviceContext(); }
+int64_t lama_mapbuilder_add(lama_mapbuilder* h, const double* pts, uint32_t n, const double* o, const double* q, const double* pose4)
+{
+    try {
+        return (int64_t)h->b->add(cloud_of(pts, n, o, q), Pose2D(SE2d::fromArray(pose4)));
+    } catch (const std::exception& e) { h->error = e.what(); return -1; }
+}
+int lama_mapbuilder_set_pose(lama_mapbuilder* h, uint64_t key, const double* pose4)
+{
+    try { h->b->setPose((size_t)key, Pose2D(SE2d::fromArray(pose4))); return 0; } catch (const std::exception& e) { h->error = e.what(); return -1; }
+}
+int lama_mapbuilder_set_poses(lama_mapbuilder* h, const double* poses4, uint64_t n)
+{
+    try {
+        std::vector<Pose2D> v;
+        for (uint64_t i = 0; i < n; ++i) v.push_back(Pose2D(SE2d::fromArray(poses4 + 4 * i)));
+        h->b->setPoses(v);
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -1; }
+}
+int lama_mapbuilder_build(lama_mapbuilder* h) { try { h->b->build(); return 0; } catch (const std::exception& e) { h->error = e.what(); return -1; } }
+int lama_mapbuilder_reset(lama_mapbuilder* h) { try { h->b->reset(); return 0; } catch (const std::exception& e) { h->error = e.what(); return -1; } }
+int64_t lama_mapbuilder_occupied_cells(const lama_mapbuilder* h, uint32_t* xy_out, uint64_t cap)
+{
+    const std::vector<uint32_t>& c = h->b->occupiedCells();
+    const uint64_t n = c.size() / 2;
+    if (xy_out) std::memcpy(xy_out, c.data(), sizeof(uint32_t) * 2 * (size_t)(n < cap ? n : cap));
+    return (int64_t)n;
+}
+int lama_mapbuilder_timing(const lama_mapbuilder* h, double* ms3)
+{
+    const MapBuilder2D::Timing t = h->b->lastTiming();
+    ms3[0] = t.integrate_ms; ms3[1] = t.occupied_ms; ms3[2] = t.distance_ms;
+    return 0;
+}
+int64_t lama_mapbuilder_view_cells(lama_mapbuilder* h, int which, uint32_t* xy_out, uint64_t cap)
+{
+    try {
+        return which == 0 ? view_cells(h->b->getOccupancyMap(), xy_out, cap) : view_cells(h->b->getDistanceMap(), xy_out, cap);
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+int lama_mapbuilder_match_solve(lama_mapbuilder* h, const double* pts, uint32_t n, const double* o, const double* q, double* pose4,
+                                uint32_t max_iterations, uint32_t* iterations)
+{
+    try {
+        const DynamicDistanceMap* dm = h->b->getDistanceMap();
+        if (!dm) return -1;
+        MatchSurface2D problem(dm, cloud_of(pts, n, o, q), SE2d::fromArray(pose4));
+        Solver::Options so;
+        so.max_iterations = max_iterations;
+        so.strategy.reset(new GaussNewton);
+        so.robust_cost.reset(new CauchyWeight(0.15));
+        Solver solver(so);
+        solver.solve(problem, nullptr);
+        problem.getState().toArray(pose4);
+        if (iterations) *iterations = solver.lastIterations();
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
 }
 
 } // extern "C"

@@ -34,30 +34,13 @@ void Loc2D::Init(const Options& o)
     w.apply = [this](std::vector<uint32_t>& cells_xy, double max_distance) -> uint32_t {
         (void)max_distance;                                 // part of the context's configuration (ensureContext)
         ensureContext();
-        {   // The FIRST build -- every occupied cell of a static map added to an empty distance map, one update(): src/loc2d.cpp:61-108
-            // with the caller's loop -- is one serial chain of pops with nothing to parallelise over; it is replayed on the host
-            // (dm_builder.hpp: from-scratch code, std::priority_queue for the reference's tie order) and uploaded like a map read
-            // from a file.  Later updates of the map that now exists run on the device.
-            uint32_t have = 0;
-            if (eng_->pf_map_patches(ctx_, 0, 0 /* distance map */, &have) == 0 && have == 0) {
-                sdm::HostMap m;
-                m.kind = sdm::kDistanceMap; m.resolution = distance_map->resolution; m.patch_length = distance_map->patch_length;
-                m.max_sqdist = distance_map->maxSqDist();
-                uint32_t processed = 0;
-                if (detail::build_distance_map(cells_xy.data(), cells_xy.size() / 2, m.max_sqdist, m, processed)) {
-                    const int32_t ru = eng_->pf_upload_map(ctx_, 0, 0, (uint32_t)m.ids.size(), m.ids.data(), m.cells.data(), m.masks.data());
-                    if (ru) fail(ru, "lama_hip_pf_upload_map (first build of the distance map)");
-                    host_built_ = true;
-                    return processed;
-                }
-            }
-        }
-        lama_hip_counters c0, c1;
-        const bool have0 = eng_->get_counters(ctx_, &c0) == 0;
-        const int32_t rc = eng_->map_add_obstacles(ctx_, 0, cells_xy.data(), (uint32_t)(cells_xy.size() / 2));
-        if (rc) fail(rc, "lama_hip_map_add_obstacles");
-        // DynamicDistanceMap::update returns the cells processed by THIS call (src/sdm/dynamic_distance_map.cpp:196)
-        return (have0 && eng_->get_counters(ctx_, &c1) == 0) ? (uint32_t)(c1.bf_cells - c0.bf_cells) : 0;
+        // an empty map is built on the host and uploaded, a map that exists is updated on the device (dm_builder.hpp)
+        bool host_built = false; uint32_t processed = 0; const char* what = "";
+        const int32_t rc = detail::add_obstacles_to_map(*eng_, ctx_, cells_xy.data(), cells_xy.size() / 2, distance_map->resolution, distance_map->patch_length,
+                                                        distance_map->maxSqDist(), host_built, processed, what);
+        if (rc) fail(rc, what);
+        if (host_built) host_built_ = true;
+        return processed;
     };
     w.download = [this](sdm::HostMap& m) -> bool {
         if (!ctx_) return false;
