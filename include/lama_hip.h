@@ -238,6 +238,43 @@ int32_t lama_hip_match_cell_distances(lama_hip_ctx* ctx, uint32_t particle, cons
                                       const double* sensor_origin3, const double* sensor_quat_wxyz, const double* pose,
                                       double* distances);
 
+/* num_problems independent scan-to-map registrations in ONE launch, one workgroup each (csrc/lama_match_batch.h): what
+ * lama_hip_match_solve_with does for one problem, for many, with the robust cost the caller names -- the matching stage of loop
+ * closure (GraphSlam2D::correlateCandidateScan, src/graph_slam2d.cpp:315-355: HuberWeight(0.15), 1 then 100 iterations, then
+ * error()), the refinement of many global-localisation candidates, a fleet on one map.  Problem b:
+ *   particles[b]                     whose distance map it is matched against (no map is changed);
+ *   pts_xyz, scan_offsets [B + 1]    its points scan_offsets[b] .. scan_offsets[b + 1] - 1 of the concatenated array (not empty);
+ *   sensor_origin3_per_problem [B][3] / sensor_quat_wxyz_per_problem [B][4]   its sensor mount (NULL: zero / identity);
+ *   poses_inout [B][4] {c,s,tx,ty}   start pose in, solution out;
+ *   max_iterations [B]               its iteration limit; 0 evaluates out8 at the start pose, which is returned bit for bit.
+ * Per call: strategy (0 = GaussNewton, 1 = LevenbergMarquard, default thresholds) and the weight RobustCost::value
+ * (src/nlls/robust_cost.cpp:36-82) of robust_kind with robust_param: UnitWeight (parameter ignored, must be finite), TukeyWeight(b),
+ * TDistributionWeight(dof), CauchyWeight(param), HuberWeight(k) -- the reference's formulas literally, Huber's test `x < k` included.
+ * Out: out8 [B][8] = lower triangle of J^T J (weighted J at the solution: 00,10,11,20,21,22), the sum of squared unweighted
+ * residuals, and the sum of squared CELL distances -- MatchSurface2D::error() is sqrt(out8[7] / n) --; iters_out [B];
+ * status_out [B] (may be NULL): 0, or 1 where a step met a zero-norm unit complex (the reference throws SophusException).  Such a
+ * problem makes the call return LAMA_HIP_E_NUMERIC with the problem named in lama_hip_last_error; every array is still written and
+ * the other problems' results stand.  A CauchyWeight(0.15) problem returns bit for bit what lama_hip_match_solve_with returns.
+ * LAMA_HIP_E_INVALID, found before anything is uploaded and with every array untouched: an empty slice, a particle out of range, a
+ * non-finite point, pose, mount or parameter, an unknown kind or strategy, a parameter for which the reference's formula divides by
+ * zero or weighs negatively (b == 0, param == 0, dof <= 0, k <= 0).  num_problems == 0 does nothing.  Workgroup b takes problem b:
+ * the problems start in the order given.  Whether a ragged batch gains from starting its long scans first is NOT measured (DESIGN.md
+ * section 4f); a caller who wants that order lists the problems so. */
+#define LAMA_HIP_ROBUST_UNIT 0
+#define LAMA_HIP_ROBUST_TUKEY 1
+#define LAMA_HIP_ROBUST_TDIST 2
+#define LAMA_HIP_ROBUST_CAUCHY 3
+#define LAMA_HIP_ROBUST_HUBER 4
+/* or-ed into robust_kind: robust_param is the constant as the reference's class STORES it -- TukeyWeight::bb_ = b * b, CauchyWeight::c_
+ * = 1 / (param * param); the other classes store their argument -- so that a caller who holds the object need not undo its
+ * constructor (lama::SolveBatch).  The same refusals apply to the stored constant. */
+#define LAMA_HIP_ROBUST_STORED 0x100
+int32_t lama_hip_match_solve_batch(lama_hip_ctx* ctx, uint32_t num_problems, const uint32_t* particles, const double* pts_xyz,
+                                   const uint32_t* scan_offsets, const double* sensor_origin3_per_problem,
+                                   const double* sensor_quat_wxyz_per_problem, double* poses_inout, const uint32_t* max_iterations,
+                                   int32_t strategy, int32_t robust_kind, double robust_param, double* out8, int32_t* iters_out,
+                                   uint32_t* status_out);
+
 /* Map rebuild from posed key scans (GraphSlam2D::generateOccupancyMap, src/graph_slam2d.cpp:131-164) on `particle`'s FREQUENCY
  * occupancy map, all scans in one order-free pass (csrc/lama_map_build.h).  Per scan k and point p, the reference's loop:
  * tf = T(pose_k) * T(sensor_origin_k) * R(sensor_quat_k); hit = tf * p; setOccupied(w2m(hit)); with flags bit 0 ("full") also

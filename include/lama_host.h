@@ -143,6 +143,19 @@ int lama_slam_match_eval(lama_slam* s, const double* pts_xyz, uint32_t n, const 
 int lama_slam_match_solve(lama_slam* s, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz,
                           double* pose4, const char* strategy, const char* weight, double weight_param, uint32_t max_iterations,
                           double* cov9, uint32_t* iterations);
+/* The same solve through lama::Solver's GENERIC host loop (a Problem that forwards to the MatchSurface2D: per-beam evaluation on the
+ * device, weights / normal equations / steps on the host).  weight: "unit", "tukey", "tdist", "cauchy", "huber"; any parameter. */
+int lama_slam_match_solve_generic(lama_slam* s, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz,
+                                  double* pose4, const char* strategy, const char* weight, double weight_param, uint32_t max_iterations,
+                                  double* cov9, uint32_t* iterations);
+/* lama::SolveBatch (lama/nlls/solver.h) over num_problems MatchSurface2D on this object's distance map -- the odd-numbered ones on
+ * `other`'s when that is not NULL --: points concatenated with num_problems + 1 offsets, origins [B][3] / quats [B][4] (NULL: zero /
+ * identity), poses4 [B][4] in / out, max_iterations [B] (NULL: 100 each), eps1 > 0 replaces the strategy's first threshold, cov9
+ * [B][9], iterations [B], errors [B] = MatchSurface2D::error() at the solution.  -3: SolveBatch threw std::invalid_argument. */
+int lama_slam_solve_batch(lama_slam* s, lama_slam* other, uint32_t num_problems, const double* pts_xyz, const uint32_t* offsets,
+                          const double* origins3, const double* quats_wxyz, double* poses4, const uint32_t* max_iterations,
+                          const char* strategy, double eps1, const char* weight, double weight_param, double* cov9, uint32_t* iterations,
+                          double* errors);
 const char* lama_slam_engine_origin(const lama_slam* s);
 
 /* ---- lama::Loc2D (include/lama/loc2d.h), flattened ---- */

@@ -18,6 +18,7 @@
 #include "lama_kernels.h"
 #include "lama_pgo.h"
 #include "lama_map_build.h"
+#include "lama_match_batch.h"
 #include "../host/pgo_pattern.hpp"
 
 using namespace lama_dev;
@@ -230,6 +231,10 @@ struct lama_hip_ctx {
     DevBuf<uint32_t> d_mb_table, d_mb_off, d_mb_list, d_mb_bins; DevBuf<int32_t> d_mb_slot; DevBuf<uint64_t> d_mb_meta;
     PinVec<double> h_mb_tfs; PinVec<uint32_t> h_mb_offs; PinVec<uint64_t> h_mb_meta;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
+    // lama_hip_match_solve_batch (lama_match_batch.h), grow-only: [out8 8B | poses 4B | mounts 12B | points 3N] and
+    // [iterations B | status B | problems 4B], with their page-locked staging copies
+    DevBuf<double> d_msb_f64; DevBuf<uint32_t> d_msb_u32;
+    PinVec<double> h_msb_f64; PinVec<uint32_t> h_msb_u32;
 
     double scan_reach = 0.0;          // largest point distance of the resident scan (sensor frame, metres)
     uint32_t visit_bound = 0;         // upper bound of the largest `visited` counter of any frequency cell (see k_occ_max_visited)
@@ -2326,6 +2331,121 @@ static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double
     if (rc) return rc;
     if (out7) std::memcpy(out7, o7, sizeof(o7));
     if (iters_out) *iters_out = it;
+    return LAMA_HIP_OK;
+}
+
+// ---- lama_hip_match_solve_batch: B independent (map, scan, start pose) registrations in one launch (lama_match_batch.h)
+extern "C++" {
+template <class WT>
+static void launch_match_solve_batch(lama_hip_ctx* c, const DevParams& prm, uint32_t B, const MsbProblem* d_prob,
+                                     const double* d_pts, const double* d_mtf, double* d_pose, double* d_out, int32_t* d_iters, uint32_t* d_status, WT wt)
+{
+    if (c->max_sqdist > (uint32_t)SM_LUT)
+        hipLaunchKernelGGL((k_match_solve_batch<true, WT>), dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, d_prob, d_pts, d_mtf, d_pose, d_out, d_iters, d_status, wt);
+    else
+        hipLaunchKernelGGL((k_match_solve_batch<false, WT>), dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, d_prob, d_pts, d_mtf, d_pose, d_out, d_iters, d_status, wt);
+}
+}   // extern "C++"
+
+int32_t lama_hip_match_solve_batch(lama_hip_ctx* c, uint32_t B, const uint32_t* particles, const double* pts, const uint32_t* offs,
+                                   const double* origins, const double* quats, double* poses, const uint32_t* max_iterations,
+                                   int32_t strategy, int32_t robust_kind, double robust_param, double* out8, int32_t* iters_out, uint32_t* status_out)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    if (B == 0) return LAMA_HIP_OK;
+    ENTER(c);
+    // ---- everything that can refuse the call, before anything is uploaded
+    if (!particles || !pts || !offs || !poses || !max_iterations || !out8 || !iters_out) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: a required array is NULL");
+    if (strategy != 0 && strategy != 1) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: strategy is 0 (GaussNewton) or 1 (LevenbergMarquard)");
+    if (!std::isfinite(robust_param))                     // (whichever form it comes in: the stored c_ of CauchyWeight(0) is an infinity)
+        return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: the robust cost's parameter is not finite");
+    // the constant the kernel's policy takes is the one the reference's class stores: formed here as its constructor forms it, or
+    // (LAMA_HIP_ROBUST_STORED) handed over already formed
+    const bool stored = (robust_kind & LAMA_HIP_ROBUST_STORED) != 0;
+    robust_kind &= ~LAMA_HIP_ROBUST_STORED;
+    double wparam = robust_param;
+    switch (robust_kind) {
+    case LAMA_HIP_ROBUST_UNIT: break;
+    case LAMA_HIP_ROBUST_TUKEY:      // 1 - x^2 / b^2
+        if (!stored) wparam = robust_param * robust_param;
+        if (!(wparam > 0.0) || !std::isfinite(wparam)) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: TukeyWeight(b) divides by b * b, which is zero (or overflows)");
+        break;
+    case LAMA_HIP_ROBUST_TDIST:      // (dof + 1) / (dof + x^2): zero divides at x = 0, a negative one at x^2 = -dof (and weighs negatively)
+        if (!(robust_param > 0.0)) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: TDistributionWeight(dof) needs dof > 0");
+        break;
+    case LAMA_HIP_ROBUST_CAUCHY:     // c_ = 1 / (param * param)
+        if (!stored) wparam = 1.0 / (robust_param * robust_param);
+        if (!std::isfinite(wparam) || wparam < 0.0) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: CauchyWeight(param) divides by param * param, which is zero");
+        break;
+    case LAMA_HIP_ROBUST_HUBER:      // k / |x| for x >= k: zero gives 0 / 0 at x = 0, a negative one a negative weight everywhere
+        if (!(robust_param > 0.0)) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: HuberWeight(k) needs k > 0");
+        break;
+    default: return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: unknown robust cost");
+    }
+    for (uint32_t b = 0; b < B; ++b) {
+        if (offs[b + 1] <= offs[b]) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: problem " + std::to_string(b) + " has an empty (or decreasing) point slice");
+        if (offs[b + 1] - offs[b] > 0x7FFFFFFFu) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: more than 2^31 - 1 points in one problem");
+        if (particles[b] >= c->P) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: problem " + std::to_string(b) + " names a particle out of range");
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(poses[4 * (size_t)b + k])) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: the start pose of problem " + std::to_string(b) + " is not finite");
+        for (int k = 0; origins && k < 3; ++k)
+            if (!std::isfinite(origins[3 * (size_t)b + k])) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: the sensor origin of problem " + std::to_string(b) + " is not finite");
+        for (int k = 0; quats && k < 4; ++k)
+            if (!std::isfinite(quats[4 * (size_t)b + k])) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: the sensor orientation of problem " + std::to_string(b) + " is not finite");
+    }
+    const size_t N = (size_t)offs[B] - offs[0];
+    {
+        const double* q = pts + 3 * (size_t)offs[0];
+        double acc = 0.0;                                            // (a NaN or an infinity anywhere makes the sum of products with zero a NaN)
+        for (size_t i = 0; i < 3 * N; ++i) acc += q[i] * 0.0;
+        if (!(acc == 0.0)) return fail(c, LAMA_HIP_E_INVALID, "lama_hip_match_solve_batch: a scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)");
+    }
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_solve_batch before a map exists");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // ---- staging: one array of doubles, one of words (layout at lama_hip_ctx)
+    const size_t o_out = 0, o_pose = 8 * (size_t)B, o_mtf = 12 * (size_t)B, o_pts = 24 * (size_t)B, n_f64 = o_pts + 3 * N;
+    const size_t o_it = 0, o_st = B, o_prob = 2 * (size_t)B, n_u32 = 6 * (size_t)B;
+    c->h_msb_f64.resize(n_f64); c->h_msb_u32.resize(n_u32);
+    double* const hf = c->h_msb_f64.data(); uint32_t* const hu = c->h_msb_u32.data();
+    std::memcpy(hf + o_pose, poses, sizeof(double) * 4 * B);
+    std::memcpy(hf + o_pts, pts + 3 * (size_t)offs[0], sizeof(double) * 3 * N);
+    for (uint32_t b = 0; b < B; ++b) {
+        const Affine m = moving_tf(origins ? origins + 3 * (size_t)b : nullptr, quats ? quats + 4 * (size_t)b : nullptr);
+        double* q = hf + o_mtf + 12 * (size_t)b;
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) q[3 * i + j] = m.R[i][j]; q[9 + i] = m.t[i]; }
+        const MsbProblem pb{particles[b], offs[b] - offs[0], offs[b + 1] - offs[b], max_iterations[b]};
+        std::memcpy(hu + o_prob + 4 * (size_t)b, &pb, sizeof(pb));
+    }
+    HIPCHK(c, c->d_msb_f64.grow(n_f64, (size_t)1 << 14)); HIPCHK(c, c->d_msb_u32.grow(n_u32, (size_t)1 << 10));
+    double* const df = c->d_msb_f64; uint32_t* const du = c->d_msb_u32;
+    HIPCHK(c, hipMemcpyAsync(df + o_pose, hf + o_pose, sizeof(double) * (n_f64 - o_pose), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(du + o_prob, hu + o_prob, sizeof(uint32_t) * (n_u32 - o_prob), hipMemcpyHostToDevice, c->stream));
+    DevParams prm = make_params(c);
+    prm.strategy = strategy;
+    const MsbProblem* const d_prob = reinterpret_cast<const MsbProblem*>(du + o_prob);
+    int32_t* const d_it = reinterpret_cast<int32_t*>(du + o_it);
+#define LAMA_MSB_LAUNCH(W) launch_match_solve_batch(c, prm, B, d_prob, df + o_pts, df + o_mtf, df + o_pose, df + o_out, d_it, du + o_st, W{wparam})
+    switch (robust_kind) {
+    case LAMA_HIP_ROBUST_UNIT: LAMA_MSB_LAUNCH(WUnit); break;
+    case LAMA_HIP_ROBUST_TUKEY: LAMA_MSB_LAUNCH(WTukey); break;
+    case LAMA_HIP_ROBUST_TDIST: LAMA_MSB_LAUNCH(WTDist); break;
+    case LAMA_HIP_ROBUST_CAUCHY: LAMA_MSB_LAUNCH(WCauchy); break;
+    default: LAMA_MSB_LAUNCH(WHuber); break;
+    }
+#undef LAMA_MSB_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hf + o_out, df + o_out, sizeof(double) * 12 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hu + o_it, du + o_it, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out8, hf + o_out, sizeof(double) * 8 * B);
+    std::memcpy(poses, hf + o_pose, sizeof(double) * 4 * B);
+    std::memcpy(iters_out, hu + o_it, sizeof(int32_t) * B);
+    if (status_out) std::memcpy(status_out, hu + o_st, sizeof(uint32_t) * B);
+    uint32_t bad = 0, first_bad = 0;
+    for (uint32_t b = B; b-- > 0;) if (hu[o_st + b]) { ++bad; first_bad = b; }
+    if (bad)
+        return fail(c, LAMA_HIP_E_NUMERIC, "lama_hip_match_solve_batch: " + std::to_string(bad) + " of " + std::to_string(B) + " problems met a zero-norm unit complex (the first is problem " +
+                                               std::to_string(first_bad) + "; status_out marks them); the other problems' results stand");
     return LAMA_HIP_OK;
 }
 

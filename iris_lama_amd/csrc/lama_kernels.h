@@ -180,9 +180,16 @@ __device__ inline int sm_gather(const DevParams& prm, const int16_t* __restrict_
     return nb;
 }
 
-template <bool BIGSQ>
+// The robust weight of a beam is a policy: an object whose operator()(x) is RobustCost::value (src/nlls/robust_cost.cpp:36-82).
+// The default is the weight every class of the reference uses; lama_match_batch.h has the five of the reference with their parameter.
+struct WCauchy015 {
+    __device__ inline double operator()(double x) const { return cauchy015(x); }
+};
+
+template <bool BIGSQ, class WT = WCauchy015>
 __device__ inline void eval_beams_jac(const DevParams& prm, const int16_t* dir, const sv_t* sv,
-                                      const double* __restrict__ pts, int n, const Affine& tf, double (&acc)[NJ], const double* lut)
+                                      const double* __restrict__ pts, int n, const Affine& tf, double (&acc)[NJ], const double* lut,
+                                      const WT wt = WT())
 {
 #pragma unroll
     for (int k = 0; k < NJ; ++k) acc[k] = 0.0;
@@ -200,7 +207,7 @@ __device__ inline void eval_beams_jac(const DevParams& prm, const int16_t* dir, 
         double gx, gy;
         double r = sm_corners_finish<BIGSQ>(prm, lut, bc[b], cv[b], &gx, &gy);
         acc[10] += own ? -(r * r) / prm.meas_sigma : 0.0;
-        const double w = sqrt(cauchy015(r));
+        const double w = sqrt(wt(r));
         r *= w;
         const double j0 = gx * w, j1 = gy * w, j2 = (gy * hx - gx * hy) * w;
         acc[0] += own ? j0 * j0 : 0.0; acc[1] += own ? j1 * j0 : 0.0; acc[2] += own ? j1 * j1 : 0.0;
@@ -214,9 +221,10 @@ __device__ inline void eval_beams_jac(const DevParams& prm, const int16_t* dir, 
 
 // residual-only evaluation: acc[0] = sum (w r)^2 (validation, solver.cpp:90-96),
 //                           acc[1] = sum -(d*d)/meas_sigma (calculateLikelihood, pf_slam2d.cpp:393-414)
-template <bool BIGSQ>
+template <bool BIGSQ, class WT = WCauchy015>
 __device__ inline void eval_beams_res(const DevParams& prm, const int16_t* dir, const sv_t* sv,
-                                      const double* __restrict__ pts, int n, const Affine& tf, double (&acc)[2], const double* lut)
+                                      const double* __restrict__ pts, int n, const Affine& tf, double (&acc)[2], const double* lut,
+                                      const WT wt = WT())
 {
     acc[0] = 0.0; acc[1] = 0.0;
     for (int base = 0; base < n; base += SM_NB * SM_BLOCK) {
@@ -227,7 +235,7 @@ __device__ inline void eval_beams_res(const DevParams& prm, const int16_t* dir, 
         for (int b = 0; b < SM_NB; ++b) {
             const bool own = b < nb;               // see eval_beams_jac
             const double d = sm_corners_finish<BIGSQ>(prm, lut, bc[b], cv[b], nullptr, nullptr);
-            const double wr = d * sqrt(cauchy015(d));
+            const double wr = d * sqrt(wt(d));
             acc[0] += own ? wr * wr : 0.0;
             acc[1] += own ? -(d * d) / prm.meas_sigma : 0.0;
         }
@@ -264,9 +272,11 @@ struct SMShared {
 #else
 #define SMT(k) do {} while (0)
 #endif
-template <bool BIGSQ>
+// `wt` is the robust weight (above).  `numeric` is where a zero-norm unit complex in the step is reported: NULL = the context's error
+// word (the whole call fails), else a word of the calling workgroup (k_match_solve_batch: the problem fails, its neighbours stand).
+template <bool BIGSQ, class WT = WCauchy015>
 __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, const sv_t* sv, const double* __restrict__ pts, int n,
-                                    const Affine& mtf, SMShared& sh, uint32_t& evals)
+                                    const Affine& mtf, SMShared& sh, uint32_t& evals, const WT wt = WT(), int* numeric = nullptr)
 {
 #ifdef LAMA_PROFILE_SM
     uint64_t smp[4] = {0, 0, 0, 0};
@@ -286,7 +296,7 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
             double acc[NJ];
             {
                 const Affine tf = sh.tf;
-                eval_beams_jac<BIGSQ>(prm, dir, sv, pts, n, tf, acc, sh.lut);
+                eval_beams_jac<BIGSQ>(prm, dir, sv, pts, n, tf, acc, sh.lut, wt);
             }
             SMT(0);
             block_sum<NJ>(acc, sh.red, sh.tot);
@@ -323,7 +333,7 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
                 if (!stop) {
                     bool ok = true;
                     sh.state = se2_exp_mul(h, sh.state, ok);    // problem.update(h)
-                    if (!ok) atomicOr(prm.err, ERR_NUMERIC);
+                    if (!ok) { if (numeric) *numeric = 1; else atomicOr(prm.err, ERR_NUMERIC); }
                     sh.tf = scan_tf(sh.state, mtf);
                     sh.lin_is_final = 0;
                 }
@@ -337,7 +347,7 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
         double acc2[NJ];
         {
             const Affine tf = sh.tf;
-            eval_beams_jac<BIGSQ>(prm, dir, sv, pts, n, tf, acc2, sh.lut);
+            eval_beams_jac<BIGSQ>(prm, dir, sv, pts, n, tf, acc2, sh.lut, wt);
         }
         SMT(0);
         block_sum<NJ>(acc2, sh.red, sh.tot2);
@@ -367,7 +377,7 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
                 const double mh[3] = {-sh.h[0], -sh.h[1], -sh.h[2]};
                 bool ok = true;
                 sh.state = se2_exp_mul(mh, sh.state, ok);   // NOT bitwise the state of sh.tot: lin_is_final stays 0
-                if (!ok) atomicOr(prm.err, ERR_NUMERIC);
+                if (!ok) { if (numeric) *numeric = 1; else atomicOr(prm.err, ERR_NUMERIC); }
                 sh.tf = scan_tf(sh.state, mtf);
                 sh.have_lin = 0;
             } else {

@@ -70,6 +70,7 @@ HIP_SYMBOLS = [
     "lama_hip_pgo_pattern", "lama_hip_pgo_set_poses", "lama_hip_pgo_get_poses", "lama_hip_pgo_linearize_system",
     "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
     "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
+    "lama_hip_match_solve_batch",
 ]
 
 _hip = None
@@ -186,6 +187,9 @@ def _bind_hip(L):
         if has_mb:
             L.lama_hip_map_integrate_scans.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32]
             L.lama_hip_map_occupied_cells.argtypes = [vp, u32, u32, vp, vp]
+        has_msb = hasattr(L, "lama_hip_match_solve_batch")   # batched registration (absent from the engine test double)
+        if has_msb:
+            L.lama_hip_match_solve_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
         has_cks = hasattr(L, "lama_hip_pf_map_checksums")   # device-only diagnostic (absent from the engine test double)
         if has_cks:
             L.lama_hip_pf_map_checksums.argtypes = [vp, i32, vp]
@@ -210,6 +214,8 @@ def _bind_hip(L):
                 continue
             if s in ("lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells") and not has_mb:
                 continue
+            if s == "lama_hip_match_solve_batch" and not has_msb:
+                continue
             if s not in ("lama_hip_default_cfg", "lama_hip_ctx_destroy", "lama_hip_last_error", "lama_hip_pgo_destroy",
                          "lama_hip_pgo_last_error"):
                 getattr(L, s).restype = i32
@@ -224,6 +230,9 @@ _Z3 = np.zeros(3)
 
 
 MAP_BUILD_FULL, MAP_BUILD_PRUNE = 1, 2
+ROBUST_KINDS = {"unit": 0, "tukey": 1, "tdist": 2, "cauchy": 3, "huber": 4}      # LAMA_HIP_ROBUST_*
+ROBUST_STORED = 0x100     # LAMA_HIP_ROBUST_STORED: robust_param is the constant as the class stores it (b * b, 1 / param^2)
+E_NUMERIC = -6
 
 
 def pack_scans(scans):
@@ -456,6 +465,47 @@ class HipContext:
                                               C.byref(it), 1 if solve else 0))
         return pose, out[:6].copy(), float(out[6]), it.value
 
+    def match_solve_with(self, particle, pts, pose4, strategy=0, max_iterations=0, origin=None, quat=None):
+        """lama_hip_match_solve_with -> (pose, out7, iterations): strategy 0 = GaussNewton, 1 = LevenbergMarquard; Cauchy(0.15)"""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        pose = np.array(pose4, dtype=np.float64)
+        out = np.zeros(7)
+        it = C.c_int32(0)
+        self._chk(self.L.lama_hip_match_solve_with(self.h, particle, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), _p(out),
+                                                   C.byref(it), int(strategy), int(max_iterations)))
+        return pose, out, it.value
+
+    def match_solve_batch(self, particles, scans, poses4, max_iterations=100, strategy=0, robust="cauchy", robust_param=0.15,
+                          origins=None, quats=None, check=True):
+        """lama_hip_match_solve_batch: B registrations in one launch.  `scans` is a list of (n_b, 3) point arrays or a
+        (points, offsets) tuple (pack_scans); particles (B,) or one number; poses4 (B, 4) {c, s, tx, ty}; max_iterations (B,) or one
+        number (0: evaluate only); robust a name of ROBUST_KINDS or a LAMA_HIP_ROBUST_* number; origins (B, 3) / quats (B, 4) or
+        None.  -> (poses (B, 4), out8 (B, 8), iterations (B,), status (B,)).  With check=False a LAMA_HIP_E_NUMERIC return (some
+        problem met a zero-norm unit complex; status marks it) does not raise."""
+        pts, offs = pack_scans(scans)
+        B = len(offs) - 1
+        poses = np.array(poses4, dtype=np.float64).reshape(-1, 4)
+        if len(poses) != B:
+            raise ValueError(f"{len(poses)} poses for {B} problems")
+        pa = np.ascontiguousarray(np.broadcast_to(np.asarray(particles, dtype=np.uint32), (B,)))
+        mi = np.ascontiguousarray(np.broadcast_to(np.asarray(max_iterations, dtype=np.uint32), (B,)))
+        if origins is not None:
+            origins = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+            if len(origins) != B:
+                raise ValueError(f"{len(origins)} sensor origins for {B} problems")
+        if quats is not None:
+            quats = np.ascontiguousarray(quats, dtype=np.float64).reshape(-1, 4)
+            if len(quats) != B:
+                raise ValueError(f"{len(quats)} sensor orientations for {B} problems")
+        kind = ROBUST_KINDS[robust] if isinstance(robust, str) else int(robust)
+        out8, it, st = np.zeros((B, 8)), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.uint32)
+        args = (self.h, B, _p(pa), _p(pts), _p(offs), _p(origins), _p(quats), _p(poses), _p(mi), int(strategy), kind, float(robust_param),
+                _p(out8), _p(it), _p(st))
+        rc = self.L.lama_hip_match_solve_batch(*args)
+        if rc != 0 and (check or rc != E_NUMERIC):
+            self._chk(rc)
+        return poses, out8, it, st
+
     def match_eval(self, particle, pts, pose4, origin=None, quat=None, jac=True):
         """-> (residuals[n], Jacobian n x 3 or None): MatchSurface2D::eval on the particle's distance map, no robust weight"""
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -572,7 +622,7 @@ HOST_SYMBOLS = [
     "lama_slam_get_pose", "lama_slam_update", "lama_slam_enough_motion", "lama_slam_processed_cells",
     "lama_slam_iterations", "lama_slam_device_context", "lama_slam_engine_origin", "lama_slam_deleted_patches", "lama_loc_create3",
     "lama_slam_view_bounds", "lama_slam_view_cells", "lama_slam_view_occupancy", "lama_slam_view_distance_cells", "lama_slam_view_distance_points",
-    "lama_slam_match_eval", "lama_slam_match_solve",
+    "lama_slam_match_eval", "lama_slam_match_solve", "lama_slam_match_solve_generic", "lama_slam_solve_batch",
     "lama_loc_create", "lama_loc_destroy", "lama_loc_last_error", "lama_loc_engine_origin", "lama_loc_set_obstacles_world",
     "lama_loc_write_distance_map", "lama_loc_read_distance_map", "lama_loc_device_context",
     "lama_loc_set_pose", "lama_loc_get_pose", "lama_loc_update", "lama_loc_covar", "lama_loc_rmse", "lama_loc_iterations",
@@ -620,6 +670,8 @@ def _bind_host(L):
         "lama_slam_view_distance_cells": (i32, [vp, C.c_uint64, vp, vp]), "lama_slam_view_distance_points": (i32, [vp, C.c_uint64, vp, vp]),
         "lama_slam_match_eval": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, vp]),
         "lama_slam_match_solve": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, d, u32, vp, vp]),
+        "lama_slam_match_solve_generic": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, d, u32, vp, vp]),
+        "lama_slam_solve_batch": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_char_p, d, C.c_char_p, d, vp, vp, vp]),
         "lama_loc_create": (vp, [d, d, d, d, u32, i32, vp, i32]), "lama_loc_destroy": (None, [vp]),
         "lama_loc_last_error": (C.c_char_p, [vp]), "lama_loc_engine_origin": (C.c_char_p, [vp]),
         "lama_loc_set_obstacles_world": (i32, [vp, vp, u32]), "lama_loc_write_distance_map": (i32, [vp, C.c_char_p]), "lama_loc_read_distance_map": (i32, [vp, C.c_char_p]), "lama_loc_device_context": (vp, [vp]), "lama_loc_set_pose": (None, [vp, d, d, d]),
@@ -972,6 +1024,35 @@ class Slam2D:
         if rc < 0:
             raise LamaError(self.L.lama_slam_last_error(self.h).decode())
         return pose, cov.reshape(3, 3), it.value
+
+    def match_solve_generic(self, pts, pose4, strategy="gn", weight="cauchy", weight_param=0.15, max_iterations=100, origin=None, quat=None):
+        """The same problem through lama::Solver's generic host loop (per-beam evaluation on the device, everything else on the
+        host): any of "unit", "tukey", "tdist", "cauchy", "huber" -> (pose, covariance, iterations)"""
+        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pose = np.array(pose4, dtype=np.float64)
+        cov, it = np.zeros(9), C.c_uint32(0)
+        rc = self.L.lama_slam_match_solve_generic(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), strategy.encode(), weight.encode(),
+                                                  float(weight_param), int(max_iterations), _p(cov), C.byref(it))
+        if rc < 0:
+            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+        return pose, cov.reshape(3, 3), it.value
+
+    def solve_batch(self, scans, poses4, strategy="gn", weight="huber", weight_param=0.15, max_iterations=None, origins=None, quats=None,
+                    other=None, eps1=0.0):
+        """lama::SolveBatch over MatchSurface2D problems on getDistanceMap() (odd problems on `other`'s map when given)
+        -> (poses (B, 4), covariances (B, 3, 3), iterations (B,), errors (B,))"""
+        pts, offs = pack_scans(scans)
+        B = len(offs) - 1
+        poses = np.array(poses4, dtype=np.float64).reshape(B, 4)
+        mi = None if max_iterations is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_iterations, dtype=np.uint32), (B,)))
+        origins = None if origins is None else np.ascontiguousarray(origins, dtype=np.float64).reshape(B, 3)
+        quats = None if quats is None else np.ascontiguousarray(quats, dtype=np.float64).reshape(B, 4)
+        cov, it, err = np.zeros((B, 9)), np.zeros(B, dtype=np.uint32), np.zeros(B)
+        rc = self.L.lama_slam_solve_batch(self.h, other.h if other is not None else None, B, _p(pts), _p(offs), _p(origins), _p(quats), _p(poses),
+                                          _p(mi), strategy.encode(), float(eps1), weight.encode(), float(weight_param), _p(cov), _p(it), _p(err))
+        if rc < 0:
+            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+        return poses, cov.reshape(B, 3, 3), it, err
 
     def hip_context(self):
         ctx = HipContext.__new__(HipContext)

@@ -97,6 +97,7 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
 #undef BIND
     e->map_integrate_scans = reinterpret_cast<decltype(e->map_integrate_scans)>(dlsym(dl, "lama_hip_map_integrate_scans"));
     e->map_occupied_cells = reinterpret_cast<decltype(e->map_occupied_cells)>(dlsym(dl, "lama_hip_map_occupied_cells"));
+    e->match_solve_batch = reinterpret_cast<decltype(e->match_solve_batch)>(dlsym(dl, "lama_hip_match_solve_batch"));
     return e;
 }
 

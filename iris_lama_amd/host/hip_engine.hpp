@@ -53,6 +53,8 @@ struct HipEngine {
     // MapBuilder2D refuses to start on it
     decltype(&lama_hip_map_integrate_scans) map_integrate_scans = nullptr;
     decltype(&lama_hip_map_occupied_cells) map_occupied_cells = nullptr;
+    // batched registration (lama::SolveBatch); optional in the same way: SolveBatch refuses to run on a library without it
+    decltype(&lama_hip_match_solve_batch) match_solve_batch = nullptr;
     ~HipEngine();
 };
 

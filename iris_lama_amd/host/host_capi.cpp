@@ -7,6 +7,7 @@
 #include <exception>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "hip_engine.hpp"
 #include "lama/pf_slam2d.h"
@@ -445,6 +446,87 @@ int lama_slam_match_solve(lama_slam* h, const double* pts, uint32_t n, const dou
         problem.getState().toArray(pose4);
         if (cov9) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) cov9[3 * r + c] = cov(r, c);
         if (iterations) *iterations = solver.lastIterations();
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+
+namespace {
+bool solver_options_of(const char* strategy, const char* weight, double weight_param, double eps1, uint32_t max_iterations, Solver::Options* so)
+{
+    so->max_iterations = max_iterations;
+    const std::string st(strategy ? strategy : "gn"), w(weight ? weight : "cauchy");
+    if (st == "lm") { LevenbergMarquard::Options o; if (eps1 > 0) o.eps1 = eps1; so->strategy.reset(new LevenbergMarquard(o)); }
+    else if (st == "gn") { GaussNewton::Options o; if (eps1 > 0) o.eps1 = eps1; so->strategy.reset(new GaussNewton(o)); }
+    else return false;
+    if (w == "cauchy") so->robust_cost.reset(new CauchyWeight(weight_param));
+    else if (w == "tukey") so->robust_cost.reset(new TukeyWeight(weight_param));
+    else if (w == "huber") so->robust_cost.reset(new HuberWeight(weight_param));
+    else if (w == "tdist") so->robust_cost.reset(new TDistributionWeight(weight_param));
+    else if (w == "unit") so->robust_cost.reset(new UnitWeight);
+    else return false;
+    return true;
+}
+
+// a Problem that forwards to a MatchSurface2D without being one: Solver::solve then runs its generic host loop around the device's
+// per-beam evaluation (lama_hip_match_eval) instead of the fused kernel
+struct ForwardingProblem : public Problem {
+    explicit ForwardingProblem(MatchSurface2D* m) : m_(m) {}
+    void eval(VectorXd& residuals, MatrixXd* J) override { m_->eval(residuals, J); }
+    void update(const VectorXd& h) override { m_->update(h); }
+    MatchSurface2D* m_;
+};
+}
+
+int lama_slam_match_solve_generic(lama_slam* h, const double* pts, uint32_t n, const double* o, const double* q, double* pose4, const char* strategy,
+                                  const char* weight, double weight_param, uint32_t max_iterations, double* cov9, uint32_t* iterations)
+{
+    try {
+        const DynamicDistanceMap* dm = h->s->getDistanceMap();
+        if (!dm) return -1;
+        MatchSurface2D problem(dm, cloud_of(pts, n, o, q), SE2d::fromArray(pose4));
+        ForwardingProblem fwd(&problem);
+        Solver::Options so;
+        if (!solver_options_of(strategy, weight, weight_param, 0.0, max_iterations, &so)) { h->error = "unknown strategy or weight"; return -3; }
+        Solver solver(so);
+        MatrixXd cov;
+        solver.solve(fwd, cov9 ? &cov : nullptr);
+        problem.getState().toArray(pose4);
+        if (cov9) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) cov9[3 * r + c] = cov(r, c);
+        if (iterations) *iterations = solver.lastIterations();
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+
+int lama_slam_solve_batch(lama_slam* h, lama_slam* other, uint32_t num_problems, const double* pts, const uint32_t* offs, const double* origins,
+                          const double* quats, double* poses4, const uint32_t* max_iterations, const char* strategy, double eps1, const char* weight,
+                          double weight_param, double* cov9, uint32_t* iterations, double* errors)
+{
+    try {
+        const DynamicDistanceMap* dm = h->s->getDistanceMap();
+        const DynamicDistanceMap* dm2 = other ? other->s->getDistanceMap() : dm;
+        if (!dm || !dm2) return -1;
+        std::vector<std::unique_ptr<MatchSurface2D>> owned;
+        std::vector<MatchSurface2D*> problems;
+        for (uint32_t b = 0; b < num_problems; ++b) {
+            owned.emplace_back(new MatchSurface2D((b & 1u) ? dm2 : dm, cloud_of(pts + 3 * (size_t)offs[b], offs[b + 1] - offs[b], origins ? origins + 3 * (size_t)b : nullptr,
+                                                                                quats ? quats + 4 * (size_t)b : nullptr), SE2d::fromArray(poses4 + 4 * (size_t)b)));
+            problems.push_back(owned.back().get());
+        }
+        Solver::Options so;
+        if (!solver_options_of(strategy, weight, weight_param, eps1, 100, &so)) { h->error = "unknown strategy or weight"; return -3; }
+        std::vector<MatrixXd> covs;
+        std::vector<uint32_t> its;
+        std::vector<double> errs;
+        try {
+            if (max_iterations) SolveBatch(so, problems, std::vector<uint32_t>(max_iterations, max_iterations + num_problems), &covs, &its, &errs);
+            else SolveBatch(so, problems, &covs, &its, &errs);
+        } catch (const std::invalid_argument& e) { h->error = e.what(); return -3; }
+        for (uint32_t b = 0; b < num_problems; ++b) {
+            problems[b]->getState().toArray(poses4 + 4 * (size_t)b);
+            if (cov9) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) cov9[9 * (size_t)b + 3 * r + c] = covs[b](r, c);
+            if (iterations) iterations[b] = its[b];
+            if (errors) errors[b] = errs[b];
+        }
         return 0;
     } catch (const std::exception& e) { h->error = e.what(); return -2; }
 }

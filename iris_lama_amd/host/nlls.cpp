@@ -338,4 +338,113 @@ void Solve(const Solver::Options& options, Problem& problem, MatrixXd* cov)
     solver.solve(problem, cov);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// SolveBatch: many MatchSurface2D problems, one launch (lama_hip_match_solve_batch)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// strategy at its default thresholds -> 0 / 1, else -1 (gn_solve hard-codes 1e-4, csrc/lama_kernels.h)
+int batch_strategy(const Solver::Options& o)
+{
+    if (const GaussNewton* gn = dynamic_cast<const GaussNewton*>(o.strategy.get()))
+        return (gn->options().eps1 == 1e-4 && gn->options().eps2 == 1e-4) ? 0 : -1;
+    if (const LevenbergMarquard* lm = dynamic_cast<const LevenbergMarquard*>(o.strategy.get()))
+        return (lm->options().eps1 == 1e-4 && lm->options().eps2 == 1e-4 && lm->options().tau == 1e-4) ? 1 : -1;
+    return -1;
+}
+
+// the weight as (LAMA_HIP_ROBUST_* | LAMA_HIP_ROBUST_STORED, the constant the class stores): the kernel's policy takes exactly that
+// constant, so nothing is squared or inverted a second time.  false: none of the five classes.
+bool batch_robust(const RobustCost* rc, int32_t* kind, double* param)
+{
+    if (dynamic_cast<const UnitWeight*>(rc)) { *kind = LAMA_HIP_ROBUST_UNIT; *param = 0.0; }
+    else if (const TukeyWeight* w = dynamic_cast<const TukeyWeight*>(rc)) {
+        *kind = LAMA_HIP_ROBUST_TUKEY; *param = w->bb_;
+        if (!(w->bb_ > 0.0) || !std::isfinite(w->bb_)) throw std::invalid_argument("lama::SolveBatch: TukeyWeight(b) needs a finite b * b > 0 (value() divides by it)");
+    } else if (const TDistributionWeight* w = dynamic_cast<const TDistributionWeight*>(rc)) {
+        *kind = LAMA_HIP_ROBUST_TDIST; *param = w->dof_;
+        if (!(w->dof_ > 0.0) || !std::isfinite(w->dof_)) throw std::invalid_argument("lama::SolveBatch: TDistributionWeight(dof) needs a finite dof > 0");
+    } else if (const CauchyWeight* w = dynamic_cast<const CauchyWeight*>(rc)) {
+        *kind = LAMA_HIP_ROBUST_CAUCHY; *param = w->c_;
+        if (!(w->c_ >= 0.0) || !std::isfinite(w->c_)) throw std::invalid_argument("lama::SolveBatch: CauchyWeight(param) needs param != 0 (c_ = 1 / (param * param) is not finite)");
+    } else if (const HuberWeight* w = dynamic_cast<const HuberWeight*>(rc)) {
+        *kind = LAMA_HIP_ROBUST_HUBER; *param = w->k_;
+        if (!(w->k_ > 0.0) || !std::isfinite(w->k_)) throw std::invalid_argument("lama::SolveBatch: HuberWeight(k) needs a finite k > 0");
+    } else return false;
+    *kind |= LAMA_HIP_ROBUST_STORED;
+    return true;
+}
+
+} // namespace
+
+void SolveBatch(const Solver::Options& options, const std::vector<MatchSurface2D*>& problems, const std::vector<uint32_t>& max_iterations,
+                std::vector<MatrixXd>* covs, std::vector<uint32_t>* iterations, std::vector<double>* errors)
+{
+    if (!options.strategy || !options.robust_cost) throw std::invalid_argument("lama::SolveBatch: strategy and robust_cost must be set");
+    if (max_iterations.size() != problems.size()) throw std::invalid_argument("lama::SolveBatch: one iteration limit per problem");
+    const int strategy = batch_strategy(options);
+    if (strategy < 0)
+        throw std::invalid_argument("lama::SolveBatch: the device loop runs GaussNewton or LevenbergMarquard at their default thresholds "
+                                    "(eps1 = eps2 = tau = 1e-4); this strategy has no device kernel and there is no CPU path to fall back to");
+    int32_t kind = 0;
+    double param = 0.0;
+    if (!batch_robust(options.robust_cost.get(), &kind, &param))
+        throw std::invalid_argument("lama::SolveBatch: the robust cost is none of UnitWeight, TukeyWeight, TDistributionWeight, CauchyWeight, "
+                                    "HuberWeight; there is no device kernel for it");
+    const size_t B = problems.size();
+    if (covs) covs->resize(B);
+    if (iterations) iterations->assign(B, 0u);
+    if (errors) errors->assign(B, 0.0);
+    if (B == 0) return;
+    const DynamicDistanceMap::DeviceBinding* dev = nullptr;
+    std::vector<uint32_t> particles(B), offs(B + 1, 0u);
+    std::vector<double> pts, origins(3 * B), quats(4 * B), poses(4 * B), out8(8 * B);
+    std::vector<int32_t> iters(B, 0);
+    for (size_t b = 0; b < B; ++b) {
+        MatchSurface2D* ms = problems[b];
+        if (!ms || !ms->surface_ || !ms->scan_) throw std::invalid_argument("lama::SolveBatch: null problem");
+        const auto& d = device_of(*ms);
+        if (!dev) dev = &d;
+        else if (d.engine != dev->engine || d.ctx != dev->ctx)
+            throw std::invalid_argument("lama::SolveBatch: the problems' distance maps live on different device contexts; one call solves "
+                                        "problems of ONE context (maps of different particles of it are fine)");
+        particles[b] = d.particle;
+        const ScanArrays s(*ms->scan_);
+        pts.insert(pts.end(), s.pts.begin(), s.pts.end());
+        offs[b + 1] = (uint32_t)(pts.size() / 3);
+        for (int k = 0; k < 3; ++k) origins[3 * b + k] = s.o[k];
+        for (int k = 0; k < 4; ++k) quats[4 * b + k] = s.q[k];
+        ms->state_.toArray(&poses[4 * b]);
+    }
+    if (!dev->engine->match_solve_batch)
+        throw std::runtime_error("lama::SolveBatch: the device library " + dev->engine->origin + " has no lama_hip_match_solve_batch (it is older than "
+                                 "this host library); rebuild it");
+    std::vector<uint32_t> status(B, 0u);
+    const int32_t rc = dev->engine->match_solve_batch(dev->ctx, (uint32_t)B, particles.data(), pts.data(), offs.data(), origins.data(), quats.data(),
+                                                      poses.data(), max_iterations.data(), strategy, kind, param, out8.data(), iters.data(), status.data());
+    if (rc == LAMA_HIP_E_INVALID) {
+        const char* msg = dev->engine->last_error ? dev->engine->last_error(dev->ctx) : "";
+        throw std::invalid_argument(std::string("lama::SolveBatch: ") + (msg ? msg : ""));
+    }
+    if (rc && rc != LAMA_HIP_E_NUMERIC) device_fail(*dev, rc, "lama_hip_match_solve_batch");
+    for (size_t b = 0; b < B; ++b) {
+        problems[b]->state_ = SE2d::fromArray(&poses[4 * b]);
+        if (iterations) (*iterations)[b] = (uint32_t)iters[b];
+        if (errors) (*errors)[b] = std::sqrt(out8[8 * b + 7] / (double)(offs[b + 1] - offs[b]));
+        if (covs) {
+            double c9[9];
+            detail::covariance_from_normal3(&out8[8 * b], c9);
+            (*covs)[b].resize(3, 3);
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) (*covs)[b](r, c) = c9[3 * r + c];
+        }
+    }
+    if (rc) device_fail(*dev, rc, "lama_hip_match_solve_batch");
+}
+
+void SolveBatch(const Solver::Options& options, const std::vector<MatchSurface2D*>& problems, std::vector<MatrixXd>* covs,
+                std::vector<uint32_t>* iterations, std::vector<double>* errors)
+{
+    SolveBatch(options, problems, std::vector<uint32_t>(problems.size(), options.max_iterations), covs, iterations, errors);
+}
+
 } // namespace lama
