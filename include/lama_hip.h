@@ -215,7 +215,8 @@ int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* ctx, uint32_t particle, con
  *      lama_hip_pf_init it also places the map window (centred on the first cell).
  *  lama_hip_match_solve: Solve(GaussNewton + Cauchy(0.15), MatchSurface2D(dm, scan, pose), &cov): pose_inout {c,s,tx,ty};
  *      out7 = lower triangle of J^T J (weighted J at the solution: 00,10,11,20,21,22) and the sum of squared unweighted
- *      residuals; iters_out = solver iterations.  do_solve == 0 only evaluates at the given pose. */
+ *      residuals; iters_out = solver iterations.  do_solve == 0 only evaluates at the given pose.  (One problem of
+ *      lama_hip_match_solve_batch's kernel, below, with the weight compiled in.) */
 int32_t lama_hip_map_add_obstacles(lama_hip_ctx* ctx, uint32_t particle, const uint32_t* cells_xy, uint32_t n);
 int32_t lama_hip_match_solve(lama_hip_ctx* ctx, uint32_t particle, const double* pts_xyz, uint32_t n,
                              const double* sensor_origin3, const double* sensor_quat_wxyz, double* pose_inout,

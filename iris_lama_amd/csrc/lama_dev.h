@@ -461,6 +461,22 @@ __device__ inline Affine scan_tf(const SE2& st, const Affine& m)
     return r;
 }
 
+// a pose {c, s, tx, ty} that the host uploaded (or another kernel wrote) for this launch: coherent loads, never the scalar cache
+__device__ __forceinline__ SE2 load_pose(const double* q) { return SE2{cload_f64(q), cload_f64(q + 1), cload_f64(q + 2), cload_f64(q + 3)}; }
+__device__ __forceinline__ Affine load_scan_tf(const double* q, const Affine& m) { return scan_tf(load_pose(q), m); }
+
+// x, y of tf * (px, py, pz) with translation (tx, ty) -- a beam's hit point (MatchSurface2D::eval, src/match_surface_2d.cpp:42-90).  Exactness against the
+// reference rests on this association and operation order: every kernel of the matching family takes its hit from here.
+__device__ __forceinline__ void hit_xy(const Affine& tf, double tx, double ty, double px, double py, double pz, double& hx, double& hy)
+{
+    hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tx;
+    hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + ty;
+}
+__device__ __forceinline__ void hit_xy(const Affine& tf, double px, double py, double pz, double& hx, double& hy)
+{
+    hit_xy(tf, tf.t[0], tf.t[1], px, py, pz, hx, hy);
+}
+
 // Eigen 3.3 LDLT<Matrix3d, Lower> with pivoting + solve (src/nlls/gauss_newton.cpp:66).
 // A: lower triangle used, indices [row][col].
 __device__ inline void ldlt3_solve(const double A[3][3], const double b[3], double x[3])

@@ -1767,34 +1767,10 @@ int32_t lama_hip_pf_upload_map(lama_hip_ctx* c, uint32_t particle, int32_t kind,
     return LAMA_HIP_OK;
 }
 
-int32_t lama_hip_match_batch(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3,
-                             const double* quat, const double* poses, uint32_t B, double* out)
+// k_eval_batch for B poses; `timed`: the launch counts into ms_eval_batch / launches_eval_batch
+static int32_t eval_batch_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                               const double* poses, uint32_t B, double* sqnorm_out, double* loglik_out, bool timed)
 {
-    if (!c || !pts || !poses || !out || n == 0 || B == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
-    ENTER(c);
-    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_batch before lama_hip_pf_init");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int32_t rc = upload_scan(c, pts, n);
-    if (rc) return rc;
-    rc = ensure_batch(c, B);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_bposes, poses, sizeof(double) * 4 * B, hipMemcpyHostToDevice, c->stream));
-    const Affine mtf = moving_tf(origin3, quat);
-    DevParams prm = make_params(c);
-    if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_loglik_batch<true>, dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes, c->d_bout);
-    else hipLaunchKernelGGL(k_loglik_batch<false>, dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes, c->d_bout);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->d_bout, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LAMA_HIP_OK;
-}
-
-int32_t lama_hip_eval_batch(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3,
-                            const double* quat, const double* poses, uint32_t B, double* sqnorm_out, double* loglik_out)
-{
-    if (!c || !poses || (!sqnorm_out && !loglik_out) || n == 0 || B == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
-    ENTER(c);
-    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_eval_batch before the map exists");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int32_t rc = upload_scan(c, pts, n);
     if (rc) return rc;
@@ -1803,18 +1779,38 @@ int32_t lama_hip_eval_batch(lama_hip_ctx* c, uint32_t particle, const double* pt
     HIPCHK(c, hipMemcpyAsync(c->d_bposes, poses, sizeof(double) * 4 * B, hipMemcpyHostToDevice, c->stream));
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
-    {
+    double* const d_sq = sqnorm_out ? (double*)c->d_bout : nullptr;
+    double* const d_ll = loglik_out ? c->d_bout + B : nullptr;
+    const auto launch = [&] { hipLaunchKernelGGL(k_eval_batch, dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes, d_sq, d_ll); };
+    if (timed) {
         Timer t(c, &c->ctr.ms_eval_batch, &c->ctr.launches_eval_batch);
-        hipLaunchKernelGGL(k_eval_batch, dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes,
-                           c->d_bout, c->d_bout + B);
+        launch();
         t.stop();
-    }
+    } else launch();
     HIPCHK(c, hipGetLastError());
-    if (sqnorm_out) HIPCHK(c, hipMemcpyAsync(sqnorm_out, c->d_bout, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
-    if (loglik_out) HIPCHK(c, hipMemcpyAsync(loglik_out, c->d_bout + B, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    if (sqnorm_out) HIPCHK(c, hipMemcpyAsync(sqnorm_out, d_sq, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
+    if (loglik_out) HIPCHK(c, hipMemcpyAsync(loglik_out, d_ll, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_timers(c);
     return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_match_batch(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3,
+                             const double* quat, const double* poses, uint32_t B, double* out)
+{
+    if (!c || !pts || !poses || !out || n == 0 || B == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_batch before lama_hip_pf_init");
+    return eval_batch_impl(c, particle, pts, n, origin3, quat, poses, B, nullptr, out, false);
+}
+
+int32_t lama_hip_eval_batch(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3,
+                            const double* quat, const double* poses, uint32_t B, double* sqnorm_out, double* loglik_out)
+{
+    if (!c || !poses || (!sqnorm_out && !loglik_out) || n == 0 || B == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_eval_batch before the map exists");
+    return eval_batch_impl(c, particle, pts, n, origin3, quat, poses, B, sqnorm_out, loglik_out, true);
 }
 
 int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3,
@@ -2247,22 +2243,6 @@ int32_t lama_hip_map_occupied_cells(lama_hip_ctx* c, uint32_t particle, uint32_t
     return LAMA_HIP_OK;
 }
 
-static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
-                                double* pose_inout, double* out7, int32_t* iters_out, int32_t do_solve, int32_t strategy, uint32_t max_iterations);
-
-int32_t lama_hip_match_solve(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
-                             double* pose_inout, double* out7, int32_t* iters_out, int32_t do_solve)
-{
-    return match_solve_impl(c, particle, pts, n, origin3, quat, pose_inout, out7, iters_out, do_solve, -1, 0);
-}
-
-int32_t lama_hip_match_solve_with(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
-                                  double* pose_inout, double* out7, int32_t* iters_out, int32_t strategy, uint32_t max_iterations)
-{
-    if (strategy != 0 && strategy != 1) return LAMA_HIP_E_INVALID;
-    return match_solve_impl(c, particle, pts, n, origin3, quat, pose_inout, out7, iters_out, 1, strategy, max_iterations);
-}
-
 static int32_t match_eval_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
                                const double* pose, double* residuals, double* jacobian, int cell_mode);
 int32_t lama_hip_match_eval(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
@@ -2300,41 +2280,24 @@ static int32_t match_eval_impl(lama_hip_ctx* c, uint32_t particle, const double*
     return LAMA_HIP_OK;
 }
 
-static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
-                                double* pose_inout, double* out7, int32_t* iters_out, int32_t do_solve, int32_t strategy, uint32_t max_iterations)
+// ---- registration (lama_match_batch.h): B independent (map, scan, start pose) problems in one launch of k_match_solve_batch;
+// lama_hip_match_solve / lama_hip_match_solve_with are a batch of one with the compile-time CauchyWeight(0.15)
+constexpr int32_t MSB_CAUCHY015 = -1;      // (beside the LAMA_HIP_ROBUST_* kinds)
+
+// the staging arrays of B problems (layout at lama_hip_ctx), in elements
+struct MsbLayout {
+    size_t out = 0, pose, mtf, pts, it = 0, st, prob, n_u32;
+    explicit MsbLayout(size_t B) : pose(8 * B), mtf(12 * B), pts(24 * B), st(B), prob(2 * B), n_u32(6 * B) {}
+};
+
+static void stage_problem(lama_hip_ctx* c, const MsbLayout& L, size_t b, const double* pose4, const Affine& m, const MsbProblem& pb)
 {
-    if (!c || !pts || !pose_inout || n == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
-    ENTER(c);
-    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_solve before a map exists");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int32_t rc = upload_scan(c, pts, n);
-    if (rc) return rc;
-    rc = ensure_batch(c, 7, 16);                                     // (a pose in, seven results out)
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_bposes, pose_inout, sizeof(double) * 4, hipMemcpyHostToDevice, c->stream));
-    const Affine mtf = moving_tf(origin3, quat);
-    DevParams prm = make_params(c);
-    if (strategy >= 0) prm.strategy = strategy;
-    if (max_iterations) prm.max_iter = max_iterations;
-    if (c->max_sqdist > (uint32_t)SM_LUT)
-        hipLaunchKernelGGL(k_match_solve<true>, dim3(1), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes, c->d_bout,
-                           c->d_iters, (int)do_solve);
-    else
-        hipLaunchKernelGGL(k_match_solve<false>, dim3(1), dim3(SM_BLOCK), 0, c->stream, prm, (int)particle, c->d_pts, (int)n, mtf, c->d_bposes, c->d_bout,
-                           c->d_iters, (int)do_solve);
-    HIPCHK(c, hipGetLastError());
-    double o7[7]; int32_t it = 0;
-    HIPCHK(c, hipMemcpyAsync(pose_inout, c->d_bposes, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(o7, c->d_bout, sizeof(double) * 7, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&it, c->d_iters, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    rc = check_device_errors(c);
-    if (rc) return rc;
-    if (out7) std::memcpy(out7, o7, sizeof(o7));
-    if (iters_out) *iters_out = it;
-    return LAMA_HIP_OK;
+    std::memcpy(c->h_msb_f64.data() + L.pose + 4 * b, pose4, sizeof(double) * 4);
+    double* q = c->h_msb_f64.data() + L.mtf + 12 * b;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) q[3 * i + j] = m.R[i][j]; q[9 + i] = m.t[i]; }
+    std::memcpy(c->h_msb_u32.data() + L.prob + 4 * b, &pb, sizeof(pb));
 }
 
-// ---- lama_hip_match_solve_batch: B independent (map, scan, start pose) registrations in one launch (lama_match_batch.h)
 extern "C++" {
 template <class WT>
 static void launch_match_solve_batch(lama_hip_ctx* c, const DevParams& prm, uint32_t B, const MsbProblem* d_prob,
@@ -2346,6 +2309,81 @@ static void launch_match_solve_batch(lama_hip_ctx* c, const DevParams& prm, uint
         hipLaunchKernelGGL((k_match_solve_batch<false, WT>), dim3(B), dim3(SM_BLOCK), 0, c->stream, prm, d_prob, d_pts, d_mtf, d_pose, d_out, d_iters, d_status, wt);
 }
 }   // extern "C++"
+
+// Uploads the first n_f64 staged doubles from the poses on (poses, mounts and, when the call staged them, its points) and the problem
+// records, runs the BIGSQ x policy instantiation on the points at d_pts (NULL: the staged ones) and fetches {out8, poses} and
+// {iterations, status} into the staging arrays.  A status word that is set makes the call LAMA_HIP_E_NUMERIC -- with `one_msg`, or,
+// without one, with the count of such problems; the results are in the staging arrays either way.
+static int32_t match_solve_staged(lama_hip_ctx* c, const DevParams& prm, uint32_t B, size_t n_f64, const double* d_pts, int32_t robust_kind,
+                                  double wparam, const char* one_msg)
+{
+    const MsbLayout L(B);
+    double* const hf = c->h_msb_f64.data(); uint32_t* const hu = c->h_msb_u32.data();
+    HIPCHK(c, c->d_msb_f64.grow(n_f64, (size_t)1 << 14)); HIPCHK(c, c->d_msb_u32.grow(L.n_u32, (size_t)1 << 10));
+    double* const df = c->d_msb_f64; uint32_t* const du = c->d_msb_u32;
+    HIPCHK(c, hipMemcpyAsync(df + L.pose, hf + L.pose, sizeof(double) * (n_f64 - L.pose), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(du + L.prob, hu + L.prob, sizeof(uint32_t) * (L.n_u32 - L.prob), hipMemcpyHostToDevice, c->stream));
+    const MsbProblem* const d_prob = reinterpret_cast<const MsbProblem*>(du + L.prob);
+    int32_t* const d_it = reinterpret_cast<int32_t*>(du + L.it);
+#define LAMA_MSB_LAUNCH(...) launch_match_solve_batch(c, prm, B, d_prob, d_pts ? d_pts : df + L.pts, df + L.mtf, df + L.pose, df + L.out, d_it, du + L.st, __VA_ARGS__)
+    switch (robust_kind) {
+    case MSB_CAUCHY015: LAMA_MSB_LAUNCH(WCauchy015{}); break;
+    case LAMA_HIP_ROBUST_UNIT: LAMA_MSB_LAUNCH(WUnit{wparam}); break;
+    case LAMA_HIP_ROBUST_TUKEY: LAMA_MSB_LAUNCH(WTukey{wparam}); break;
+    case LAMA_HIP_ROBUST_TDIST: LAMA_MSB_LAUNCH(WTDist{wparam}); break;
+    case LAMA_HIP_ROBUST_CAUCHY: LAMA_MSB_LAUNCH(WCauchy{wparam}); break;
+    default: LAMA_MSB_LAUNCH(WHuber{wparam}); break;
+    }
+#undef LAMA_MSB_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hf + L.out, df + L.out, sizeof(double) * 12 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hu + L.it, du + L.it, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint32_t bad = 0, first_bad = 0;
+    for (uint32_t b = B; b-- > 0;) if (hu[L.st + b]) { ++bad; first_bad = b; }
+    if (bad && one_msg) return fail(c, LAMA_HIP_E_NUMERIC, one_msg);
+    if (bad)
+        return fail(c, LAMA_HIP_E_NUMERIC, "lama_hip_match_solve_batch: " + std::to_string(bad) + " of " + std::to_string(B) + " problems met a zero-norm unit complex (the first is problem " +
+                                               std::to_string(first_bad) + "; status_out marks them); the other problems' results stand");
+    return LAMA_HIP_OK;
+}
+
+// one problem on the resident scan (upload_scan).  strategy < 0, max_iterations == 0: the context's; do_solve == 0: evaluate only, the
+// pose comes back as it went in
+static int32_t match_solve_one(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                               double* pose_inout, double* out7, int32_t* iters_out, int32_t do_solve, int32_t strategy, uint32_t max_iterations)
+{
+    if (!c || !pts || !pose_inout || n == 0 || particle >= c->P) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_solve before a map exists");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int32_t rc = upload_scan(c, pts, n);
+    if (rc) return rc;
+    const MsbLayout L(1);
+    c->h_msb_f64.resize(L.pts); c->h_msb_u32.resize(L.n_u32);
+    DevParams prm = make_params(c);
+    if (strategy >= 0) prm.strategy = strategy;
+    stage_problem(c, L, 0, pose_inout, moving_tf(origin3, quat), MsbProblem{particle, 0u, n, !do_solve ? 0u : max_iterations ? max_iterations : prm.max_iter});
+    rc = match_solve_staged(c, prm, 1, L.pts, c->d_pts, MSB_CAUCHY015, 0.0, "unit complex number is (near) zero (SophusException in the reference)");
+    if (rc == LAMA_HIP_OK || rc == LAMA_HIP_E_NUMERIC) std::memcpy(pose_inout, c->h_msb_f64.data() + L.pose, sizeof(double) * 4);
+    if (rc) return rc;
+    if (out7) std::memcpy(out7, c->h_msb_f64.data() + L.out, sizeof(double) * 7);
+    if (iters_out) std::memcpy(iters_out, c->h_msb_u32.data() + L.it, sizeof(int32_t));
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_match_solve(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                             double* pose_inout, double* out7, int32_t* iters_out, int32_t do_solve)
+{
+    return match_solve_one(c, particle, pts, n, origin3, quat, pose_inout, out7, iters_out, do_solve, -1, 0);
+}
+
+int32_t lama_hip_match_solve_with(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                                  double* pose_inout, double* out7, int32_t* iters_out, int32_t strategy, uint32_t max_iterations)
+{
+    if (strategy != 0 && strategy != 1) return LAMA_HIP_E_INVALID;
+    return match_solve_one(c, particle, pts, n, origin3, quat, pose_inout, out7, iters_out, 1, strategy, max_iterations);
+}
 
 int32_t lama_hip_match_solve_batch(lama_hip_ctx* c, uint32_t B, const uint32_t* particles, const double* pts, const uint32_t* offs,
                                    const double* origins, const double* quats, double* poses, const uint32_t* max_iterations,
@@ -2403,50 +2441,23 @@ int32_t lama_hip_match_solve_batch(lama_hip_ctx* c, uint32_t B, const uint32_t* 
     if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_solve_batch before a map exists");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     // ---- staging: one array of doubles, one of words (layout at lama_hip_ctx)
-    const size_t o_out = 0, o_pose = 8 * (size_t)B, o_mtf = 12 * (size_t)B, o_pts = 24 * (size_t)B, n_f64 = o_pts + 3 * N;
-    const size_t o_it = 0, o_st = B, o_prob = 2 * (size_t)B, n_u32 = 6 * (size_t)B;
-    c->h_msb_f64.resize(n_f64); c->h_msb_u32.resize(n_u32);
-    double* const hf = c->h_msb_f64.data(); uint32_t* const hu = c->h_msb_u32.data();
-    std::memcpy(hf + o_pose, poses, sizeof(double) * 4 * B);
-    std::memcpy(hf + o_pts, pts + 3 * (size_t)offs[0], sizeof(double) * 3 * N);
-    for (uint32_t b = 0; b < B; ++b) {
-        const Affine m = moving_tf(origins ? origins + 3 * (size_t)b : nullptr, quats ? quats + 4 * (size_t)b : nullptr);
-        double* q = hf + o_mtf + 12 * (size_t)b;
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) q[3 * i + j] = m.R[i][j]; q[9 + i] = m.t[i]; }
-        const MsbProblem pb{particles[b], offs[b] - offs[0], offs[b + 1] - offs[b], max_iterations[b]};
-        std::memcpy(hu + o_prob + 4 * (size_t)b, &pb, sizeof(pb));
-    }
-    HIPCHK(c, c->d_msb_f64.grow(n_f64, (size_t)1 << 14)); HIPCHK(c, c->d_msb_u32.grow(n_u32, (size_t)1 << 10));
-    double* const df = c->d_msb_f64; uint32_t* const du = c->d_msb_u32;
-    HIPCHK(c, hipMemcpyAsync(df + o_pose, hf + o_pose, sizeof(double) * (n_f64 - o_pose), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(du + o_prob, hu + o_prob, sizeof(uint32_t) * (n_u32 - o_prob), hipMemcpyHostToDevice, c->stream));
+    const MsbLayout L(B);
+    const size_t n_f64 = L.pts + 3 * N;
+    c->h_msb_f64.resize(n_f64); c->h_msb_u32.resize(L.n_u32);
+    std::memcpy(c->h_msb_f64.data() + L.pts, pts + 3 * (size_t)offs[0], sizeof(double) * 3 * N);
+    for (uint32_t b = 0; b < B; ++b)
+        stage_problem(c, L, b, poses + 4 * (size_t)b, moving_tf(origins ? origins + 3 * (size_t)b : nullptr, quats ? quats + 4 * (size_t)b : nullptr),
+                      MsbProblem{particles[b], offs[b] - offs[0], offs[b + 1] - offs[b], max_iterations[b]});
     DevParams prm = make_params(c);
     prm.strategy = strategy;
-    const MsbProblem* const d_prob = reinterpret_cast<const MsbProblem*>(du + o_prob);
-    int32_t* const d_it = reinterpret_cast<int32_t*>(du + o_it);
-#define LAMA_MSB_LAUNCH(W) launch_match_solve_batch(c, prm, B, d_prob, df + o_pts, df + o_mtf, df + o_pose, df + o_out, d_it, du + o_st, W{wparam})
-    switch (robust_kind) {
-    case LAMA_HIP_ROBUST_UNIT: LAMA_MSB_LAUNCH(WUnit); break;
-    case LAMA_HIP_ROBUST_TUKEY: LAMA_MSB_LAUNCH(WTukey); break;
-    case LAMA_HIP_ROBUST_TDIST: LAMA_MSB_LAUNCH(WTDist); break;
-    case LAMA_HIP_ROBUST_CAUCHY: LAMA_MSB_LAUNCH(WCauchy); break;
-    default: LAMA_MSB_LAUNCH(WHuber); break;
-    }
-#undef LAMA_MSB_LAUNCH
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hf + o_out, df + o_out, sizeof(double) * 12 * B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hu + o_it, du + o_it, sizeof(uint32_t) * 2 * B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(out8, hf + o_out, sizeof(double) * 8 * B);
-    std::memcpy(poses, hf + o_pose, sizeof(double) * 4 * B);
-    std::memcpy(iters_out, hu + o_it, sizeof(int32_t) * B);
-    if (status_out) std::memcpy(status_out, hu + o_st, sizeof(uint32_t) * B);
-    uint32_t bad = 0, first_bad = 0;
-    for (uint32_t b = B; b-- > 0;) if (hu[o_st + b]) { ++bad; first_bad = b; }
-    if (bad)
-        return fail(c, LAMA_HIP_E_NUMERIC, "lama_hip_match_solve_batch: " + std::to_string(bad) + " of " + std::to_string(B) + " problems met a zero-norm unit complex (the first is problem " +
-                                               std::to_string(first_bad) + "; status_out marks them); the other problems' results stand");
-    return LAMA_HIP_OK;
+    const int32_t rc = match_solve_staged(c, prm, B, n_f64, nullptr, robust_kind, wparam, nullptr);
+    if (rc && rc != LAMA_HIP_E_NUMERIC) return rc;
+    const double* const hf = c->h_msb_f64.data(); const uint32_t* const hu = c->h_msb_u32.data();
+    std::memcpy(out8, hf + L.out, sizeof(double) * 8 * B);
+    std::memcpy(poses, hf + L.pose, sizeof(double) * 4 * B);
+    std::memcpy(iters_out, hu + L.it, sizeof(int32_t) * B);
+    if (status_out) std::memcpy(status_out, hu + L.st, sizeof(uint32_t) * B);
+    return rc;
 }
 
 // Particle blob layout: [pose 4 f64][header 8 i32][dm_dir][occ_dir][dm_sv used][dm_obs used][dm_mask used][occ used][occ_mask used]

@@ -6,7 +6,6 @@
 //   k_raycast      : region 2a (src/pf_slam2d.cpp:458-505): ray-cast + occupancy counters + obstacle events,
 //   k_brushfire    : region 2b (:508): exact dynamic brushfire; both one wave per particle.
 //   k_copy_particles: resample() / first-scan cloning (src/pf_slam2d.cpp:204-216, 558-574).
-//   k_loglik_batch : calculateLikelihood for B poses on one map (src/pf_slam2d.cpp:393-414).
 //
 // All of this is HBM/latency-bound gather/scatter + integer RMW work: no MFMA anywhere.
 #pragma once
@@ -108,8 +107,7 @@ struct BeamCorners {
 
 __device__ inline void sm_corners_begin(const DevParams& prm, const Affine& tf, double px, double py, double pz, BeamCorners& b)
 {
-    b.hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tf.t[0];
-    b.hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + tf.t[1];
+    hit_xy(tf, px, py, pz, b.hx, b.hy);
     const double mx = w2m_nocast(prm, b.hx), my = w2m_nocast(prm, b.hy);
     const uint32_t dx = (uint32_t)mx, dy = (uint32_t)my;
     b.mu0 = mx - (double)dx; b.mu1 = my - (double)dy;
@@ -414,8 +412,7 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
     const int16_t* dir = pv_.dm_dir;
     const sv_t* sv = pv_.dm_sv;
     if (threadIdx.x == 0) {
-        const double* q = prm.poses + 4 * p;
-        sh.state = SE2{cload_f64(q), cload_f64(q + 1), cload_f64(q + 2), cload_f64(q + 3)};
+        sh.state = load_pose(prm.poses + 4 * p);
         sh.tf = scan_tf(sh.state, mtf);
         sh.ctl[0] = 0; sh.ctl[1] = 0;
     }
@@ -448,54 +445,6 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// k_match_solve: Solve(options, MatchSurface2D(dm, scan, pose), &cov) as Loc2D::update uses it
-// (src/loc2d.cpp:168-180): pose in/out, plus what the covariance and the RMSE need at the solution:
-//   out[0..5] lower triangle of J^T J with J weighted (Solver::solve cov branch, src/nlls/solver.cpp:109-116)
-//   out[6]    sum of squared UNWEIGHTED residuals (RMSE, src/loc2d.cpp:178-180)
-// ------------------------------------------------------------------------------------------------
-template <bool BIGSQ>
-__global__ __launch_bounds__(SM_BLOCK) void k_match_solve(DevParams prm, int particle, const double* __restrict__ pts, int n, Affine mtf,
-                                                           double* __restrict__ pose_io, double* __restrict__ out7, int32_t* __restrict__ iters_out,
-                                                           int do_solve)
-{
-    __shared__ SMShared sh;
-    const PV pv_ = pview_w(prm, particle);
-    const int16_t* dir = pv_.dm_dir;
-    const sv_t* sv = pv_.dm_sv;
-    if (threadIdx.x == 0) {
-        sh.state = SE2{cload_f64(pose_io), cload_f64(pose_io + 1), cload_f64(pose_io + 2), cload_f64(pose_io + 3)};
-        sh.tf = scan_tf(sh.state, mtf);
-        sh.ctl[0] = 0; sh.ctl[1] = 0;
-    }
-    sm_build_lut(prm, sh.lut);
-    __syncthreads();
-    uint32_t evals = 0;
-    const uint32_t iter = do_solve ? gn_solve<BIGSQ>(prm, dir, sv, pts, n, mtf, sh, evals) : 0u;
-    double acc[10];
-    const Affine tf = sh.tf;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < n; i += SM_BLOCK) {
-        const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-        const double hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tf.t[0];
-        const double hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + tf.t[1];
-        double gx, gy;
-        const double r = dm_distance(prm, dir, sv, hx, hy, &gx, &gy);
-        const double w = sqrt(cauchy015(r));
-        const double j0 = gx * w, j1 = gy * w, j2 = (gy * hx - gx * hy) * w;
-        acc[0] += j0 * j0; acc[1] += j1 * j0; acc[2] += j1 * j1;
-        acc[3] += j2 * j0; acc[4] += j2 * j1; acc[5] += j2 * j2;
-        acc[6] += r * r;
-    }
-    block_sum<10>(acc, sh.red, sh.tot);
-    if (threadIdx.x == 0) {
-        pose_io[0] = sh.state.c; pose_io[1] = sh.state.s; pose_io[2] = sh.state.tx; pose_io[3] = sh.state.ty;
-        for (int k = 0; k < 7; ++k) out7[k] = sh.tot[k];
-        iters_out[0] = (int32_t)iter;
-    }
-}
-
 // MatchSurface2D::eval (src/match_surface_2d.cpp:42-90) as the reference's Problem interface exposes it: the UNWEIGHTED
 // residual of every beam and, optionally, its Jacobian row [gx, gy, gy*hx - gx*hy] (column-major n x 3 like Eigen's MatrixXd).
 __global__ __launch_bounds__(256) void k_match_eval(DevParams prm, int particle, const double* __restrict__ pts, int n, Affine mtf,
@@ -506,44 +455,18 @@ __global__ __launch_bounds__(256) void k_match_eval(DevParams prm, int particle,
     const PV pv_ = pview_w(prm, particle);
     const int16_t* dir = pv_.dm_dir;
     const sv_t* sv = pv_.dm_sv;
-    if (threadIdx.x == 0) tfs = scan_tf(SE2{cload_f64(pose), cload_f64(pose + 1), cload_f64(pose + 2), cload_f64(pose + 3)}, mtf);     // (a pose the host uploaded)
+    if (threadIdx.x == 0) tfs = load_scan_tf(pose, mtf);
     __syncthreads();
     const Affine tf = tfs;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-    const double hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tf.t[0];
-    const double hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + tf.t[1];
+    double hx, hy;
+    hit_xy(tf, px, py, pz, hx, hy);
     if (cell_mode) { r_out[i] = dm_distance_cell(prm, dir, sv, w2m(prm, hx), w2m(prm, hy)); return; }
     double gx, gy;
     r_out[i] = dm_distance(prm, dir, sv, hx, hy, &gx, &gy);
     if (j_out) { j_out[i] = gx; j_out[(size_t)n + i] = gy; j_out[2 * (size_t)n + i] = gy * hx - gx * hy; }
-}
-
-// calculateLikelihood for B poses against particle `particle`'s distance map
-template <bool BIGSQ>
-__global__ __launch_bounds__(SM_BLOCK) void k_loglik_batch(DevParams prm, int particle, const double* __restrict__ pts, int n,
-                                                            Affine mtf, const double* __restrict__ poses, double* __restrict__ out)
-{
-    __shared__ double red[(SM_BLOCK / 64) * 2];
-    __shared__ double tot[2];
-    __shared__ double lut[SM_LUT];
-    __shared__ Affine tfs;
-    const int b = blockIdx.x;
-    const PV pv_ = pview_w(prm, particle);
-    const int16_t* dir = pv_.dm_dir;
-    const sv_t* sv = pv_.dm_sv;
-    if (threadIdx.x == 0) {
-        const double* q = poses + 4 * b;
-        tfs = scan_tf(SE2{cload_f64(q), cload_f64(q + 1), cload_f64(q + 2), cload_f64(q + 3)}, mtf);
-    }
-    sm_build_lut(prm, lut);
-    __syncthreads();
-    double a2[2];
-    const Affine tf = tfs;
-    eval_beams_res<BIGSQ>(prm, dir, sv, pts, n, tf, a2, lut);
-    block_sum<2>(a2, red, tot);
-    if (threadIdx.x == 0) out[b] = tot[1];
 }
 
 // Loc2D::globalLocalization's inner evaluation (src/loc2d.cpp:275-280): B candidate poses against particle
@@ -560,17 +483,14 @@ __global__ __launch_bounds__(SM_BLOCK) void k_eval_batch(DevParams prm, int part
     const PV pv_ = pview_w(prm, particle);
     const int16_t* dir = pv_.dm_dir;
     const sv_t* sv = pv_.dm_sv;
-    if (threadIdx.x == 0) {
-        const double* q = poses + 4 * b;
-        tfs = scan_tf(SE2{cload_f64(q), cload_f64(q + 1), cload_f64(q + 2), cload_f64(q + 3)}, mtf);
-    }
+    if (threadIdx.x == 0) tfs = load_scan_tf(poses + 4 * b, mtf);
     __syncthreads();
     const Affine tf = tfs;
     double a2[2] = {0.0, 0.0};
     for (int i = threadIdx.x; i < n; i += SM_BLOCK) {
         const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-        const double hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tf.t[0];
-        const double hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + tf.t[1];
+        double hx, hy;
+        hit_xy(tf, px, py, pz, hx, hy);
         const double d = dm_distance(prm, dir, sv, hx, hy, nullptr, nullptr);
         a2[0] += d * d;
         a2[1] += -(d * d) / prm.meas_sigma;
@@ -602,8 +522,8 @@ __global__ __launch_bounds__(64) void k_sample_likelihood(DevParams prm, int par
     for (int j = threadIdx.x; j < nterms; j += 64) {
         const int i = j * step;
         const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-        const double hx = ((base.R[0][0] * px + base.R[0][1] * py) + base.R[0][2] * pz) + tx;
-        const double hy = ((base.R[1][0] * px + base.R[1][1] * py) + base.R[1][2] * pz) + ty;
+        double hx, hy;
+        hit_xy(base, tx, ty, px, py, pz, hx, hy);
         const double dist = dm_distance_cell(prm, dir, sv, w2m(prm, hx), w2m(prm, hy));
         const double e = exp(-(dist * dist) / 0.01);
         terms[j] = e * e * e;

@@ -1,7 +1,9 @@
 // lama_match_batch.h -- k_match_solve_batch: B independent scan-to-map registrations in one launch, with the robust cost the
-// caller names (lama_hip_match_solve_batch, include/lama_hip.h).
+// caller names (lama_hip_match_solve_batch, include/lama_hip.h).  The single-problem entry points (lama_hip_match_solve,
+// lama_hip_match_solve_with: Solve(options, MatchSurface2D(dm, scan, pose), &cov) as Loc2D::update uses it, src/loc2d.cpp:168-180)
+// run it on a batch of one with the compile-time CauchyWeight(0.15) of lama_kernels.h.
 //
-// One workgroup of SM_BLOCK threads per problem, exactly the workgroup of k_match_solve: the same beams per thread, the same
+// One workgroup of SM_BLOCK threads per problem, the workgroup of k_scan_match: the same beams per thread, the same
 // block_sum tree, the same single-lane step (gn_solve, lama_kernels.h).  A problem is a latency chain -- evaluate, reduce, step,
 // evaluate -- of a few microseconds per link; nothing is gained by tiling one problem wider, everything by running many chains
 // side by side.  What differs per problem comes from memory: whose distance map, which slice of the
@@ -48,9 +50,9 @@ struct MsbProblem {
 static_assert(sizeof(MsbProblem) == 16, "MsbProblem is read as two quadwords");
 
 // poses_io [B][4] {c, s, tx, ty}; mtfs [B][12] = the sensor mount of every problem (Translation(origin) * q, rows of R then t);
-// out8 [B][8]: [0..5] lower triangle of J^T J with the weighted J at the returned pose, [6] sum of squared UNWEIGHTED residuals (both
-// as k_match_solve's epilogue computes them), [7] sum of squared CELL distances (MatchSurface2D::error's terms,
-// src/match_surface_2d.cpp:92-116); status [B]: 1 = a step produced a zero-norm unit complex (the reference throws SophusException).
+// out8 [B][8]: [0..5] lower triangle of J^T J with the weighted J at the returned pose (Solver::solve cov branch,
+// src/nlls/solver.cpp:109-116), [6] sum of squared UNWEIGHTED residuals (RMSE, src/loc2d.cpp:178-180), [7] sum of squared CELL
+// distances (MatchSurface2D::error's terms, src/match_surface_2d.cpp:92-116); status [B]: 1 = a step produced a zero-norm unit complex (the reference throws SophusException).
 template <bool BIGSQ, class WT>
 __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) void k_match_solve_batch(
     DevParams prm, const MsbProblem* __restrict__ problems, const double* __restrict__ pts_all,
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
     const int n = (int)pb.n;
     double* const pose_io = poses_io + 4 * (size_t)b;
     if (threadIdx.x == 0) {
-        sh.state = SE2{cload_f64(pose_io), cload_f64(pose_io + 1), cload_f64(pose_io + 2), cload_f64(pose_io + 3)};
+        sh.state = load_pose(pose_io);
         sh.tf = scan_tf(sh.state, mtf);
         sh.ctl[0] = 0; sh.ctl[1] = 0;
         numeric = 0;
@@ -89,15 +91,15 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
     lp.max_iter = pb.max_iter;
     uint32_t evals = 0;
     const uint32_t iter = gn_solve<BIGSQ, WT>(lp, dir, sv, pts, n, mtf, sh, evals, wt, &numeric);
-    // the epilogue of k_match_solve with the problem's own weight, plus the cell distances of MatchSurface2D::error
+    // what the covariance, the RMSE and MatchSurface2D::error need at the solution
     double acc[10];
     const Affine tf = sh.tf;
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[k] = 0.0;
     for (int i = threadIdx.x; i < n; i += SM_BLOCK) {
         const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-        const double hx = ((tf.R[0][0] * px + tf.R[0][1] * py) + tf.R[0][2] * pz) + tf.t[0];
-        const double hy = ((tf.R[1][0] * px + tf.R[1][1] * py) + tf.R[1][2] * pz) + tf.t[1];
+        double hx, hy;
+        hit_xy(tf, px, py, pz, hx, hy);
         double gx, gy;
         const double r = dm_distance(prm, dir, sv, hx, hy, &gx, &gy);
         const double w = sqrt(wt(r));

@@ -9,19 +9,10 @@
 #include <stdexcept>
 
 #include "hip_engine.hpp"
+#include "scan_arrays.hpp"
 #include "transient_map.hpp"
 
 namespace lama {
-
-namespace {
-void scan_arrays(const PointCloudXYZ& s, std::vector<double>& pts, double o[3], double q[4])
-{
-    pts.resize(s.points.size() * 3);
-    for (size_t i = 0; i < s.points.size(); ++i) { pts[3 * i] = s.points[i].x(); pts[3 * i + 1] = s.points[i].y(); pts[3 * i + 2] = s.points[i].z(); }
-    o[0] = s.sensor_origin_.x(); o[1] = s.sensor_origin_.y(); o[2] = s.sensor_origin_.z();
-    q[0] = s.sensor_orientation_.w(); q[1] = s.sensor_orientation_.x(); q[2] = s.sensor_orientation_.y(); q[3] = s.sensor_orientation_.z();
-}
-} // namespace
 
 LidarOdometry2D::LidarOdometry2D(const Options& o) : opt_(o)              // src/lidar_odometry_2d.cpp:42-52
 {
@@ -60,12 +51,11 @@ bool LidarOdometry2D::update(const PointCloudXYZ::Ptr& surface, double)   // :60
         has_first_scan = true;
         return true;
     }
-    std::vector<double> pts; double o[3], q[4];
-    scan_arrays(*surface, pts, o, q);
+    const detail::ScanArrays s(*surface);
     double p[4], out7[7];
     int32_t iters = 0;
     odom.state.toArray(p);
-    const int32_t rc = eng_->match_solve(ctx_, 0, pts.data(), (uint32_t)surface->points.size(), o, q, p, out7, &iters, 1);
+    const int32_t rc = eng_->match_solve(ctx_, 0, s.pts.data(), (uint32_t)surface->points.size(), s.o, s.q, p, out7, &iters, 1);
     if (rc) fail(rc, "lama_hip_match_solve");
     odom.state = SE2d::fromArray(p);                                       // :72
     last_iterations_ = (uint32_t)iters;
@@ -80,20 +70,19 @@ bool LidarOdometry2D::update(const PointCloudXYZ::Ptr& surface, double)   // :60
 void LidarOdometry2D::updateMaps(const PointCloudXYZ::Ptr& surface)        // :85-200
 {
     const PointCloudXYZ& s = *surface;
-    std::vector<double> pts; double o[3], q[4];
-    scan_arrays(s, pts, o, q);
+    const detail::ScanArrays a(s);
     double p[4];
     odom.state.toArray(p);
     const uint32_t n = (uint32_t)s.points.size();
     int32_t rc;
     if (!device_initialised_) {
-        rc = eng_->pf_init(ctx_, pts.data(), n, o, q, p);
+        rc = eng_->pf_init(ctx_, a.pts.data(), n, a.o, a.q, p);
         if (rc) fail(rc, "lama_hip_pf_init");
         device_initialised_ = true;
     } else {
         rc = eng_->pf_set_poses(ctx_, p);
         if (rc) fail(rc, "lama_hip_pf_set_poses");
-        rc = eng_->pf_update_maps(ctx_, pts.data(), n, o, q);
+        rc = eng_->pf_update_maps(ctx_, a.pts.data(), n, a.o, a.q);
         if (rc) fail(rc, "lama_hip_pf_update_maps");
     }
     // transient map (:128-199)

@@ -10,6 +10,7 @@
 #include "covariance3.hpp"
 #include "dm_builder.hpp"
 #include "hip_engine.hpp"
+#include "scan_arrays.hpp"
 #include "lama/random.h"
 
 namespace lama {
@@ -121,14 +122,11 @@ bool Loc2D::enoughMotion(const Pose2D& odometry)               // src/loc2d.cpp:
 void Loc2D::solve(const PointCloudXYZ& s, bool do_solve)
 {
     ensureContext();
-    std::vector<double> pts(s.points.size() * 3);
-    for (size_t i = 0; i < s.points.size(); ++i) { pts[3 * i] = s.points[i].x(); pts[3 * i + 1] = s.points[i].y(); pts[3 * i + 2] = s.points[i].z(); }
-    const double o[3] = {s.sensor_origin_.x(), s.sensor_origin_.y(), s.sensor_origin_.z()};
-    const double q[4] = {s.sensor_orientation_.w(), s.sensor_orientation_.x(), s.sensor_orientation_.y(), s.sensor_orientation_.z()};
+    const detail::ScanArrays a(s);
     double p[4], out7[7];
     int32_t iters = 0;
     pose_.state.toArray(p);
-    const int32_t rc = eng_->match_solve(ctx_, 0, pts.data(), (uint32_t)s.points.size(), o, q, p, out7, &iters, do_solve ? 1 : 0);
+    const int32_t rc = eng_->match_solve(ctx_, 0, a.pts.data(), (uint32_t)s.points.size(), a.o, a.q, p, out7, &iters, do_solve ? 1 : 0);
     if (rc) fail(rc, "lama_hip_match_solve");
     if (do_solve) {
         pose_.state = SE2d::fromArray(p);
@@ -175,14 +173,6 @@ bool Loc2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, do
 
 void Loc2D::triggerGlobalLocalization() { do_global_localization_ = true; }      // :194-197
 
-static void scan_arrays(const PointCloudXYZ& s, std::vector<double>& pts, double o[3], double q[4])
-{
-    pts.resize(s.points.size() * 3);
-    for (size_t i = 0; i < s.points.size(); ++i) { pts[3 * i] = s.points[i].x(); pts[3 * i + 1] = s.points[i].y(); pts[3 * i + 2] = s.points[i].z(); }
-    o[0] = s.sensor_origin_.x(); o[1] = s.sensor_origin_.y(); o[2] = s.sensor_origin_.z();
-    q[0] = s.sensor_orientation_.w(); q[1] = s.sensor_orientation_.x(); q[2] = s.sensor_orientation_.y(); q[3] = s.sensor_orientation_.z();
-}
-
 // :249-286.  The candidates are drawn exactly like the reference (x, y until the cell is free in the occupancy map,
 // then the heading; lama::random's stream); their squared residual norms come from the device in one batch and the
 // FIRST smallest one wins (the reference's strict `<`).
@@ -210,9 +200,8 @@ void Loc2D::globalLocalization(const PointCloudXYZ& surface)
         }
         Pose2D(x, y, a).state.toArray(&gloc_poses_[4 * i]);
     }
-    std::vector<double> pts; double o[3], q[4];
-    scan_arrays(surface, pts, o, q);
-    const int32_t rc = eng_->eval_batch(ctx_, 0, pts.data(), (uint32_t)surface.points.size(), o, q, gloc_poses_.data(), B, gloc_errors_.data(), nullptr);
+    const detail::ScanArrays a(surface);
+    const int32_t rc = eng_->eval_batch(ctx_, 0, a.pts.data(), (uint32_t)surface.points.size(), a.o, a.q, gloc_poses_.data(), B, gloc_errors_.data(), nullptr);
     if (rc) fail(rc, "lama_hip_eval_batch");
     double best_error = std::numeric_limits<double>::max();
     for (uint32_t i = 0; i < B; ++i)
@@ -229,9 +218,8 @@ void Loc2D::addSamplingCovariance(const PointCloudXYZ& surface)
     std::vector<double> xy(2 * K);
     for (size_t i = 0; i < K; ++i) { xy[2 * i] = pose_.x() + sampling_steps_[i].x(); xy[2 * i + 1] = pose_.y() + sampling_steps_[i].y(); }
     sampling_l_.assign(K, 0.0);
-    std::vector<double> pts; double o[3], q[4];
-    scan_arrays(surface, pts, o, q);
-    const int32_t rc = eng_->map_sample_likelihood(ctx_, 0, pts.data(), (uint32_t)num_points, o, q, pose_.rotation(), xy.data(), (uint32_t)K,
+    const detail::ScanArrays a(surface);
+    const int32_t rc = eng_->map_sample_likelihood(ctx_, 0, a.pts.data(), (uint32_t)num_points, a.o, a.q, pose_.rotation(), xy.data(), (uint32_t)K,
                                                    (uint32_t)step, sampling_l_.data());
     if (rc) fail(rc, "lama_hip_map_sample_likelihood");
     double Km[2][2] = {{0, 0}, {0, 0}}, u[2] = {0, 0}, s = 0;

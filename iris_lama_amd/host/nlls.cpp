@@ -8,6 +8,7 @@
 
 #include "covariance3.hpp"
 #include "hip_engine.hpp"
+#include "scan_arrays.hpp"
 #include "lama/match_surface_2d.h"
 #include "lama/nlls/solver.h"
 
@@ -157,16 +158,7 @@ bool LevenbergMarquard::valid(const VectorXd& residuals)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct ScanArrays {
-    std::vector<double> pts;
-    double o[3], q[4];
-    explicit ScanArrays(const PointCloudXYZ& s) : pts(s.points.size() * 3)
-    {
-        for (size_t i = 0; i < s.points.size(); ++i) { pts[3 * i] = s.points[i].x(); pts[3 * i + 1] = s.points[i].y(); pts[3 * i + 2] = s.points[i].z(); }
-        o[0] = s.sensor_origin_.x(); o[1] = s.sensor_origin_.y(); o[2] = s.sensor_origin_.z();
-        q[0] = s.sensor_orientation_.w(); q[1] = s.sensor_orientation_.x(); q[2] = s.sensor_orientation_.y(); q[3] = s.sensor_orientation_.z();
-    }
-};
+using detail::ScanArrays;
 
 const DynamicDistanceMap::DeviceBinding& device_of(const MatchSurface2D& m)
 {
@@ -232,16 +224,21 @@ Solver::Options::Options() : max_iterations(100), strategy(new GaussNewton), rob
 
 namespace {
 
-// the one configuration of a scan-matching problem the fused device solver implements
-int device_strategy(const Solver::Options& o)
+// strategy at its default thresholds -> 0 / 1, else -1 (gn_solve hard-codes 1e-4, csrc/lama_kernels.h)
+int batch_strategy(const Solver::Options& o)
 {
-    const CauchyWeight* cw = dynamic_cast<const CauchyWeight*>(o.robust_cost.get());
-    if (!cw || cw->c_ != 1.0 / (0.15 * 0.15)) return -1;
     if (const GaussNewton* gn = dynamic_cast<const GaussNewton*>(o.strategy.get()))
         return (gn->options().eps1 == 1e-4 && gn->options().eps2 == 1e-4) ? 0 : -1;
     if (const LevenbergMarquard* lm = dynamic_cast<const LevenbergMarquard*>(o.strategy.get()))
         return (lm->options().eps1 == 1e-4 && lm->options().eps2 == 1e-4 && lm->options().tau == 1e-4) ? 1 : -1;
     return -1;
+}
+
+// the one configuration of a scan-matching problem lama::Solve runs on the device: CauchyWeight(0.15) and such a strategy
+int device_strategy(const Solver::Options& o)
+{
+    const CauchyWeight* cw = dynamic_cast<const CauchyWeight*>(o.robust_cost.get());
+    return (cw && cw->c_ == 1.0 / (0.15 * 0.15)) ? batch_strategy(o) : -1;
 }
 
 void cov_from_jacobian(const MatrixXd& J, MatrixXd* cov)
@@ -342,16 +339,6 @@ void Solve(const Solver::Options& options, Problem& problem, MatrixXd* cov)
 // SolveBatch: many MatchSurface2D problems, one launch (lama_hip_match_solve_batch)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-
-// strategy at its default thresholds -> 0 / 1, else -1 (gn_solve hard-codes 1e-4, csrc/lama_kernels.h)
-int batch_strategy(const Solver::Options& o)
-{
-    if (const GaussNewton* gn = dynamic_cast<const GaussNewton*>(o.strategy.get()))
-        return (gn->options().eps1 == 1e-4 && gn->options().eps2 == 1e-4) ? 0 : -1;
-    if (const LevenbergMarquard* lm = dynamic_cast<const LevenbergMarquard*>(o.strategy.get()))
-        return (lm->options().eps1 == 1e-4 && lm->options().eps2 == 1e-4 && lm->options().tau == 1e-4) ? 1 : -1;
-    return -1;
-}
 
 // the weight as (LAMA_HIP_ROBUST_* | LAMA_HIP_ROBUST_STORED, the constant the class stores): the kernel's policy takes exactly that
 // constant, so nothing is squared or inverted a second time.  false: none of the five classes.

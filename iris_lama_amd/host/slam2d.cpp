@@ -8,19 +8,10 @@
 #include <stdexcept>
 
 #include "hip_engine.hpp"
+#include "scan_arrays.hpp"
 #include "transient_map.hpp"
 
 namespace lama {
-
-namespace {
-void scan_arrays(const PointCloudXYZ& s, std::vector<double>& pts, double o[3], double q[4])
-{
-    pts.resize(s.points.size() * 3);
-    for (size_t i = 0; i < s.points.size(); ++i) { pts[3 * i] = s.points[i].x(); pts[3 * i + 1] = s.points[i].y(); pts[3 * i + 2] = s.points[i].z(); }
-    o[0] = s.sensor_origin_.x(); o[1] = s.sensor_origin_.y(); o[2] = s.sensor_origin_.z();
-    q[0] = s.sensor_orientation_.w(); q[1] = s.sensor_orientation_.x(); q[2] = s.sensor_orientation_.y(); q[3] = s.sensor_orientation_.z();
-}
-} // namespace
 
 Slam2D::Slam2D(const Options& o) : trans_thresh_(o.trans_thresh), rot_thresh_(o.rot_thresh), resolution_(o.resolution), l2_max_(o.l2_max)
 {
@@ -108,16 +99,15 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
     if (!surface || surface->points.empty()) throw std::runtime_error("lama::Slam2D::update: empty scan");
     const double t_begin = now_s();
     occ_view_.reset(); dm_view_.reset();
-    std::vector<double> pts;
-    double o[3], q[4], p[4];
-    scan_arrays(*surface, pts, o, q);
+    const detail::ScanArrays s(*surface);
+    double p[4];
     const uint32_t n = (uint32_t)surface->points.size();
     lama_hip_counters c0, c1;
 
     if (!has_first_scan) {                                        // :147-160
         odom_ = odometry;
         pose_.state.toArray(p);
-        int32_t rc = eng_->pf_init(ctx_, pts.data(), n, o, q, p); // updateMaps(surface) at pose_
+        int32_t rc = eng_->pf_init(ctx_, s.pts.data(), n, s.o, s.q, p); // updateMaps(surface) at pose_
         if (rc) fail(rc, "lama_hip_pf_init");
         if (eng_->get_counters(ctx_, &c1) == 0) number_of_proccessed_cells_ = (uint32_t)c1.bf_cells;
         if (transient_map_) {                                      // :322-379
@@ -144,7 +134,7 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
     int32_t rc = eng_->pf_set_poses(ctx_, p);
     if (rc) fail(rc, "lama_hip_pf_set_poses");
     int32_t iters = 0;
-    rc = eng_->pf_scan_match(ctx_, pts.data(), n, o, q, p, nullptr, &iters);
+    rc = eng_->pf_scan_match(ctx_, s.pts.data(), n, s.o, s.q, p, nullptr, &iters);
     if (rc) fail(rc, "lama_hip_pf_scan_match");
     pose_.state = SE2d::fromArray(p);
     last_iterations_ = (uint32_t)iters;
@@ -152,7 +142,7 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
     // 3. update maps                                              :184-186
     const double t_map = now_s();
     (void)eng_->get_counters(ctx_, &c0);
-    rc = eng_->pf_update_maps(ctx_, pts.data(), n, o, q);
+    rc = eng_->pf_update_maps(ctx_, s.pts.data(), n, s.o, s.q);
     if (rc) fail(rc, "lama_hip_pf_update_maps");
     if (eng_->get_counters(ctx_, &c1) == 0) number_of_proccessed_cells_ = (uint32_t)(c1.bf_cells - c0.bf_cells);
     if (transient_map_) {                                          // :322-379

@@ -1,4 +1,4 @@
-"""Checks of the single-map matching kernels (k_match_eval and its cell mode, k_match_solve, k_eval_batch, k_loglik_batch,
+"""Checks of the single-map matching kernels (k_match_eval and its cell mode, k_match_solve_batch on a batch of one, k_eval_batch,
 k_sample_likelihood) against the CPU oracle, shared by tests/test_match_kernels_gpu.py and the lane-simulator tests.
 
 Tolerances (each derived, none tuned):
@@ -161,12 +161,12 @@ def check_eval(ctx, dm, pts, pose, origin=O.ZERO3, quat=O.IDENT_Q, same_libm=Fal
 
 
 def check_batch(ctx, dm, pts, poses, origin=O.ZERO3, quat=O.IDENT_Q, what=""):
-    """k_eval_batch (squared norm, log-likelihood) and k_loglik_batch on poses with c = 1, s = 0, against fsum of the
-    oracle's per-beam terms"""
+    """k_eval_batch (squared norm, log-likelihood; lama_hip_match_batch is its log-likelihood alone) on poses with c = 1, s = 0,
+    against fsum of the oracle's per-beam terms"""
     assert np.all(poses[:, 0] == 1.0) and np.all(poses[:, 1] == 0.0)
     sq, ll = ctx.eval_batch(0, pts, poses, origin, quat)
     ll2 = ctx.match_batch(0, pts, poses, origin, quat)
-    # the same beams per thread in the same order, the same block tree: bit-equal (test_eval_batch_matches_oracle_and_match_batch)
+    # the same kernel with and without its squared-norm output: bit-equal (test_eval_batch_matches_oracle_and_match_batch)
     assert np.array_equal(ll, ll2), what
     for b, q in enumerate(poses):
         r = O.eval_(dm, pts, q, origin, quat, jac=False)
@@ -177,7 +177,7 @@ def check_batch(ctx, dm, pts, poses, origin=O.ZERO3, quat=O.IDENT_Q, what=""):
 
 
 def check_solve(ctx, dm, pts, start, origin=O.ZERO3, quat=O.IDENT_Q, same_libm=False, what=""):
-    """k_match_solve: pose and iteration count of Solve(GN, Cauchy(0.15)); J^T J lower triangle (weighted J) and the sum of
+    """lama_hip_match_solve (k_match_solve_batch, one problem): pose and iteration count of Solve(GN, Cauchy(0.15)); J^T J lower triangle (weighted J) and the sum of
     squared unweighted residuals at the returned pose against fsum of the per-beam terms there"""
     pose, jtj, sr2, it = ctx.match_solve(0, pts, start, origin, quat)
     opose, oit, _ = O.solve_full(dm, pts, start, origin=origin, quat=quat)

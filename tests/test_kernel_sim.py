@@ -311,7 +311,7 @@ def test_wide_build_randomized_small_rooms(Fsim_wide, seed, l2_max):
 
 
 def test_single_map_matching_kernels_at_small_scan_sizes_on_the_simulator(Fsim):
-    """k_match_eval (and its cell mode), k_match_solve, k_eval_batch / k_loglik_batch and k_sample_likelihood on one static map
+    """k_match_eval (and its cell mode), k_match_solve_batch as the single solves run it, k_eval_batch and k_sample_likelihood on one static map
     (tests/_match_checks.py): scans shorter than a wave, than a block, with a tail past the 256-thread block, and the point
     counts for which Loc2D's sampling step asks for more than 128 terms (180, 257, 390).  The simulator links the host's libm,
     so every per-beam value and the sampled sums are bit-equal to the oracle's; summed outputs are within the fsum bound."""
@@ -333,4 +333,9 @@ def test_single_map_matching_kernels_at_small_scan_sizes_on_the_simulator(Fsim):
     pts, pose = M.edge_scan()
     M.check_eval(ctx, dm, pts, pose, same_libm=True, what="mu = 0")
     M.check_solve(ctx, dm, pts, pose, same_libm=True, what="mu = 0")
+    # the scan of a lama_hip_match_solve call stays resident: the next call may pass pts == NULL and reads the same points
+    ctx.match_solve(0, pts, pose)
+    poses, sq = M.batch_poses(rng, 4), np.zeros(4)
+    assert ctx.L.lama_hip_eval_batch(ctx.h, 0, None, len(pts), None, None, Fsim._p(poses), 4, Fsim._p(sq), None) == 0
+    assert np.array_equal(sq, ctx.eval_batch(0, pts, poses)[0])
     ctx.close()

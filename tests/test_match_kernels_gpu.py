@@ -1,5 +1,5 @@
 """-m gpu: the single-map matching kernels behind lama::Loc2D, MatchSurface2D / Solve and global localisation (k_match_eval and its
-cell mode, k_match_solve, k_eval_batch, k_loglik_batch, k_sample_likelihood) against the CPU oracle across scan sizes: shorter than
+cell mode, k_match_solve_batch as the single solves run it, k_eval_batch, k_sample_likelihood) against the CPU oracle across scan sizes: shorter than
 a wave, than a block, tails past the 256-thread block and the 1280-beam gather batch, the point counts for which Loc2D's sampling
 step asks for more than 128 terms, on both sides of the LDS sqrt table (max_sqdist 484 / 529) and in the wide library.
 
