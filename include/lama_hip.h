@@ -353,7 +353,9 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
  *                      Outputs may be NULL.  (Bit for bit: blocks are the scatter of lama_hip_pgo_linearize's Hdiag / Hoff.)
  *   try_step         : candidate = current * exp(dx) per pose (dx [N][3], the right-multiplicative retract of minisam's Sophus
  *                      traits) and its 0.5 sum ||e||^2; only dx goes up and one scalar comes back.
- *   accept           : the candidate becomes the current state (no copy).
+ *   accept           : the candidate becomes the current state (no copy).  A candidate is pending from a successful try_step until
+ *                      the next accept, set_poses or lama_hip_pgo_linearize; with none pending accept returns LAMA_HIP_E_STATE
+ *                      (lama_hip_pgo_last_error says so) and leaves the current state as it is.
  * kernel_ms: device time of the call's kernels (may be NULL). */
 int32_t lama_hip_pgo_pattern(const lama_hip_pgo* g, int32_t* row_ptr, int32_t* cols, uint32_t* nnzb);
 int32_t lama_hip_pgo_set_poses(lama_hip_pgo* g, const double* poses4);

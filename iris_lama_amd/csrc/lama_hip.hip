@@ -1864,6 +1864,7 @@ struct lama_hip_pgo {
     std::vector<int32_t> h_rowptr, h_cols;
     DevBuf<double> d_cand, d_dx, d_blocks, d_diag, d_half;
     DevBuf<int32_t> d_brow, d_bcol, d_cptr, d_contrib;
+    bool candidate_pending = false;        // d_cand holds the candidate of a try_step that no accept / set_poses / linearize followed
 
     __attribute__((visibility("hidden"))) ~lama_hip_pgo() { (void)hipSetDevice(device); }     // (not exported: the C-ABI is)
 };
@@ -1929,6 +1930,7 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
                                double* kernel_ms)
 {
     if (!g || !poses4) return LAMA_HIP_E_INVALID;
+    g->candidate_pending = false;
     PGOCHK(g, hipSetDevice(g->device));
     PGOCHK(g, hipMemcpyAsync(g->d_poses, poses4, sizeof(double) * 4 * g->N, hipMemcpyHostToDevice, g->stream));
     PgoPtrs p{g->d_poses, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
@@ -1961,6 +1963,7 @@ int32_t lama_hip_pgo_pattern(const lama_hip_pgo* g, int32_t* row_ptr, int32_t* c
 int32_t lama_hip_pgo_set_poses(lama_hip_pgo* g, const double* poses4)
 {
     if (!g || !poses4) return LAMA_HIP_E_INVALID;
+    g->candidate_pending = false;
     PGOCHK(g, hipSetDevice(g->device));
     PGOCHK(g, hipMemcpyAsync(g->d_poses, poses4, sizeof(double) * 4 * g->N, hipMemcpyHostToDevice, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
@@ -2004,6 +2007,7 @@ int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b
 int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_chi2, double* kernel_ms)
 {
     if (!g || !dx || !half_chi2) return LAMA_HIP_E_INVALID;
+    g->candidate_pending = false;          // (set again once the candidate is complete)
     PGOCHK(g, hipSetDevice(g->device));
     PgoPtrs p{g->d_cand, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
               g->d_hdiag, g->d_b, g->d_chi};
@@ -2019,6 +2023,7 @@ int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_ch
     PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
     *half_chi2 = h;
+    g->candidate_pending = true;
     if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
     return LAMA_HIP_OK;
 }
@@ -2026,6 +2031,11 @@ int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_ch
 int32_t lama_hip_pgo_accept(lama_hip_pgo* g)
 {
     if (!g) return LAMA_HIP_E_INVALID;
+    if (!g->candidate_pending) {           // (the swap would bring back whatever the candidate buffer held before)
+        g->error = "lama_hip_pgo_accept: no candidate pending (call lama_hip_pgo_try_step first)";
+        return LAMA_HIP_E_STATE;
+    }
+    g->candidate_pending = false;
     g->d_poses.swap(g->d_cand);            // (the stream is idle: try_step synchronised it)
     return LAMA_HIP_OK;
 }

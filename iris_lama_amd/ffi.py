@@ -1326,6 +1326,7 @@ class PoseGraph:
         return half.value, ms.value
 
     def accept(self):
+        """The candidate of the last try_step becomes the current state; LamaError when none is pending."""
         self._check(self.L.lama_hip_pgo_accept(self.h))
 
 

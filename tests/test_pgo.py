@@ -139,5 +139,10 @@ def test_device_linearisation_at_config5_size():
     orc = O.pgo_linearize(init, fi, fj, meas, sq)
     assert np.allclose(dev["Hdiag"], orc["Hdiag"], rtol=1e-12, atol=1e-11)
     assert np.allclose(dev["b"], orc["b"], rtol=1e-10, atol=1e-10)
+    # 196 partial sums: the per-factor outputs and the error, too (tolerances of test_device_linearisation_matches_oracle; the sum
+    # of 50000 non-negative terms in another order is within 3 F eps of the oracle's)
+    assert np.allclose(dev["err"], orc["err"], rtol=1e-12, atol=1e-13)
+    assert np.allclose(dev["Hoff"], orc["Hoff"], rtol=1e-12, atol=1e-13)
+    assert abs(dev["chi2"] - orc["chi2"]) <= 3 * len(fi) * np.finfo(np.float64).eps * orc["chi2"]
     print(f"pgo linearize 10k poses / 50k factors: {dev['kernel_ms']:.3f} ms on the device")
     g.close()
