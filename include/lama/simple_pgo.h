@@ -4,7 +4,8 @@
 // (sigmas 1, 1, 1) -- or one prior per fixed node (sigmas 0.1) --, odometry between consecutive nodes and the loop closures of
 // edge_list (sigmas 0.5, 0.5, 0.1), solved by minisam's Levenberg-Marquardt with its default parameters.  Here the poses stay on the
 // GPU for the whole optimize(): the residuals, the Jacobians, the assembled Hessian blocks and every trial step are computed by the
-// device library (lama_hip_pgo_*, include/lama_hip.h); the sparse LDL^T factorisation runs on the host.  There is no CPU fallback:
+// device library (lama_hip_pgo_*, include/lama_hip.h); the sparse LDL^T factorisation runs on the host unless linear_solver (below)
+// asks for the device's conjugate gradient in its place.  There is no CPU fallback:
 // optimize() throws std::runtime_error when the device library or a HIP device is missing.
 //
 // optimize() returns true and writes the result into node_list only when the optimizer reports SUCCESS; any other status
@@ -52,8 +53,25 @@ struct SimplePGO {
         double ms_factorize = 0.0;          // host: numeric factorisation and solve (every try)
         double ms_total = 0.0;
         DynamicArray<int8_t> trace;         // per try: 1 accepted, 0 rejected (no gain), 2 rank deficient
+        // linear_solver = DevicePCG (all zero otherwise)
+        uint64_t pcg_iterations = 0;        // conjugate-gradient iterations, summed over the tries
+        uint32_t pcg_max_iterations_seen = 0;   // the longest solve
+        uint32_t pcg_fallbacks = 0;         // tries that reached the iteration cap and went to the host LDL^T instead
+        double ms_device_solve = 0.0;       // device: the solves (summed)
     };
     Report report;
+
+    // How the damped system (H + lambda diag(H)) dx = b of every Levenberg-Marquardt try is solved.
+    //   HostLDLT  : the sparse LDL^T on the host (the default; what the lines above describe).
+    //   DevicePCG : a conjugate gradient preconditioned by the damped 3x3 diagonal blocks, on the device (lama_hip_pgo_solve_pcg):
+    //               nothing is factorised, the system and the step never leave the device.  The right choice for graphs with many
+    //               loop closures, whose factor fills in; a chain with few closures needs thousands of iterations and has no fill --
+    //               leave those to HostLDLT.  A try whose solve reaches pcg_max_iterations is solved by the host LDL^T instead
+    //               (report.pcg_fallbacks counts them); optimize() throws std::runtime_error when the device library lacks the solver.
+    enum LinearSolver { HostLDLT = 0, DevicePCG = 1 };
+    LinearSolver linear_solver = HostLDLT;
+    double pcg_rel_tol = 1e-10;        // stop at ||r|| <= pcg_rel_tol ||b||
+    uint32_t pcg_max_iterations = 0;   // 0: max(100, 6 * node_list.size())
 };
 
 } // namespace lama

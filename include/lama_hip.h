@@ -364,6 +364,28 @@ int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b
 int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_chi2, double* kernel_ms);
 int32_t lama_hip_pgo_accept(lama_hip_pgo* g);
 
+/* The damped system of one Levenberg-Marquardt try, (H + lambda diag(H)) dx = b, solved on the device by a conjugate gradient
+ * preconditioned with the inverse of the damped 3x3 diagonal blocks (iris_lama_amd/csrc/lama_pgo_pcg.h): no factorisation, no fill.
+ * Opt-in (lama::SimplePGO::linear_solver); the calls above are unchanged.
+ *   solve_pcg       : needs a lama_hip_pgo_linearize_system since the last set_poses / accept / lama_hip_pgo_linearize, otherwise
+ *                     LAMA_HIP_E_STATE (lama_hip_pgo_last_error says so).  Stops when r.r <= rel_tol^2 b.b (outcome CONVERGED; b = 0
+ *                     gives dx = 0 after 0 iterations), after max_iterations (CAP), or when a damped diagonal block is not positive
+ *                     definite or p.(H + lambda D)p is not a positive finite number (BREAKDOWN; nothing non-finite is stored).  The
+ *                     solution stays on the device; dx [N][3] may be NULL.  rel_residual_sq = r.r / b.b of the recurrence;
+ *                     model_decrease = 0.5 sum dx (lambda diag dx + b), the denominator of minisam's gain ratio.  The iterations are
+ *                     enqueued `batch` at a time (0: LAMA_HIP_PCG_DEFAULT_BATCH) and the device's stop word is read once per batch;
+ *                     the result does not depend on the batch.  LAMA_HIP_E_INVALID with nothing touched: lambda negative or not
+ *                     finite, rel_tol outside (0, 1), max_iterations == 0.  The system (blocks, b, diag) is only read.
+ *   try_solved_step : lama_hip_pgo_try_step with the solution the device holds (after CONVERGED or CAP); LAMA_HIP_E_STATE when there
+ *                     is none or the state or the system changed since the solve.  accept works after it as after try_step. */
+#define LAMA_HIP_PCG_CONVERGED 0
+#define LAMA_HIP_PCG_CAP 1
+#define LAMA_HIP_PCG_BREAKDOWN 2
+#define LAMA_HIP_PCG_DEFAULT_BATCH 32
+int32_t lama_hip_pgo_solve_pcg(lama_hip_pgo* g, double lambda, double rel_tol, uint32_t max_iterations, uint32_t batch, double* dx,
+                               uint32_t* iterations, double* rel_residual_sq, int32_t* outcome, double* model_decrease, double* kernel_ms);
+int32_t lama_hip_pgo_try_solved_step(lama_hip_pgo* g, double* half_chi2, double* kernel_ms);
+
 /* Accumulated per-kernel device time (hipEvent elapsed, on the stream the kernels run on) and work
  * counters since the last reset; valid when cfg.profile != 0. */
 typedef struct lama_hip_counters {

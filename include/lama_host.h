@@ -239,6 +239,31 @@ typedef struct lama_pgo_report {
 int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4, uint32_t ne,
                       const int32_t* fixed_idx, const double* fixed4, uint32_t nf, int32_t device, double* out4, lama_pgo_report* report,
                       int8_t* trace, uint32_t trace_cap, char* err, int errcap);
+/* The same with the choice of the linear solver (lama::SimplePGO::linear_solver and its pcg_* members).  Both structs begin with their
+ * own size as the CALLER compiled it: the library reads and writes at most that many bytes, so either may grow at its end.
+ * lama_pgo_report2 is lama_pgo_report behind struct_bytes, then the counters of the device solver (all zero with the host LDL^T). */
+typedef struct lama_pgo_options {
+    uint32_t struct_bytes;          /* sizeof(lama_pgo_options) */
+    int32_t device;
+    int32_t linear_solver;          /* 0: sparse LDL^T on the host (what lama_pgo_optimize runs), 1: block-Jacobi PCG on the device */
+    uint32_t pcg_max_iterations;    /* 0: max(100, 6 n) */
+    double pcg_rel_tol;             /* ||r|| <= pcg_rel_tol ||b||; 1e-10 in lama::SimplePGO */
+} lama_pgo_options;
+typedef struct lama_pgo_report2 {
+    uint32_t struct_bytes;          /* sizeof(lama_pgo_report2), set by the caller */
+    int32_t status;
+    uint32_t iterations, tries;
+    double initial_error, final_error;
+    uint64_t nnz_L;                 /* 0 when no try needed the host factorisation */
+    double ms_device_linearize, ms_device_try, ms_analyze, ms_factorize, ms_total;
+    uint64_t pcg_iterations;        /* summed over the tries */
+    uint32_t pcg_max_iterations_seen;    /* the longest solve */
+    uint32_t pcg_fallbacks;         /* tries that reached the iteration cap and were solved by the host LDL^T instead */
+    double ms_device_solve;         /* device time of the solves, summed */
+} lama_pgo_report2;
+int lama_pgo_optimize_with(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4,
+                           uint32_t ne, const int32_t* fixed_idx, const double* fixed4, uint32_t nf, const lama_pgo_options* options,
+                           double* out4, lama_pgo_report2* report, int8_t* trace, uint32_t trace_cap, char* err, int errcap);
 /* ---- lama::MapBuilder2D (include/lama/map_builder_2d.h), flattened: a map rebuilt from posed key scans ---- */
 typedef struct lama_mapbuilder lama_mapbuilder;
 typedef struct lama_mapbuilder_options {

@@ -17,6 +17,7 @@
 
 #include "lama_kernels.h"
 #include "lama_pgo.h"
+#include "lama_pgo_pcg.h"
 #include "lama_map_build.h"
 #include "lama_match_batch.h"
 #include "../host/pgo_pattern.hpp"
@@ -1865,6 +1866,13 @@ struct lama_hip_pgo {
     DevBuf<double> d_cand, d_dx, d_blocks, d_diag, d_half;
     DevBuf<int32_t> d_brow, d_bcol, d_cptr, d_contrib;
     bool candidate_pending = false;        // d_cand holds the candidate of a try_step that no accept / set_poses / linearize followed
+    // the device solver of the damped system (lama_pgo_pcg.h; lama_hip_pgo_solve_pcg, _try_solved_step)
+    uint32_t parts_pq = 0, parts_v = 0;    // partials per dot product: one per PCG_ROWS rows (p.q), one per PGO_BLOCK poses (the others)
+    DevBuf<int32_t> d_rowptr, d_tptr, d_tidx;
+    DevBuf<double> d_minv, d_px, d_pr, d_pz, d_pp, d_pq, d_part_pq, d_part_rr, d_part_rz;
+    DevBuf<PcgState> d_pcg;
+    bool system_valid = false;             // d_blocks / d_b / d_diag are the system at d_poses (linearize_system since the state last changed)
+    bool solution_valid = false;           // d_px solves that system (solve_pcg since)
 
     __attribute__((visibility("hidden"))) ~lama_hip_pgo() { (void)hipSetDevice(device); }     // (not exported: the C-ABI is)
 };
@@ -1918,6 +1926,25 @@ int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const
         hipMemcpy(p->d_cptr, cptr.data(), sizeof(int32_t) * cptr.size(), hipMemcpyHostToDevice) ||
         (!contrib.empty() && hipMemcpy(p->d_contrib, contrib.data(), sizeof(int32_t) * contrib.size(), hipMemcpyHostToDevice)))
         return LAMA_HIP_E_HIP;
+    // the transpose index of the lower pattern (lama_pgo_pcg.h): for every row r the off-diagonal blocks whose COLUMN is r, ascending
+    // in their row (the blocks are stored by ascending row, so a counting sort by column keeps that order)
+    std::vector<int32_t> tptr(N + 1, 0), tidx;
+    for (uint32_t q = 0; q < p->nnzb; ++q) if (brow[q] != bcol[q]) ++tptr[bcol[q] + 1];
+    for (uint32_t v = 0; v < N; ++v) tptr[v + 1] += tptr[v];
+    tidx.resize(tptr[N]);
+    { std::vector<int32_t> at(tptr.begin(), tptr.end() - 1);
+      for (uint32_t q = 0; q < p->nnzb; ++q) if (brow[q] != bcol[q]) tidx[at[bcol[q]]++] = (int32_t)q; }
+    p->parts_pq = (N + PCG_ROWS - 1) / PCG_ROWS;
+    p->parts_v = (N + PGO_BLOCK - 1) / PGO_BLOCK;
+    if (p->d_rowptr.alloc((size_t)N + 1) || p->d_tptr.alloc((size_t)N + 1) || p->d_tidx.alloc(std::max<size_t>(tidx.size(), 1)) ||
+        p->d_minv.alloc(9 * (size_t)N) || p->d_px.alloc(3 * (size_t)N) || p->d_pr.alloc(3 * (size_t)N) || p->d_pz.alloc(3 * (size_t)N) ||
+        p->d_pp.alloc(3 * (size_t)N) || p->d_pq.alloc(3 * (size_t)N) || p->d_part_pq.alloc(p->parts_pq) || p->d_part_rr.alloc(p->parts_v) ||
+        p->d_part_rz.alloc(p->parts_v) || p->d_pcg.alloc(1))
+        return LAMA_HIP_E_HIP;
+    if (hipMemcpy(p->d_rowptr, bp.row_ptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_tptr, tptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice) ||
+        (!tidx.empty() && hipMemcpy(p->d_tidx, tidx.data(), sizeof(int32_t) * tidx.size(), hipMemcpyHostToDevice)))
+        return LAMA_HIP_E_HIP;
     *out = p.release();
     return LAMA_HIP_OK;
 }
@@ -1931,6 +1958,7 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
 {
     if (!g || !poses4) return LAMA_HIP_E_INVALID;
     g->candidate_pending = false;
+    g->system_valid = g->solution_valid = false;
     PGOCHK(g, hipSetDevice(g->device));
     PGOCHK(g, hipMemcpyAsync(g->d_poses, poses4, sizeof(double) * 4 * g->N, hipMemcpyHostToDevice, g->stream));
     PgoPtrs p{g->d_poses, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
@@ -1964,6 +1992,7 @@ int32_t lama_hip_pgo_set_poses(lama_hip_pgo* g, const double* poses4)
 {
     if (!g || !poses4) return LAMA_HIP_E_INVALID;
     g->candidate_pending = false;
+    g->system_valid = g->solution_valid = false;
     PGOCHK(g, hipSetDevice(g->device));
     PGOCHK(g, hipMemcpyAsync(g->d_poses, poses4, sizeof(double) * 4 * g->N, hipMemcpyHostToDevice, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
@@ -1982,6 +2011,7 @@ int32_t lama_hip_pgo_get_poses(lama_hip_pgo* g, double* poses4)
 int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b, double* diag, double* half_chi2, double* kernel_ms)
 {
     if (!g) return LAMA_HIP_E_INVALID;
+    g->system_valid = g->solution_valid = false;   // (set again once the system is complete)
     PGOCHK(g, hipSetDevice(g->device));
     PgoPtrs p{g->d_poses, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
               g->d_hdiag, g->d_b, g->d_chi};
@@ -1999,6 +2029,7 @@ int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b
     double h = 0.0;
     PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
+    g->system_valid = true;
     if (half_chi2) *half_chi2 = h;
     if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
     return LAMA_HIP_OK;
@@ -2036,7 +2067,98 @@ int32_t lama_hip_pgo_accept(lama_hip_pgo* g)
         return LAMA_HIP_E_STATE;
     }
     g->candidate_pending = false;
+    g->system_valid = g->solution_valid = false;
     g->d_poses.swap(g->d_cand);            // (the stream is idle: try_step synchronised it)
+    return LAMA_HIP_OK;
+}
+
+// ---- the damped system solved on the device (lama_pgo_pcg.h)
+static PcgPtrs pcg_ptrs(lama_hip_pgo* g)
+{
+    return PcgPtrs{g->d_blocks, g->d_diag, g->d_b, g->d_rowptr, g->d_bcol, g->d_brow, g->d_tptr, g->d_tidx, g->d_minv, g->d_px, g->d_pr,
+                   g->d_pz, g->d_pp, g->d_pq, g->d_part_pq, g->d_part_rr, g->d_part_rz, g->d_pcg};
+}
+
+int32_t lama_hip_pgo_solve_pcg(lama_hip_pgo* g, double lambda, double rel_tol, uint32_t max_iterations, uint32_t batch, double* dx,
+                               uint32_t* iterations, double* rel_residual_sq, int32_t* outcome, double* model_decrease, double* kernel_ms)
+{
+    if (!g) return LAMA_HIP_E_INVALID;
+    if (!(lambda >= 0.0) || !std::isfinite(lambda) || !(rel_tol > 0.0 && rel_tol < 1.0) || max_iterations == 0) {
+        g->error = "lama_hip_pgo_solve_pcg: lambda must be finite and >= 0, rel_tol in (0, 1), max_iterations > 0";
+        return LAMA_HIP_E_INVALID;
+    }
+    if (!g->system_valid) {
+        g->error = "lama_hip_pgo_solve_pcg: no linear system at the current state (call lama_hip_pgo_linearize_system first)";
+        return LAMA_HIP_E_STATE;
+    }
+    if (batch == 0) batch = LAMA_HIP_PCG_DEFAULT_BATCH;
+    g->solution_valid = false;
+    PGOCHK(g, hipSetDevice(g->device));
+    const PcgPtrs s = pcg_ptrs(g);
+    const uint32_t N = g->N;
+    const dim3 grid_v(g->parts_v), grid_pq(g->parts_pq), block(PGO_BLOCK);
+    PcgState st;
+    PGOCHK(g, hipMemsetAsync(g->d_pcg, 0, sizeof(PcgState), g->stream));
+    PGOCHK(g, hipEventRecord(g->ev0, g->stream));
+    hipLaunchKernelGGL(k_pgo_pcg_setup, grid_v, block, 0, g->stream, s, lambda, N);
+    hipLaunchKernelGGL(k_pgo_pcg_begin, dim3(1), dim3(64), 0, g->stream, s, rel_tol * rel_tol, g->parts_v);
+    PGOCHK(g, hipGetLastError());
+    PGOCHK(g, hipMemcpyAsync(&st, g->d_pcg, sizeof(PcgState), hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    uint32_t enqueued = 0;
+    while (st.done == 0 && enqueued < max_iterations) {
+        const uint32_t n = std::min(batch, max_iterations - enqueued);
+        for (uint32_t k = enqueued; k < enqueued + n; ++k) {
+            hipLaunchKernelGGL(k_pgo_pcg_spmv, grid_pq, block, 0, g->stream, s, lambda, N);
+            hipLaunchKernelGGL(k_pgo_pcg_step, grid_v, block, 0, g->stream, s, k & 1u, g->parts_pq, N);
+            hipLaunchKernelGGL(k_pgo_pcg_dir, grid_v, block, 0, g->stream, s, k, g->parts_pq, g->parts_v, N);
+        }
+        enqueued += n;
+        PGOCHK(g, hipGetLastError());
+        PGOCHK(g, hipMemcpyAsync(&st, g->d_pcg, sizeof(PcgState), hipMemcpyDeviceToHost, g->stream));
+        PGOCHK(g, hipStreamSynchronize(g->stream));
+    }
+    hipLaunchKernelGGL(k_pgo_pcg_model, grid_v, block, 0, g->stream, s, lambda, N);
+    hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_part_rr, g->parts_v, &((PcgState*)g->d_pcg)->model);
+    PGOCHK(g, hipEventRecord(g->ev1, g->stream));
+    PGOCHK(g, hipGetLastError());
+    PGOCHK(g, hipMemcpyAsync(&st, g->d_pcg, sizeof(PcgState), hipMemcpyDeviceToHost, g->stream));
+    if (dx) PGOCHK(g, hipMemcpyAsync(dx, g->d_px, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    const int32_t oc = st.done == PCG_CONVERGED ? LAMA_HIP_PCG_CONVERGED : st.done == PCG_BREAKDOWN ? LAMA_HIP_PCG_BREAKDOWN : LAMA_HIP_PCG_CAP;
+    g->solution_valid = oc != LAMA_HIP_PCG_BREAKDOWN;
+    if (iterations) *iterations = st.iters;
+    if (rel_residual_sq) *rel_residual_sq = st.bb == 0.0 ? 0.0 : st.rr / st.bb;
+    if (outcome) *outcome = oc;
+    if (model_decrease) *model_decrease = st.model;
+    if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pgo_try_solved_step(lama_hip_pgo* g, double* half_chi2, double* kernel_ms)
+{
+    if (!g || !half_chi2) return LAMA_HIP_E_INVALID;
+    if (!g->solution_valid) {
+        g->error = "lama_hip_pgo_try_solved_step: no solution of the system at the current state (call lama_hip_pgo_solve_pcg first)";
+        return LAMA_HIP_E_STATE;
+    }
+    g->candidate_pending = false;          // (set again once the candidate is complete)
+    PGOCHK(g, hipSetDevice(g->device));
+    PgoPtrs p{g->d_cand, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
+              g->d_hdiag, g->d_b, g->d_chi};
+    PGOCHK(g, hipEventRecord(g->ev0, g->stream));
+    hipLaunchKernelGGL(k_pgo_retract, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, (const double*)g->d_poses,
+                       (const double*)g->d_px, (double*)g->d_cand, g->N);
+    hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
+    hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
+    PGOCHK(g, hipEventRecord(g->ev1, g->stream));
+    PGOCHK(g, hipGetLastError());
+    double h = 0.0;
+    PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    *half_chi2 = h;
+    g->candidate_pending = true;
+    if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
     return LAMA_HIP_OK;
 }
 

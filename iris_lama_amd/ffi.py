@@ -71,6 +71,7 @@ HIP_SYMBOLS = [
     "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
     "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
     "lama_hip_match_solve_batch",
+    "lama_hip_pgo_solve_pcg", "lama_hip_pgo_try_solved_step",
 ]
 
 _hip = None
@@ -207,6 +208,8 @@ def _bind_hip(L):
             L.lama_hip_pgo_linearize_system.argtypes = [vp, vp, vp, vp, vp, vp]
             L.lama_hip_pgo_try_step.argtypes = [vp, vp, vp, vp]
             L.lama_hip_pgo_accept.argtypes = [vp]
+            L.lama_hip_pgo_solve_pcg.argtypes = [vp, C.c_double, C.c_double, u32, u32, vp, vp, vp, vp, vp, vp]
+            L.lama_hip_pgo_try_solved_step.argtypes = [vp, vp, vp]
         for s in HIP_SYMBOLS:
             if s.startswith("lama_hip_pgo_") and not has_pgo:
                 continue
@@ -632,7 +635,7 @@ HOST_SYMBOLS = [
     "lama_sdm_write", "lama_sdm_read", "lama_sdm_image", "lama_sdm_export_png", "lama_dm_build", "lama_dm_build_fetch",
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
-    "lama_pgo_optimize",
+    "lama_pgo_optimize", "lama_pgo_optimize_with",
     "lama_mapbuilder_default_options", "lama_mapbuilder_create", "lama_mapbuilder_destroy", "lama_mapbuilder_last_error",
     "lama_mapbuilder_engine_origin", "lama_mapbuilder_device_context", "lama_mapbuilder_add", "lama_mapbuilder_set_pose",
     "lama_mapbuilder_set_poses", "lama_mapbuilder_build", "lama_mapbuilder_reset", "lama_mapbuilder_occupied_cells",
@@ -693,6 +696,7 @@ def _bind_host(L):
         "lama_sdm_export_png": (i32, [i32, d, u32, u32, vp, vp, vp, C.c_char_p]),
         "lama_dm_build": (C.c_int64, [vp, C.c_uint64, u32, vp]), "lama_dm_build_fetch": (i32, [vp, vp, vp]),
         "lama_pgo_optimize": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, u32, vp, i32]),
+        "lama_pgo_optimize_with": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp, i32]),
         "lama_mapbuilder_default_options": (None, [vp]), "lama_mapbuilder_create": (vp, [vp, vp, i32]), "lama_mapbuilder_destroy": (None, [vp]),
         "lama_mapbuilder_last_error": (C.c_char_p, [vp]), "lama_mapbuilder_engine_origin": (C.c_char_p, [vp]),
         "lama_mapbuilder_device_context": (vp, [vp]), "lama_mapbuilder_add": (C.c_int64, [vp, vp, u32, vp, vp, vp]),
@@ -1329,6 +1333,28 @@ class PoseGraph:
         """The candidate of the last try_step becomes the current state; LamaError when none is pending."""
         self._check(self.L.lama_hip_pgo_accept(self.h))
 
+    def solve_pcg(self, lam, rel_tol=1e-10, max_iterations=None, batch=0, want_dx=True):
+        """(H + lam diag(H)) dx = b of the last linearize_system, solved on the device by block-Jacobi PCG (lama_hip_pgo_solve_pcg).
+        max_iterations None: max(100, 6 N).  -> dict(dx [N,3] or None, iterations, rel_residual_sq, outcome (PCG_CONVERGED / PCG_CAP /
+        PCG_BREAKDOWN), model_decrease, kernel_ms); the solution stays on the device for try_solved_step."""
+        dx = np.zeros((self.N, 3)) if want_dx else None
+        it, oc = C.c_uint32(0), C.c_int32(-1)
+        rel, model, ms = C.c_double(0), C.c_double(0), C.c_double(0)
+        cap = max(100, 6 * self.N) if max_iterations is None else int(max_iterations)
+        self._check(self.L.lama_hip_pgo_solve_pcg(self.h, float(lam), float(rel_tol), cap, int(batch), _p(dx), C.byref(it), C.byref(rel),
+                                                  C.byref(oc), C.byref(model), C.byref(ms)))
+        return {"dx": dx, "iterations": it.value, "rel_residual_sq": rel.value, "outcome": oc.value, "model_decrease": model.value,
+                "kernel_ms": ms.value}
+
+    def try_solved_step(self):
+        """try_step with the solution solve_pcg left on the device -> (0.5 * chi2 at the candidate, kernel_ms)."""
+        half, ms = C.c_double(0), C.c_double(0)
+        self._check(self.L.lama_hip_pgo_try_solved_step(self.h, C.byref(half), C.byref(ms)))
+        return half.value, ms.value
+
+
+PCG_CONVERGED, PCG_CAP, PCG_BREAKDOWN = 0, 1, 2          # include/lama_hip.h, LAMA_HIP_PCG_*
+
 
 class PgoReport(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_uint32), ("tries", C.c_uint32),
@@ -1340,13 +1366,35 @@ class PgoReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PgoOptions(C.Structure):
+    """lama_pgo_options (include/lama_host.h)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("device", C.c_int32), ("linear_solver", C.c_int32), ("pcg_max_iterations", C.c_uint32),
+                ("pcg_rel_tol", C.c_double)]
+
+
+class PgoReport2(C.Structure):
+    """lama_pgo_report2 (include/lama_host.h): lama_pgo_report behind its own size, then the device solver's counters"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("status", C.c_int32), ("iterations", C.c_uint32), ("tries", C.c_uint32),
+                ("initial_error", C.c_double), ("final_error", C.c_double), ("nnz_L", C.c_uint64),
+                ("ms_device_linearize", C.c_double), ("ms_device_try", C.c_double), ("ms_analyze", C.c_double),
+                ("ms_factorize", C.c_double), ("ms_total", C.c_double),
+                ("pcg_iterations", C.c_uint64), ("pcg_max_iterations_seen", C.c_uint32), ("pcg_fallbacks", C.c_uint32),
+                ("ms_device_solve", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "struct_bytes"}
+
+
+PGO_SOLVERS = {"ldlt": 0, "pcg": 1}                      # lama::SimplePGO::LinearSolver
 PGO_STATUS = {0: "SUCCESS", 1: "MAX_ITERATION", 2: "ERROR_INCREASE", 3: "RANK_DEFICIENCY", 4: "INVALID", -1: "NOT_RUN"}
 
 
-def simple_pgo(nodes, edges=(), fixed=(), device=0):
+def simple_pgo(nodes, edges=(), fixed=(), device=0, solver=None, pcg_rel_tol=1e-10, pcg_max_iterations=0):
     """lama::SimplePGO::optimize (include/lama/simple_pgo.h) on the device.  nodes [n,4] {c, s, tx, ty} (node_list); edges: iterable of
-    (from, to, pose4) (edge_list); fixed: iterable of (index, pose4) (fixed_list).
-    -> (ok, poses [n,4], report dict with the try trace under "trace": 1 accepted, 0 rejected, 2 rank deficient)."""
+    (from, to, pose4) (edge_list); fixed: iterable of (index, pose4) (fixed_list).  solver: "ldlt" (the default: the sparse LDL^T on
+    the host) or "pcg" (the damped system solved on the device, lama_hip_pgo_solve_pcg; pcg_max_iterations 0: max(100, 6 n)).
+    -> (ok, poses [n,4], report dict with the try trace under "trace": 1 accepted, 0 rejected, 2 rank deficient; with "pcg" also
+    pcg_iterations, pcg_max_iterations_seen, pcg_fallbacks and ms_device_solve)."""
     nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 4)
     n = len(nodes)
     edges, fixed = list(edges), list(fixed)
@@ -1356,12 +1404,21 @@ def simple_pgo(nodes, edges=(), fixed=(), device=0):
     fx = np.array([f[0] for f in fixed], dtype=np.int32)
     f4 = np.ascontiguousarray(np.array([f[1] for f in fixed], dtype=np.float64).reshape(-1, 4))
     out = np.zeros((n, 4))
-    rep = PgoReport()
     cap = 1 << 16
     trace = np.zeros(cap, dtype=np.int8)
     err = C.create_string_buffer(512)
-    rc = _hostlib().lama_pgo_optimize(_p(nodes) if n else None, n, _p(ef), _p(et), _p(e4), len(edges), _p(fx), _p(f4), len(fixed),
-                                     device, _p(out) if n else None, C.byref(rep), _p(trace), cap, err, 512)
+    if solver is None or solver == "ldlt":
+        rep = PgoReport()
+        rc = _hostlib().lama_pgo_optimize(_p(nodes) if n else None, n, _p(ef), _p(et), _p(e4), len(edges), _p(fx), _p(f4), len(fixed),
+                                         device, _p(out) if n else None, C.byref(rep), _p(trace), cap, err, 512)
+    else:
+        if solver not in PGO_SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(PGO_SOLVERS)}, not {solver!r}")
+        opt = PgoOptions(C.sizeof(PgoOptions), device, PGO_SOLVERS[solver], int(pcg_max_iterations), float(pcg_rel_tol))
+        rep = PgoReport2()
+        rep.struct_bytes = C.sizeof(PgoReport2)
+        rc = _hostlib().lama_pgo_optimize_with(_p(nodes) if n else None, n, _p(ef), _p(et), _p(e4), len(edges), _p(fx), _p(f4), len(fixed),
+                                              C.byref(opt), _p(out) if n else None, C.byref(rep), _p(trace), cap, err, 512)
     if rc < 0:
         raise LamaError(err.value.decode())
     r = rep.as_dict()

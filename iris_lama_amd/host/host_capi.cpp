@@ -3,6 +3,7 @@
 #include "lama/match_surface_2d.h"
 #include "lama/nlls/solver.h"
 
+#include <algorithm>
 #include <cstring>
 #include <exception>
 #include <stdexcept>
@@ -802,6 +803,48 @@ int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from
             report->initial_error = r.initial_error; report->final_error = r.final_error; report->nnz_L = r.nnz_L;
             report->ms_device_linearize = r.ms_device_linearize; report->ms_device_try = r.ms_device_try;
             report->ms_analyze = r.ms_analyze; report->ms_factorize = r.ms_factorize; report->ms_total = r.ms_total;
+        }
+        if (trace) for (size_t q = 0; q < p.report.trace.size() && q < trace_cap; ++q) trace[q] = p.report.trace[q];
+        return ok ? 1 : 0;
+    } catch (const std::exception& e) {
+        if (err && errcap > 0) { std::strncpy(err, e.what(), (size_t)errcap - 1); err[errcap - 1] = 0; }
+        return -1;
+    }
+}
+
+int lama_pgo_optimize_with(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4,
+                           uint32_t ne, const int32_t* fixed_idx, const double* fixed4, uint32_t nf, const lama_pgo_options* options,
+                           double* out4, lama_pgo_report2* report, int8_t* trace, uint32_t trace_cap, char* err, int errcap)
+{
+    try {
+        lama_pgo_options o;
+        std::memset(&o, 0, sizeof(o));
+        o.pcg_rel_tol = SimplePGO().pcg_rel_tol;
+        if (options) std::memcpy(&o, options, std::min<size_t>(options->struct_bytes, sizeof(o)));
+        SimplePGO p;
+        p.device = o.device;
+        if (o.linear_solver != SimplePGO::HostLDLT && o.linear_solver != SimplePGO::DevicePCG)
+            throw std::invalid_argument("lama_pgo_optimize_with: linear_solver must be 0 (host LDL^T) or 1 (device PCG)");
+        p.linear_solver = (SimplePGO::LinearSolver)o.linear_solver;
+        p.pcg_rel_tol = o.pcg_rel_tol;
+        p.pcg_max_iterations = o.pcg_max_iterations;
+        for (uint32_t i = 0; i < n; ++i) p.node_list.push_back(Pose2D(SE2d::fromArray(nodes4 + 4 * i)));
+        for (uint32_t k = 0; k < ne; ++k) p.edge_list.push_back({edge_from[k], {edge_to[k], Pose2D(SE2d::fromArray(edge4 + 4 * k))}});
+        for (uint32_t k = 0; k < nf; ++k) p.fixed_list.push_back({fixed_idx[k], Pose2D(SE2d::fromArray(fixed4 + 4 * k))});
+        const bool ok = p.optimize();
+        if (out4) for (uint32_t i = 0; i < n; ++i) p.node_list[i].state.toArray(out4 + 4 * i);
+        if (report) {
+            const SimplePGO::Report& r = p.report;
+            lama_pgo_report2 f;
+            std::memset(&f, 0, sizeof(f));
+            f.struct_bytes = report->struct_bytes;
+            f.status = r.status; f.iterations = r.iterations; f.tries = r.tries;
+            f.initial_error = r.initial_error; f.final_error = r.final_error; f.nnz_L = r.nnz_L;
+            f.ms_device_linearize = r.ms_device_linearize; f.ms_device_try = r.ms_device_try;
+            f.ms_analyze = r.ms_analyze; f.ms_factorize = r.ms_factorize; f.ms_total = r.ms_total;
+            f.pcg_iterations = r.pcg_iterations; f.pcg_max_iterations_seen = r.pcg_max_iterations_seen;
+            f.pcg_fallbacks = r.pcg_fallbacks; f.ms_device_solve = r.ms_device_solve;
+            std::memcpy(report, &f, std::min<size_t>(report->struct_bytes, sizeof(f)));
         }
         if (trace) for (size_t q = 0; q < p.report.trace.size() && q < trace_cap; ++q) trace[q] = p.report.trace[q];
         return ok ? 1 : 0;

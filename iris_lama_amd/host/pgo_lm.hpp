@@ -9,12 +9,17 @@
 //   one try           :160-262 (gain ratio, NaN = rejection), damping :265-318 + :369-374 (H_ii += (lambda - lambda_last) diag_i,
 //                     incremental within one iteration), lambda rules :321-333
 //   linear solver     linear/SparseCholesky.cpp (analysed once per optimize, factorised per try, NumericalIssue -> RANK_DEFICIENCY)
+//
+// Not in the reference: LmParams::linear_solver = SOLVER_DEVICE_PCG solves the damped system behind the interface (System::solvePcg,
+// the device's block-Jacobi conjugate gradient) and forms the gain ratio from the model decrease it returns; nothing is analysed or
+// factorised unless a solve reaches its iteration cap, in which case that try goes to the LDL^T below.
 #pragma once
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "block_ldlt.hpp"
@@ -40,13 +45,32 @@ struct System {
     virtual double tryStep(const double* dx, double* device_ms) = 0;
     // the candidate becomes the current state
     virtual void accept() = 0;
+    // ---- SOLVER_DEVICE_PCG only (an implementation without them cannot be asked for that solver)
+    // (H + lambda diag) dx = b of the last linearize(), solved behind the interface; the solution stays there.  outcome: PcgOutcome;
+    // model_decrease = 0.5 dx . (lambda diag dx + b)
+    virtual void solvePcg(double /*lambda*/, double /*rel_tol*/, uint32_t /*max_iterations*/, uint32_t* /*iterations*/, int32_t* /*outcome*/,
+                          double* /*model_decrease*/, double* /*device_ms*/)
+    {
+        throw std::runtime_error("lama::pgo::System: this linearisation has no device solver (solvePcg not supported)");
+    }
+    // tryStep with that solution
+    virtual double trySolvedStep(double* /*device_ms*/)
+    {
+        throw std::runtime_error("lama::pgo::System: this linearisation has no device solver (trySolvedStep not supported)");
+    }
 };
+
+enum LinearSolverKind : int32_t { SOLVER_HOST_LDLT = 0, SOLVER_DEVICE_PCG = 1 };
+enum PcgOutcome : int32_t { PCG_CONVERGED = 0, PCG_CAP = 1, PCG_BREAKDOWN = 2 };     // LAMA_HIP_PCG_* (include/lama_hip.h)
 
 struct LmParams {
     uint32_t max_iterations = 100;
     double min_rel_err_decrease = 1e-5, min_abs_err_decrease = 1e-5;
     double lambda_init = 1e-5, lambda_increase_factor_init = 2.0, lambda_increase_factor_update = 2.0;
     double lambda_decrease_factor_min = 1.0 / 3.0, lambda_min = 1e-20, lambda_max = 1e10, gain_ratio_thresh = 1e-3;
+    int32_t linear_solver = SOLVER_HOST_LDLT;
+    double pcg_rel_tol = 1e-10;
+    uint32_t pcg_max_iterations = 0;                            // 0: max(100, 6 N)
 };
 
 struct LmResult {
@@ -58,6 +82,10 @@ struct LmResult {
     double ms_analyze = 0.0, ms_factorize = 0.0;              // host: ordering + symbolic, numeric factorisation + solve
     double ms_total = 0.0;
     std::vector<int8_t> trace;                                 // TryOutcome per try
+    // SOLVER_DEVICE_PCG
+    uint64_t pcg_iterations = 0;                               // summed over the tries
+    uint32_t pcg_max_iterations_seen = 0, pcg_fallbacks = 0;   // the longest solve; tries that hit the cap and went to the LDL^T
+    double ms_device_solve = 0.0;
 };
 
 inline double msSince(std::chrono::steady_clock::time_point t0)
@@ -74,12 +102,22 @@ inline LmResult levenbergMarquardt(System& sys, const LmParams& prm = LmParams()
     std::vector<int32_t> row_ptr, cols;
     sys.pattern(row_ptr, cols);
     const size_t nnzb = cols.size();
+    const bool pcg = prm.linear_solver == SOLVER_DEVICE_PCG;
+    const uint32_t pcg_cap = prm.pcg_max_iterations ? prm.pcg_max_iterations : std::max<uint32_t>(100u, 6u * N);
     BlockLDLT ldlt;
+    bool analyzed = false;
     auto t0 = clock::now();
-    ldlt.analyze((int32_t)N, row_ptr.data(), cols.data(), natural_order);
-    res.ms_analyze = msSince(t0);
-    res.nnz_L = ldlt.nnzL();
-    std::vector<double> blocks(9 * nnzb), H(9 * nnzb), b(3 * (size_t)N), diag(3 * (size_t)N), dx(3 * (size_t)N);
+    const auto analyze = [&]() {                               // (up front for the LDL^T; on first need for a fallback try of the PCG)
+        t0 = clock::now();
+        ldlt.analyze((int32_t)N, row_ptr.data(), cols.data(), natural_order);
+        res.ms_analyze = msSince(t0);
+        res.nnz_L = ldlt.nnzL();
+        analyzed = true;
+    };
+    if (!pcg) analyze();
+    std::vector<double> blocks, H, b, diag, dx;
+    const auto host_arrays = [&]() { blocks.resize(9 * nnzb); H.resize(9 * nnzb); b.resize(3 * (size_t)N); diag.resize(3 * (size_t)N); dx.resize(3 * (size_t)N); };
+    if (!pcg) host_arrays();
 
     double lambda = prm.lambda_init, increase = prm.lambda_increase_factor_init;
     double last_err = 0.0;
@@ -88,15 +126,62 @@ inline LmResult levenbergMarquardt(System& sys, const LmParams& prm = LmParams()
     while (res.iterations < prm.max_iterations) {
         // ---- iterate(): linearise once
         double ms = 0.0;
-        const double lin_err = sys.linearize(blocks.data(), b.data(), diag.data(), &ms);
+        const double lin_err = pcg ? sys.linearize(nullptr, nullptr, nullptr, &ms) : sys.linearize(blocks.data(), b.data(), diag.data(), &ms);
         res.ms_device_linearize += ms;
         if (!have_err) { last_err = lin_err; res.initial_error = lin_err; have_err = true; }   // 0.5 errorSquaredNorm(init)
         const double values_curr_err = last_err;
-        H = blocks;
+        if (!pcg) H = blocks;
+        bool on_host = !pcg;                                       // this iteration's system is in blocks / b / diag / H
         double last_lambda = 0.0;
         Status it_status = ERROR_INCREASE;
         double new_err = 0.0;
         while (lambda < prm.lambda_max) {
+            if (pcg) {
+                uint32_t its = 0;
+                int32_t outcome = PCG_BREAKDOWN;
+                double model = 0.0;
+                ms = 0.0;
+                sys.solvePcg(lambda, prm.pcg_rel_tol, pcg_cap, &its, &outcome, &model, &ms);
+                res.ms_device_solve += ms;
+                res.pcg_iterations += its;
+                res.pcg_max_iterations_seen = std::max(res.pcg_max_iterations_seen, its);
+                if (outcome != PCG_CAP) {
+                    ++res.tries;
+                    bool accepted = false;
+                    if (outcome == PCG_CONVERGED) {
+                        ms = 0.0;
+                        const double err_upd = sys.trySolvedStep(&ms);
+                        res.ms_device_try += ms;
+                        const double ratio = (values_curr_err - err_upd) / model;
+                        if (ratio > prm.gain_ratio_thresh) {            // (a NaN ratio is a rejection)
+                            sys.accept();
+                            new_err = err_upd;
+                            accepted = true;
+                            lambda *= std::max(prm.lambda_decrease_factor_min, 1.0 - std::pow(2.0 * ratio - 1.0, 3.0));
+                            lambda = std::max(prm.lambda_min, lambda);
+                            increase = prm.lambda_increase_factor_init;
+                        }
+                    }
+                    res.trace.push_back(accepted ? TRY_ACCEPTED : outcome == PCG_CONVERGED ? TRY_REJECTED : TRY_RANK_DEFICIENT);
+                    if (accepted) { it_status = SUCCESS; break; }
+                    lambda *= increase;
+                    increase *= prm.lambda_increase_factor_update;
+                    continue;
+                }
+                // the cap: this try is the host's.  The system is downloaded once per iteration (the same kernels at the same state
+                // give the same numbers), the ordering is made on first need.
+                ++res.pcg_fallbacks;
+                if (!analyzed) analyze();
+                if (!on_host) {
+                    host_arrays();
+                    ms = 0.0;
+                    sys.linearize(blocks.data(), b.data(), diag.data(), &ms);
+                    res.ms_device_linearize += ms;
+                    H = blocks;
+                    last_lambda = 0.0;
+                    on_host = true;
+                }
+            }
             // dumpLinearSystem_: H.diagonal() += (lambda - last_lambda) * hessian_diag
             const double dl = lambda - last_lambda;
             for (uint32_t v = 0; v < N; ++v) {

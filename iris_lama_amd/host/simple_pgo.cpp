@@ -1,5 +1,6 @@
 // simple_pgo.cpp -- lama::SimplePGO::optimize (include/lama/simple_pgo.h): the reference's graph (pgo_graph.hpp), minisam's
-// Levenberg-Marquardt (pgo_lm.hpp) over the device-resident linearisation of lama_hip_pgo_* (include/lama_hip.h).
+// Levenberg-Marquardt (pgo_lm.hpp) over the device-resident linearisation of lama_hip_pgo_* (include/lama_hip.h).  With
+// linear_solver = DevicePCG the damped system is solved on the device too (lama_hip_pgo_solve_pcg, _try_solved_step).
 #include <dlfcn.h>
 
 #include <stdexcept>
@@ -25,10 +26,13 @@ struct PgoApi {
     decltype(&lama_hip_pgo_linearize_system) linearize_system = nullptr;
     decltype(&lama_hip_pgo_try_step) try_step = nullptr;
     decltype(&lama_hip_pgo_accept) accept = nullptr;
+    // optional: only linear_solver = DevicePCG needs them (an implementation of the C-ABI without them still serves the default solver)
+    decltype(&lama_hip_pgo_solve_pcg) solve_pcg = nullptr;
+    decltype(&lama_hip_pgo_try_solved_step) try_solved_step = nullptr;
     std::shared_ptr<HipEngine> engine;
 };
 
-PgoApi resolvePgoApi()
+PgoApi resolvePgoApi(bool need_pcg)
 {
     PgoApi a;
     a.engine = defaultEngine();
@@ -46,6 +50,13 @@ PgoApi resolvePgoApi()
     RESOLVE(try_step, lama_hip_pgo_try_step)
     RESOLVE(accept, lama_hip_pgo_accept)
 #undef RESOLVE
+#define OPTIONAL(field, sym)                                                                                                 \
+    a.field = reinterpret_cast<decltype(a.field)>(a.engine->dl ? dlsym(a.engine->dl, #sym) : nullptr);                     \
+    if (!a.field && need_pcg) throw std::runtime_error(std::string("lama::SimplePGO: symbol " #sym " missing in ") + a.engine->origin + \
+                                                       " (linear_solver = DevicePCG needs it; there is no CPU fallback)");
+    OPTIONAL(solve_pcg, lama_hip_pgo_solve_pcg)
+    OPTIONAL(try_solved_step, lama_hip_pgo_try_solved_step)
+#undef OPTIONAL
     return a;
 }
 
@@ -86,6 +97,17 @@ public:
         return half;
     }
     void accept() override { check(api_.accept(h_)); }
+    void solvePcg(double lambda, double rel_tol, uint32_t max_iterations, uint32_t* iterations, int32_t* outcome, double* model_decrease,
+                  double* device_ms) override
+    {
+        check(api_.solve_pcg(h_, lambda, rel_tol, max_iterations, 0, nullptr, iterations, nullptr, outcome, model_decrease, device_ms));
+    }
+    double trySolvedStep(double* device_ms) override
+    {
+        double half = 0.0;
+        check(api_.try_solved_step(h_, &half, device_ms));
+        return half;
+    }
     void poses(double* out4) { check(api_.get_poses(h_, out4)); }
 
 private:
@@ -105,9 +127,13 @@ bool SimplePGO::optimize()
     report = Report();
     pgo::Graph g;
     if (!pgo::buildGraph(*this, g)) return false;
-    const PgoApi api = resolvePgoApi();
+    const PgoApi api = resolvePgoApi(linear_solver == DevicePCG);
     DeviceSystem sys(api, device, g);
-    const pgo::LmResult r = pgo::levenbergMarquardt(sys);
+    pgo::LmParams prm;
+    prm.linear_solver = linear_solver == DevicePCG ? pgo::SOLVER_DEVICE_PCG : pgo::SOLVER_HOST_LDLT;
+    prm.pcg_rel_tol = pcg_rel_tol;
+    prm.pcg_max_iterations = pcg_max_iterations;
+    const pgo::LmResult r = pgo::levenbergMarquardt(sys, prm);
     report.status = r.status;
     report.iterations = r.iterations;
     report.tries = r.tries;
@@ -119,6 +145,10 @@ bool SimplePGO::optimize()
     report.ms_analyze = r.ms_analyze;
     report.ms_factorize = r.ms_factorize;
     report.ms_total = r.ms_total;
+    report.pcg_iterations = r.pcg_iterations;
+    report.pcg_max_iterations_seen = r.pcg_max_iterations_seen;
+    report.pcg_fallbacks = r.pcg_fallbacks;
+    report.ms_device_solve = r.ms_device_solve;
     report.trace.assign(r.trace.begin(), r.trace.end());
     if (r.status != pgo::SUCCESS) return false;
     std::vector<double> out(4 * (size_t)g.N);
