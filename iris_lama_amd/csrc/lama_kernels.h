@@ -545,10 +545,13 @@ __global__ __launch_bounds__(64) void k_sample_likelihood(DevParams prm, int par
 // Exactness contract: the counters AND the order of add/remove obstacle events AND the order in which the
 // brushfire pops equal-priority cells are those of the reference's sequential code, so the resulting maps are
 // bit-identical (cells, obstacle offsets, flags, masks, patch sets).
-//   * cells of one ray are distinct => plain RMW, no atomics; the closed form
-//     steps_j(t) = floor((2 t |d_j| + n) / (2 n)) replays Map::computeRay (src/sdm/map.cpp:198-227);
-//   * the beam's hit (-> lower queue) and its ray cells (-> raise queue) touch distinct cells and distinct
+//   * the (x, y) cells of one ray are distinct while x or y sets the step count n => plain RMW, no atomics; the
+//     closed form steps_j(t) = floor((2 t |d_j| + n) / (2 n)) replays Map::computeRay (src/sdm/map.cpp:198-227);
+//   * the beam's hit (-> lower queue) and its ray cells (-> raise queue) then touch distinct cells and distinct
 //     queues, so they share one 64-lane section (lane 0 of the first section is the hit);
+//   * a beam whose z delta sets n (a steep beam of a tilted sensor) stays in an (x, y) cell for several steps and
+//     ends with free visits of its own hit cell: the lanes of a section that share a cell take turns in step
+//     order (one round per repetition, tests/_ray_checks.py: the third axis);
 //   * events are appended in (beam, step) order via ballot ranks (priority 0 => libstdc++ push_heap leaves
 //     them at the end of the heap array);
 //   * the brushfire pops one cell at a time through the libstdc++-exact heap of lama_heap.h (LDS resident);
@@ -684,6 +687,8 @@ __global__ __launch_bounds__(UM_BLOCK) void k_raycast(DevParams prm, const doubl
         // q = (num * M) >> 42 with M = floor(2^42 / (2n)) + 1 is exact (num * 2n < 2^42); one division per beam.
         const uint64_t magic = (1ull << 42) / (uint64_t)(2 * (nn > 0 ? nn : 1)) + 1ull;
         const uint32_t ua0 = (uint32_t)a0, ua1 = (uint32_t)a1, un = (uint32_t)nn;
+        // the z delta sets n: consecutive steps share an (x, y) cell, the last ones lie in the hit cell (wave-uniform)
+        const bool zdom = a2 > a0 && a2 > a1;
 
         // sections of 64 lanes over t = 0 (the hit cell, :493-498) , 1 .. steps (the free cells, :500-504)
         for (int base = 0; base <= steps; base += 64) {
@@ -704,56 +709,74 @@ __global__ __launch_bounds__(UM_BLOCK) void k_raycast(DevParams prm, const doubl
             const uint32_t pidx = (ry >> 5) * prm.W + (rx >> 5);
             const uint32_t ci = (rx & 31u) | ((ry & 31u) << 5);
             const int slot = coop_slot(occ_dc, occ_dir, occ_count, (int)pv.occ_cap, want, pidx, ERR_OCC_CAP, prm.err);
-            bool changed = false;
-            if (want && slot >= 0) {
-                uint32_t* cell = occ + (size_t)slot * 1024 + ci;
-                const uint32_t v = *cell;
-                uint32_t o = v & 0xFFFFu, vis = v >> 16;
-                if (prm.occ_policy == 1) {
-                    // ProbabilisticOccupancyMap (probabilistic_occupancy_map.cpp:82-107): float log-odds cell, double parameters,
-                    // occ_thresh = 0; every get() turns the mask bit on
-                    const float lp = __uint_as_float(v);
-                    float np_;
-                    if (is_hit) {
-                        const bool occupied = (double)lp > 0.0;
-                        np_ = (float)fmin((double)lp + prm.lo_hit, prm.lo_max);
-                        changed = !occupied && ((double)np_ > 0.0);
-                    } else {
-                        const bool was_free = (double)lp < 0.0;
-                        np_ = (float)fmax((double)lp + prm.lo_miss, prm.lo_min);
-                        changed = !was_free && ((double)np_ < 0.0);
-                    }
-                    *cell = __float_as_uint(np_);
-                    atomicOr((unsigned long long*)(occ_mask + (size_t)slot * 16 + (ci >> 6)), 1ull << (ci & 63));
-                } else {
-                if (is_hit) {                                               // setOccupied (frequency_occupancy_map.cpp:81-91)
-                    const bool occupied = vis != 0 && 4u * o > vis;         // prob > 0.25
-                    o = (o + 1) & 0xFFFFu; vis = (vis + 1) & 0xFFFFu;
-                    changed = !occupied && (vis != 0 && 4u * o > vis);
-                } else {                                                    // setFree (:65-74)
-                    const bool was_free = vis != 0 && 4u * o < vis;         // prob < 0.25
-                    vis = (vis + 1) & 0xFFFFu;
-                    changed = !was_free && (vis != 0 && 4u * o < vis);
+            // round of this lane's visit: how many earlier steps of the section visit the same cell (0 unless zdom)
+            int round = 0, rounds = 1;
+            if (zdom) {
+                const uint32_t key = (ry << 16) | rx;
+                for (int j = 0; j < 63; ++j) {
+                    const uint32_t kj = (uint32_t)__shfl((int)key, j, 64);
+                    const int wj = __shfl(want ? 1 : 0, j, 64);
+                    if (j < lane && wj && kj == key) ++round;
                 }
-                *cell = o | (vis << 16);
-                // Container mask bit of an occupancy cell == "visited != 0"; only a uint16 wrap needs the plane
-                if (vis == 0) atomicOr((unsigned long long*)(occ_mask + (size_t)slot * 16 + (ci >> 6)), 1ull << (ci & 63));
-                }
+                int mx = want ? round : 0;
+                for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(mx, off, 64); mx = o > mx ? o : mx; }
+                rounds = mx + 1;
             }
-            const int dslot = coop_slot(dm_dc, dm_dir, dm_count, (int)pv.dm_cap, changed, pidx, ERR_DM_CAP, prm.err);
             bool push = false;
-            if (changed && dslot >= 0) {
-                const uint64_t bit = 1ull << (ci & 63);
-                uint64_t* w = dm_mask + (size_t)dslot * 16 + (ci >> 6);
-                if (!(*w & bit)) atomicOr((unsigned long long*)w, (unsigned long long)bit);
-                const uint32_t di = (uint32_t)dslot * 1024u + ci;
-                const sv_t s = dm_sv[di];
-                const bool is_obstacle = (s & SV_VALID) && (s & SV_SQMASK) == 0;
-                if (is_hit) {                                               // addObstacle (dynamic_distance_map.cpp:212-226)
-                    if (!is_obstacle) { dm_sv[di] = (sv_t)(SV_VALID | SV_QUEUED); dm_obs[di] = 0; push = true; }
-                } else {                                                    // removeObstacle (:228-242)
-                    if (is_obstacle) { dm_sv[di] = SV_QUEUED; dm_obs[di] = 0; push = true; }
+            for (int r = 0; r < rounds; ++r) {
+                const bool mine = want && round == r;
+                bool changed = false;
+                if (mine && slot >= 0) {
+                    uint32_t* cell = occ + (size_t)slot * 1024 + ci;
+                    const uint32_t v = *cell;
+                    uint32_t o = v & 0xFFFFu, vis = v >> 16;
+                    if (prm.occ_policy == 1) {
+                        // ProbabilisticOccupancyMap (probabilistic_occupancy_map.cpp:82-107): float log-odds cell, double parameters,
+                        // occ_thresh = 0; every get() turns the mask bit on
+                        const float lp = __uint_as_float(v);
+                        float np_;
+                        if (is_hit) {
+                            const bool occupied = (double)lp > 0.0;
+                            np_ = (float)fmin((double)lp + prm.lo_hit, prm.lo_max);
+                            changed = !occupied && ((double)np_ > 0.0);
+                        } else {
+                            const bool was_free = (double)lp < 0.0;
+                            np_ = (float)fmax((double)lp + prm.lo_miss, prm.lo_min);
+                            changed = !was_free && ((double)np_ < 0.0);
+                        }
+                        *cell = __float_as_uint(np_);
+                        atomicOr((unsigned long long*)(occ_mask + (size_t)slot * 16 + (ci >> 6)), 1ull << (ci & 63));
+                    } else {
+                    if (is_hit) {                                               // setOccupied (frequency_occupancy_map.cpp:81-91)
+                        const bool occupied = vis != 0 && 4u * o > vis;         // prob > 0.25
+                        o = (o + 1) & 0xFFFFu; vis = (vis + 1) & 0xFFFFu;
+                        changed = !occupied && (vis != 0 && 4u * o > vis);
+                    } else {                                                    // setFree (:65-74)
+                        const bool was_free = vis != 0 && 4u * o < vis;         // prob < 0.25
+                        vis = (vis + 1) & 0xFFFFu;
+                        changed = !was_free && (vis != 0 && 4u * o < vis);
+                    }
+                    *cell = o | (vis << 16);
+                    // Container mask bit of an occupancy cell == "visited != 0"; only a uint16 wrap needs the plane
+                    if (vis == 0) atomicOr((unsigned long long*)(occ_mask + (size_t)slot * 16 + (ci >> 6)), 1ull << (ci & 63));
+                    }
                 }
+                const int dslot = coop_slot(dm_dc, dm_dir, dm_count, (int)pv.dm_cap, changed, pidx, ERR_DM_CAP, prm.err);
+                if (changed && dslot >= 0) {
+                    const uint64_t bit = 1ull << (ci & 63);
+                    uint64_t* w = dm_mask + (size_t)dslot * 16 + (ci >> 6);
+                    if (!(*w & bit)) atomicOr((unsigned long long*)w, (unsigned long long)bit);
+                    const uint32_t di = (uint32_t)dslot * 1024u + ci;
+                    const sv_t s = dm_sv[di];
+                    const bool is_obstacle = (s & SV_VALID) && (s & SV_SQMASK) == 0;
+                    if (is_hit) {                                               // addObstacle (dynamic_distance_map.cpp:212-226)
+                        if (!is_obstacle) { dm_sv[di] = (sv_t)(SV_VALID | SV_QUEUED); dm_obs[di] = 0; push = true; }
+                    } else {                                                    // removeObstacle (:228-242)
+                        if (is_obstacle) { dm_sv[di] = SV_QUEUED; dm_obs[di] = 0; push = true; }
+                    }
+                }
+                // the next round's lanes read what this round's lanes stored (same wave: ordering only)
+                if (zdom) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             }
             const unsigned long long pm = __ballot(push);
             if (pm) {

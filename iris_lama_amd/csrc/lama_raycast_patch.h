@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_occ_reverse_dir(DevParams prm, int firs
     const int scx = (int)(w2m(prm, uload_f64(tfs + 12 * (size_t)p + 9)) - prm.wx0), scy = (int)(w2m(prm, uload_f64(tfs + 12 * (size_t)p + 10)) - prm.wy0);
     const int bx0 = imax((scx - reach_cells) >> 5, 0), bx1 = imin((scx + reach_cells) >> 5, (int)W - 1);
     const int by0 = imax((scy - reach_cells) >> 5, 0), by1 = imin((scy + reach_cells) >> 5, (int)W - 1);
-    // the marked region: that box grown by guard_r, clipped to the window; too large for the bitmap -> no bound (as guard_off)
+    // the marked region: that box grown by guard_r, clipped to the window; too large for the bitmap -> counted in tiles below
     const int mx0 = imax(bx0 - r, 0), my0 = imax(by0 - r, 0), mw = imin(bx1 + r, (int)W - 1) - mx0 + 1, mh = imin(by1 + r, (int)W - 1) - my0 + 1;
     const bool bounded = mw > 0 && mh > 0 && mw <= RD_MARK_SIDE && mh <= RD_MARK_SIDE;
     const uint32_t nbits = bounded ? (uint32_t)(mw * mh) : 0u;
@@ -252,9 +252,47 @@ __global__ __launch_bounds__(256) void k_occ_reverse_dir(DevParams prm, int firs
     }
     if (need) atomicAdd(&need_s, need);
     __syncthreads();
+    // A marked region wider than the bitmap (a scan that reaches further than ~200 m: one ray of 8191 cells crosses 256 patches and
+    // makes a distance-map patch of every one it enters first) is counted tile by tile, each tile with a directory pass of its own
+    // over the rows that can mark it.  Without a bound such an update ran out of distance-map patches AFTER cells were modified.
+    const bool tiled = !bounded && mw > 0 && mh > 0;
+    if (tiled) {
+        for (int ty = my0; ty < my0 + mh; ty += RD_MARK_SIDE)
+            for (int tx = mx0; tx < mx0 + mw; tx += RD_MARK_SIDE) {
+                const int tw = imin(RD_MARK_SIDE, mx0 + mw - tx), th = imin(RD_MARK_SIDE, my0 + mh - ty);
+                const uint32_t tbits = (uint32_t)(tw * th);
+                for (uint32_t i = tid; i < (tbits + 31u) / 32u; i += 256u) mark[i] = 0;
+                __syncthreads();
+                const int ry0 = imax(ty - r, by0), ry1 = imin(ty + th - 1 + r, by1);       // occupancy patches in reach that can mark the tile
+                const int rx0 = imax(tx - r, bx0), rx1 = imin(tx + tw - 1 + r, bx1);
+                const int nx = rx1 - rx0 + 1, nrow = ry1 - ry0 + 1;
+                for (int i = tid; nx > 0 && i < nx * nrow; i += 256) {
+                    const int ox = rx0 + i % nx, oy = ry0 + i / nx;
+                    if (occ_dir[(uint32_t)oy * W + (uint32_t)ox] < 0) continue;
+                    for (int dy = -r; dy <= r; ++dy)
+                        for (int dx = -r; dx <= r; ++dx) {
+                            const int x = ox + dx - tx, y = oy + dy - ty;
+                            if ((uint32_t)x < (uint32_t)tw && (uint32_t)y < (uint32_t)th) { const uint32_t n = (uint32_t)y * (uint32_t)tw + (uint32_t)x; atomicOr(&mark[n >> 5], 1u << (n & 31u)); }
+                        }
+                }
+                __syncthreads();
+                uint32_t tneed = 0;
+                for (uint32_t i = tid; i < (tbits + 31u) / 32u; i += 256u) {
+                    uint32_t m = mark[i];
+                    while (m) {
+                        const uint32_t n = i * 32u + (uint32_t)(__ffs((int)m) - 1);
+                        const uint32_t wx = (uint32_t)tx + n % (uint32_t)tw, wy = (uint32_t)ty + n / (uint32_t)tw;
+                        if (dm_dir[wy * W + wx] < 0) ++tneed;
+                        m &= m - 1u;
+                    }
+                }
+                if (tneed) atomicAdd(&need_s, tneed);
+                __syncthreads();
+            }
+    }
     // (the bound itself is left for the host: a particle whose region is too small is grown by what it asks for -- guard[p])
-    if (tid == 0) prm.guard[p] = bounded ? need_s : 0u;
-    if (tid == 0 && bounded && !guard_off && (uint64_t)prm.counts[2 * p] + need_s > pv.dm_cap) atomicOr(prm.err, ERR_DM_CAP);
+    if (tid == 0) prm.guard[p] = (bounded || tiled) ? need_s : 0u;
+    if (tid == 0 && (bounded || tiled) && !guard_off && (uint64_t)prm.counts[2 * p] + need_s > pv.dm_cap) atomicOr(prm.err, ERR_DM_CAP);
 }
 
 // developer build (-DLAMA_PROFILE_RAY, tools/prof_ray.py): event counts and per-phase cycles of k_ray_patches, summed over the launch
