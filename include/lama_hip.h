@@ -327,8 +327,8 @@ int32_t lama_hip_blob_copy(lama_hip_ctx* dst_ctx, void* dst_device_buf, lama_hip
 
 /* SE2 pose-graph linearisation: the per-factor body and the accumulation of minisam's
  * linearzationLowerHessian (vendor/minisam/minisam/nonlinear/linearization.cpp:150-272,290-341) for PriorFactor<SE2d> /
- * BetweenFactor<SE2d> with DiagonalLoss, as built by SimplePGO::optimize (src/simple_pgo.cpp:48-105) and
- * GraphSlam2D::optimizePoseGraph (src/graph_slam2d.cpp:394-430).  The graph structure and measurements are uploaded once
+ * BetweenFactor<SE2d> with DiagonalLoss, as built by SimplePGO::optimize (src/simple_pgo.cpp:48-105) and -- with the robust
+ * losses of lama_hip_pgo_create_robust below -- GraphSlam2D::optimizePoseGraph (src/graph_slam2d.cpp:394-430).  The graph structure and measurements are uploaded once
  * (create), every Levenberg-Marquardt iteration calls linearize with the current poses {c, s, tx, ty}.  Outputs, dense 3x3
  * blocks row-major (the caller scatters them into its sparse lower Hessian and runs the Cholesky on the host):
  *   err   [F][3]  whitened error           Hoff [F][9]  J_i^T J_j of factor f (zero for a prior, fj = -1)
@@ -385,6 +385,30 @@ int32_t lama_hip_pgo_accept(lama_hip_pgo* g);
 int32_t lama_hip_pgo_solve_pcg(lama_hip_pgo* g, double lambda, double rel_tol, uint32_t max_iterations, uint32_t batch, double* dx,
                                uint32_t* iterations, double* rel_residual_sq, int32_t* outcome, double* model_decrease, double* kernel_ms);
 int32_t lama_hip_pgo_try_solved_step(lama_hip_pgo* g, double* half_chi2, double* kernel_ms);
+
+/* Per-factor robust losses, applied AFTER the diagonal whitening: minisam's ComposedLoss(DiagonalLoss, robust), and with
+ * sqrt_info = 1 the bare HuberLoss GraphSlam2D::optimizePoseGraph puts on its loop closures (src/graph_slam2d.cpp:266).  With e the
+ * whitened error and n = sqrt((e0 e0 + e1 e1) + e2 e2) (vendor/minisam/minisam/core/LossFunction.h:173,200-202,230-238):
+ *   HUBER  (param k): w = n < k ? 1 : k / |n|        CAUCHY (param k): w = k^2 / (k^2 + n^2)
+ *   DCS    (param c): w = n^2 > c ? (2 c / (c + n^2))^2 : 1
+ * The error and both whitened Jacobians are multiplied by sqrt(w) before any product is formed, so err, chi2 / half_chi2, Hdiag,
+ * Hoff, b and the assembled system of every call above are those of the robustly weighted error (Factor::weightedError), and
+ * try_step / try_solved_step return the error under the same weight.
+ *   create_robust  : lama_hip_pgo_create with loss_kind [F] (LAMA_HIP_PGO_LOSS_*) and loss_param [F]; loss_param is not read for a
+ *                    factor of kind NONE, and may be NULL when every kind is NONE.  loss_kind NULL is lama_hip_pgo_create.  A graph
+ *                    without a robust factor runs exactly the kernels lama_hip_pgo_create's runs.  LAMA_HIP_E_INVALID with nothing
+ *                    created: an unknown kind, or a robust factor whose parameter is not finite and > 0 --
+ *                    lama_hip_pgo_last_error(NULL) then names the factor (per thread, until the next create_robust).
+ *   factor_weights : w [F] (w, not its root) of every factor in the last linearize / linearize_system, 1 for a loss-free factor;
+ *                    LAMA_HIP_E_STATE before the first linearisation. */
+#define LAMA_HIP_PGO_LOSS_NONE 0
+#define LAMA_HIP_PGO_LOSS_HUBER 1
+#define LAMA_HIP_PGO_LOSS_CAUCHY 2
+#define LAMA_HIP_PGO_LOSS_DCS 3
+int32_t lama_hip_pgo_create_robust(int32_t device, uint32_t num_poses, const int32_t* fi, const int32_t* fj, const double* meas4,
+                                   const double* sqrt_info3, const int32_t* loss_kind, const double* loss_param, uint32_t num_factors,
+                                   lama_hip_pgo** out);
+int32_t lama_hip_pgo_factor_weights(lama_hip_pgo* g, double* w);
 
 /* Accumulated per-kernel device time (hipEvent elapsed, on the stream the kernels run on) and work
  * counters since the last reset; valid when cfg.profile != 0. */

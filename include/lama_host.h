@@ -264,6 +264,15 @@ typedef struct lama_pgo_report2 {
 int lama_pgo_optimize_with(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4,
                            uint32_t ne, const int32_t* fixed_idx, const double* fixed4, uint32_t nf, const lama_pgo_options* options,
                            double* out4, lama_pgo_report2* report, int8_t* trace, uint32_t trace_cap, char* err, int errcap);
+/* ---- lama::PoseGraph2D (include/lama/pose_graph_2d.h) flattened: nodes4 [n][4]; factor k < nf on nodes fi[k], fj[k] (fj = -1: a prior on
+ * fi[k]) with measurement meas4[k], sigmas3[k] and the loss loss_kind[k] (LAMA_HIP_PGO_LOSS_* of include/lama_hip.h: 0 none, 1 Huber,
+ * 2 Cauchy, 3 DCS) with parameter loss_param[k]; both loss arrays NULL: no losses.  Any other negative fj is an invalid index.  options NULL: the defaults.  Returns as
+ * lama_pgo_optimize_with; weights [nf] (may be NULL) receives lama::PoseGraph2D::weights when optimize() ran (1 or 0 returned with
+ * report.status != -1) and is left untouched otherwise. */
+int lama_pose_graph_optimize(const double* nodes4, uint32_t n, const int32_t* fi, const int32_t* fj, const double* meas4,
+                             const double* sigmas3, const int32_t* loss_kind, const double* loss_param, uint32_t nf,
+                             const lama_pgo_options* options, double* out4, double* weights, lama_pgo_report2* report, int8_t* trace,
+                             uint32_t trace_cap, char* err, int errcap);
 /* ---- lama::MapBuilder2D (include/lama/map_builder_2d.h), flattened: a map rebuilt from posed key scans ---- */
 typedef struct lama_mapbuilder lama_mapbuilder;
 typedef struct lama_mapbuilder_options {

@@ -1873,14 +1873,23 @@ struct lama_hip_pgo {
     DevBuf<PcgState> d_pcg;
     bool system_valid = false;             // d_blocks / d_b / d_diag are the system at d_poses (linearize_system since the state last changed)
     bool solution_valid = false;           // d_px solves that system (solve_pcg since)
+    // per-factor robust losses (lama_hip_pgo_create_robust): allocated only when a factor has one; without, the graph launches
+    // k_pgo_factors / k_pgo_error as lama_hip_pgo_create's does
+    bool robust = false;
+    bool linearized = false;               // a linearize / linearize_system has run: lama_hip_pgo_factor_weights has something to return
+    DevBuf<int32_t> d_loss_kind;
+    DevBuf<double> d_loss_param, d_weight;
 
     __attribute__((visibility("hidden"))) ~lama_hip_pgo() { (void)hipSetDevice(device); }     // (not exported: the C-ABI is)
 };
 
 #define PGOCHK(g, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (g)->error = std::string(#call) + ": " + hipGetErrorString(e_); return LAMA_HIP_E_HIP; } } while (0)
 
-int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const int32_t* fj, const double* meas4, const double* sqrt_info3,
-                            uint32_t F, lama_hip_pgo** out)
+static thread_local std::string g_pgo_create_error;     // why the last lama_hip_pgo_create_robust of this thread refused its losses
+
+// loss_kind / loss_param: NULL, or validated by the caller ([F] each)
+static int32_t pgo_create(int32_t device, uint32_t N, const int32_t* fi, const int32_t* fj, const double* meas4, const double* sqrt_info3,
+                          const int32_t* loss_kind, const double* loss_param, uint32_t F, lama_hip_pgo** out)
 {
     if (!out || !fi || !fj || !meas4 || !sqrt_info3 || N == 0 || F == 0) return LAMA_HIP_E_INVALID;
     *out = nullptr;
@@ -1945,13 +1954,69 @@ int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const
         hipMemcpy(p->d_tptr, tptr.data(), sizeof(int32_t) * (N + 1), hipMemcpyHostToDevice) ||
         (!tidx.empty() && hipMemcpy(p->d_tidx, tidx.data(), sizeof(int32_t) * tidx.size(), hipMemcpyHostToDevice)))
         return LAMA_HIP_E_HIP;
+    for (uint32_t k = 0; loss_kind && k < F; ++k) p->robust = p->robust || loss_kind[k] != LAMA_HIP_PGO_LOSS_NONE;
+    if (p->robust) {
+        std::vector<double> prm(F, 0.0);                                   // Cauchy: k2_ = k * k, formed once (LossFunction.h:162)
+        for (uint32_t k = 0; k < F; ++k)
+            if (loss_kind[k] != LAMA_HIP_PGO_LOSS_NONE) prm[k] = loss_kind[k] == LAMA_HIP_PGO_LOSS_CAUCHY ? loss_param[k] * loss_param[k] : loss_param[k];
+        if (p->d_loss_kind.alloc(F) || p->d_loss_param.alloc(F) || p->d_weight.alloc(F)) return LAMA_HIP_E_HIP;
+        if (hipMemcpy(p->d_loss_kind, loss_kind, sizeof(int32_t) * F, hipMemcpyHostToDevice) ||
+            hipMemcpy(p->d_loss_param, prm.data(), sizeof(double) * F, hipMemcpyHostToDevice))
+            return LAMA_HIP_E_HIP;
+    }
     *out = p.release();
     return LAMA_HIP_OK;
 }
 
+int32_t lama_hip_pgo_create(int32_t device, uint32_t N, const int32_t* fi, const int32_t* fj, const double* meas4, const double* sqrt_info3,
+                            uint32_t F, lama_hip_pgo** out)
+{
+    return pgo_create(device, N, fi, fj, meas4, sqrt_info3, nullptr, nullptr, F, out);
+}
+
+int32_t lama_hip_pgo_create_robust(int32_t device, uint32_t N, const int32_t* fi, const int32_t* fj, const double* meas4,
+                                   const double* sqrt_info3, const int32_t* loss_kind, const double* loss_param, uint32_t F, lama_hip_pgo** out)
+{
+    g_pgo_create_error.clear();
+    if (out) *out = nullptr;
+    for (uint32_t k = 0; loss_kind && k < F; ++k) {
+        const int32_t kind = loss_kind[k];
+        if (kind < LAMA_HIP_PGO_LOSS_NONE || kind > LAMA_HIP_PGO_LOSS_DCS) {
+            g_pgo_create_error = "lama_hip_pgo_create_robust: factor " + std::to_string(k) + " has the unknown loss kind " + std::to_string(kind);
+            return LAMA_HIP_E_INVALID;
+        }
+        if (kind == LAMA_HIP_PGO_LOSS_NONE) continue;
+        if (!loss_param || !std::isfinite(loss_param[k]) || !(loss_param[k] > 0.0)) {
+            g_pgo_create_error = "lama_hip_pgo_create_robust: factor " + std::to_string(k) + " has a robust loss whose parameter is not finite and > 0";
+            return LAMA_HIP_E_INVALID;
+        }
+    }
+    return pgo_create(device, N, fi, fj, meas4, sqrt_info3, loss_kind, loss_param, F, out);
+}
+
 void lama_hip_pgo_destroy(lama_hip_pgo* g) { delete g; }
 
-const char* lama_hip_pgo_last_error(const lama_hip_pgo* g) { return g ? g->error.c_str() : "null handle"; }
+const char* lama_hip_pgo_last_error(const lama_hip_pgo* g)
+{
+    if (g) return g->error.c_str();
+    return g_pgo_create_error.empty() ? "null handle" : g_pgo_create_error.c_str();     // (a refused create_robust left no handle to ask)
+}
+
+static PgoLossPtrs pgo_loss_ptrs(lama_hip_pgo* g) { return PgoLossPtrs{g->d_loss_kind, g->d_loss_param, g->d_weight}; }
+
+int32_t lama_hip_pgo_factor_weights(lama_hip_pgo* g, double* w)
+{
+    if (!g || !w) return LAMA_HIP_E_INVALID;
+    if (!g->linearized) {
+        g->error = "lama_hip_pgo_factor_weights: nothing linearised yet (call lama_hip_pgo_linearize or lama_hip_pgo_linearize_system first)";
+        return LAMA_HIP_E_STATE;
+    }
+    if (!g->robust) { std::fill(w, w + g->F, 1.0); return LAMA_HIP_OK; }
+    PGOCHK(g, hipSetDevice(g->device));
+    PGOCHK(g, hipMemcpyAsync(w, g->d_weight, sizeof(double) * g->F, hipMemcpyDeviceToHost, g->stream));
+    PGOCHK(g, hipStreamSynchronize(g->stream));
+    return LAMA_HIP_OK;
+}
 
 int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* err, double* Hdiag, double* Hoff, double* b, double* chi2,
                                double* kernel_ms)
@@ -1964,7 +2029,8 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
     PgoPtrs p{g->d_poses, g->d_fi, g->d_fj, g->d_meas, g->d_sqrt, g->d_err, g->d_hoff, g->d_fdi, g->d_fdj, g->d_fg, g->d_incptr, g->d_inc,
               g->d_hdiag, g->d_b, g->d_chi};
     PGOCHK(g, hipEventRecord(g->ev0, g->stream));
-    hipLaunchKernelGGL(k_pgo_factors, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, g->F);
+    if (g->robust) hipLaunchKernelGGL(k_pgo_factors_robust, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, pgo_loss_ptrs(g), g->F);
+    else hipLaunchKernelGGL(k_pgo_factors, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, g->F);
     hipLaunchKernelGGL(k_pgo_reduce, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, p, g->N);
     PGOCHK(g, hipEventRecord(g->ev1, g->stream));
     PGOCHK(g, hipGetLastError());
@@ -1974,6 +2040,7 @@ int32_t lama_hip_pgo_linearize(lama_hip_pgo* g, const double* poses4, double* er
     if (b) PGOCHK(g, hipMemcpyAsync(b, g->d_b, sizeof(double) * 3 * g->N, hipMemcpyDeviceToHost, g->stream));
     PGOCHK(g, hipMemcpyAsync(g->h_chi.data(), g->d_chi, sizeof(double) * g->blocksF, hipMemcpyDeviceToHost, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
+    g->linearized = true;
     if (chi2) { double t = 0; for (double x : g->h_chi) t += x; *chi2 = t; }
     if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
     return LAMA_HIP_OK;
@@ -2017,7 +2084,8 @@ int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b
               g->d_hdiag, g->d_b, g->d_chi};
     PgoSysPtrs s{g->d_hdiag, g->d_hoff, g->d_brow, g->d_bcol, g->d_cptr, g->d_contrib, g->d_blocks, g->d_diag};
     PGOCHK(g, hipEventRecord(g->ev0, g->stream));
-    hipLaunchKernelGGL(k_pgo_factors, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, g->F);
+    if (g->robust) hipLaunchKernelGGL(k_pgo_factors_robust, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, pgo_loss_ptrs(g), g->F);
+    else hipLaunchKernelGGL(k_pgo_factors, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, g->F);
     hipLaunchKernelGGL(k_pgo_reduce, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, p, g->N);
     hipLaunchKernelGGL(k_pgo_assemble, dim3((g->nnzb + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, s, g->nnzb);
     hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
@@ -2030,6 +2098,7 @@ int32_t lama_hip_pgo_linearize_system(lama_hip_pgo* g, double* blocks, double* b
     PGOCHK(g, hipMemcpyAsync(&h, g->d_half, sizeof(double), hipMemcpyDeviceToHost, g->stream));
     PGOCHK(g, hipStreamSynchronize(g->stream));
     g->system_valid = true;
+    g->linearized = true;
     if (half_chi2) *half_chi2 = h;
     if (kernel_ms) { float ms = 0; PGOCHK(g, hipEventElapsedTime(&ms, g->ev0, g->ev1)); *kernel_ms = ms; }
     return LAMA_HIP_OK;
@@ -2046,7 +2115,8 @@ int32_t lama_hip_pgo_try_step(lama_hip_pgo* g, const double* dx, double* half_ch
     PGOCHK(g, hipEventRecord(g->ev0, g->stream));
     hipLaunchKernelGGL(k_pgo_retract, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, (const double*)g->d_poses,
                        (const double*)g->d_dx, (double*)g->d_cand, g->N);
-    hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
+    if (g->robust) hipLaunchKernelGGL(k_pgo_error_robust, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, pgo_loss_ptrs(g), (const double*)g->d_cand, g->F);
+    else hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
     hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
     PGOCHK(g, hipEventRecord(g->ev1, g->stream));
     PGOCHK(g, hipGetLastError());
@@ -2149,7 +2219,8 @@ int32_t lama_hip_pgo_try_solved_step(lama_hip_pgo* g, double* half_chi2, double*
     PGOCHK(g, hipEventRecord(g->ev0, g->stream));
     hipLaunchKernelGGL(k_pgo_retract, dim3((g->N + PGO_BLOCK - 1) / PGO_BLOCK), dim3(PGO_BLOCK), 0, g->stream, (const double*)g->d_poses,
                        (const double*)g->d_px, (double*)g->d_cand, g->N);
-    hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
+    if (g->robust) hipLaunchKernelGGL(k_pgo_error_robust, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, pgo_loss_ptrs(g), (const double*)g->d_cand, g->F);
+    else hipLaunchKernelGGL(k_pgo_error, dim3(g->blocksF), dim3(PGO_BLOCK), 0, g->stream, p, (const double*)g->d_cand, g->F);
     hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, g->stream, (const double*)g->d_chi, g->blocksF, (double*)g->d_half);
     PGOCHK(g, hipEventRecord(g->ev1, g->stream));
     PGOCHK(g, hipGetLastError());

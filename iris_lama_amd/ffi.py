@@ -72,6 +72,7 @@ HIP_SYMBOLS = [
     "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
     "lama_hip_match_solve_batch",
     "lama_hip_pgo_solve_pcg", "lama_hip_pgo_try_solved_step",
+    "lama_hip_pgo_create_robust", "lama_hip_pgo_factor_weights",
 ]
 
 _hip = None
@@ -210,6 +211,8 @@ def _bind_hip(L):
             L.lama_hip_pgo_accept.argtypes = [vp]
             L.lama_hip_pgo_solve_pcg.argtypes = [vp, C.c_double, C.c_double, u32, u32, vp, vp, vp, vp, vp, vp]
             L.lama_hip_pgo_try_solved_step.argtypes = [vp, vp, vp]
+            L.lama_hip_pgo_create_robust.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, u32, vp]
+            L.lama_hip_pgo_factor_weights.argtypes = [vp, vp]
         for s in HIP_SYMBOLS:
             if s.startswith("lama_hip_pgo_") and not has_pgo:
                 continue
@@ -635,7 +638,7 @@ HOST_SYMBOLS = [
     "lama_sdm_write", "lama_sdm_read", "lama_sdm_image", "lama_sdm_export_png", "lama_dm_build", "lama_dm_build_fetch",
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
-    "lama_pgo_optimize", "lama_pgo_optimize_with",
+    "lama_pgo_optimize", "lama_pgo_optimize_with", "lama_pose_graph_optimize",
     "lama_mapbuilder_default_options", "lama_mapbuilder_create", "lama_mapbuilder_destroy", "lama_mapbuilder_last_error",
     "lama_mapbuilder_engine_origin", "lama_mapbuilder_device_context", "lama_mapbuilder_add", "lama_mapbuilder_set_pose",
     "lama_mapbuilder_set_poses", "lama_mapbuilder_build", "lama_mapbuilder_reset", "lama_mapbuilder_occupied_cells",
@@ -697,6 +700,7 @@ def _bind_host(L):
         "lama_dm_build": (C.c_int64, [vp, C.c_uint64, u32, vp]), "lama_dm_build_fetch": (i32, [vp, vp, vp]),
         "lama_pgo_optimize": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, u32, vp, i32]),
         "lama_pgo_optimize_with": (i32, [vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp, i32]),
+        "lama_pose_graph_optimize": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, i32]),
         "lama_mapbuilder_default_options": (None, [vp]), "lama_mapbuilder_create": (vp, [vp, vp, i32]), "lama_mapbuilder_destroy": (None, [vp]),
         "lama_mapbuilder_last_error": (C.c_char_p, [vp]), "lama_mapbuilder_engine_origin": (C.c_char_p, [vp]),
         "lama_mapbuilder_device_context": (vp, [vp]), "lama_mapbuilder_add": (C.c_int64, [vp, vp, u32, vp, vp, vp]),
@@ -1256,9 +1260,11 @@ def sdm_export_png(filename, patches, kind, resolution=0.05, max_sqdist=100):
 # SE2 pose-graph linearisation on the device (include/lama_hip.h, lama_hip_pgo_*)
 # ---------------------------------------------------------------------------------------------------------------
 class PoseGraph:
-    """Factors: fi, fj (fj = -1: prior on fi), meas [F,4] = {c, s, tx, ty}, sqrt_info [F,3] (DiagonalLoss: 1 / sigma)."""
+    """Factors: fi, fj (fj = -1: prior on fi), meas [F,4] = {c, s, tx, ty}, sqrt_info [F,3] (DiagonalLoss: 1 / sigma).
+    loss_kind [F] (PGO_LOSS_*) and loss_param [F]: a robust loss per factor, applied after the whitening
+    (lama_hip_pgo_create_robust); both None: lama_hip_pgo_create."""
 
-    def __init__(self, num_poses, fi, fj, meas, sqrt_info, device=0):
+    def __init__(self, num_poses, fi, fj, meas, sqrt_info, device=0, loss_kind=None, loss_param=None):
         self.L = hip_lib()
         self.N = int(num_poses)
         self.fi = np.ascontiguousarray(fi, dtype=np.int32)
@@ -1267,7 +1273,19 @@ class PoseGraph:
         self.sqrt_info = np.ascontiguousarray(sqrt_info, dtype=np.float64).reshape(-1, 3)
         self.F = len(self.fi)
         h = C.c_void_p()
-        rc = self.L.lama_hip_pgo_create(device, self.N, _p(self.fi), _p(self.fj), _p(self.meas), _p(self.sqrt_info), self.F, C.byref(h))
+        if loss_kind is None and loss_param is None:
+            rc = self.L.lama_hip_pgo_create(device, self.N, _p(self.fi), _p(self.fj), _p(self.meas), _p(self.sqrt_info), self.F, C.byref(h))
+        else:
+            self.loss_kind = None if loss_kind is None else np.ascontiguousarray(loss_kind, dtype=np.int32)
+            self.loss_param = None if loss_param is None else np.ascontiguousarray(loss_param, dtype=np.float64)
+            for a in (self.loss_kind, self.loss_param):
+                if a is not None and a.shape != (self.F,):
+                    raise ValueError(f"loss_kind / loss_param must have one entry per factor ({self.F}), not shape {a.shape}")
+            rc = self.L.lama_hip_pgo_create_robust(device, self.N, _p(self.fi), _p(self.fj), _p(self.meas), _p(self.sqrt_info),
+                                                   _p(self.loss_kind), _p(self.loss_param), self.F, C.byref(h))
+            why = self.L.lama_hip_pgo_last_error(None).decode()
+            if rc != 0 and why != "null handle":
+                raise LamaError(why)
         if rc != 0 or not h:
             raise LamaError(f"lama_hip_pgo_create failed (status {rc}): no usable MI355X / HIP device or invalid graph; there is no CPU fallback")
         self.h = h
@@ -1333,6 +1351,12 @@ class PoseGraph:
         """The candidate of the last try_step becomes the current state; LamaError when none is pending."""
         self._check(self.L.lama_hip_pgo_accept(self.h))
 
+    def factor_weights(self):
+        """-> w [F] of every factor's loss in the last linearize / linearize_system (1 without a loss); LamaError before the first."""
+        w = np.zeros(self.F)
+        self._check(self.L.lama_hip_pgo_factor_weights(self.h, _p(w)))
+        return w
+
     def solve_pcg(self, lam, rel_tol=1e-10, max_iterations=None, batch=0, want_dx=True):
         """(H + lam diag(H)) dx = b of the last linearize_system, solved on the device by block-Jacobi PCG (lama_hip_pgo_solve_pcg).
         max_iterations None: max(100, 6 N).  -> dict(dx [N,3] or None, iterations, rel_residual_sq, outcome (PCG_CONVERGED / PCG_CAP /
@@ -1354,6 +1378,8 @@ class PoseGraph:
 
 
 PCG_CONVERGED, PCG_CAP, PCG_BREAKDOWN = 0, 1, 2          # include/lama_hip.h, LAMA_HIP_PCG_*
+PGO_LOSS_NONE, PGO_LOSS_HUBER, PGO_LOSS_CAUCHY, PGO_LOSS_DCS = 0, 1, 2, 3      # include/lama_hip.h, LAMA_HIP_PGO_LOSS_*
+PGO_LOSSES = {None: PGO_LOSS_NONE, "none": PGO_LOSS_NONE, "huber": PGO_LOSS_HUBER, "cauchy": PGO_LOSS_CAUCHY, "dcs": PGO_LOSS_DCS}
 
 
 class PgoReport(C.Structure):
@@ -1424,6 +1450,46 @@ def simple_pgo(nodes, edges=(), fixed=(), device=0, solver=None, pcg_rel_tol=1e-
     r = rep.as_dict()
     r["status_name"] = PGO_STATUS.get(r["status"], str(r["status"]))
     r["trace"] = trace[:min(rep.tries, cap)].copy()
+    return rc == 1, out, r
+
+
+def pose_graph_optimize(nodes, factors, device=0, solver=None, pcg_rel_tol=1e-10, pcg_max_iterations=0):
+    """lama::PoseGraph2D::optimize (include/lama/pose_graph_2d.h) on the device.  nodes [n,4] {c, s, tx, ty}; factors: iterable of
+    (from, to, pose4, sigmas3) or (from, to, pose4, sigmas3, loss) with to = -1 for a prior on `from` and loss None or a pair
+    (name, parameter), name one of "huber", "cauchy", "dcs".  solver, pcg_*: as simple_pgo.
+    -> (ok, poses [n,4], report dict as simple_pgo's with "pcg", plus "weights" [F]: every factor's loss weight at the state the
+    run ended in; empty when the graph was refused, status -1)."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, 4)
+    n = len(nodes)
+    factors = list(factors)
+    nf = len(factors)
+    fi = np.array([f[0] for f in factors], dtype=np.int32)
+    fj = np.array([f[1] for f in factors], dtype=np.int32)
+    m4 = np.ascontiguousarray(np.array([f[2] for f in factors], dtype=np.float64).reshape(-1, 4))
+    s3 = np.ascontiguousarray(np.array([f[3] for f in factors], dtype=np.float64).reshape(-1, 3))
+    losses = [f[4] if len(f) > 4 and f[4] is not None else (None, 0.0) for f in factors]
+    for name, _ in losses:
+        if name not in PGO_LOSSES:
+            raise ValueError(f"loss must be None or (name, parameter) with name one of 'huber', 'cauchy', 'dcs', not {name!r}")
+    kind = np.array([PGO_LOSSES[l[0]] for l in losses], dtype=np.int32)
+    param = np.array([l[1] for l in losses], dtype=np.float64)
+    if (solver or "ldlt") not in PGO_SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(PGO_SOLVERS)}, not {solver!r}")
+    opt = PgoOptions(C.sizeof(PgoOptions), device, PGO_SOLVERS[solver or "ldlt"], int(pcg_max_iterations), float(pcg_rel_tol))
+    rep = PgoReport2()
+    rep.struct_bytes = C.sizeof(PgoReport2)
+    out, weights = np.zeros((n, 4)), np.ones(nf)
+    cap = 1 << 16
+    trace = np.zeros(cap, dtype=np.int8)
+    err = C.create_string_buffer(512)
+    rc = _hostlib().lama_pose_graph_optimize(_p(nodes) if n else None, n, _p(fi), _p(fj), _p(m4), _p(s3), _p(kind), _p(param), nf, C.byref(opt),
+                                            _p(out) if n else None, _p(weights), C.byref(rep), _p(trace), cap, err, 512)
+    if rc < 0:
+        raise LamaError(err.value.decode())
+    r = rep.as_dict()
+    r["status_name"] = PGO_STATUS.get(r["status"], str(r["status"]))
+    r["trace"] = trace[:min(rep.tries, cap)].copy()
+    r["weights"] = weights if r["status"] != -1 else np.zeros(0)
     return rc == 1, out, r
 
 

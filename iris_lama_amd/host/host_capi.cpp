@@ -18,6 +18,7 @@
 #include "lama/sdm_io.h"
 #include "dm_builder.hpp"
 #include "lama/slam2d.h"
+#include "lama/pose_graph_2d.h"
 #include "lama/simple_pgo.h"
 #include "lama/map_builder_2d.h"
 
@@ -812,6 +813,21 @@ int lama_pgo_optimize(const double* nodes4, uint32_t n, const int32_t* edge_from
     }
 }
 
+// lama_pgo_report2 from the class's report: at most the bytes the caller's struct has
+static void fill_report2(const SimplePGO::Report& r, lama_pgo_report2* report)
+{
+    lama_pgo_report2 f;
+    std::memset(&f, 0, sizeof(f));
+    f.struct_bytes = report->struct_bytes;
+    f.status = r.status; f.iterations = r.iterations; f.tries = r.tries;
+    f.initial_error = r.initial_error; f.final_error = r.final_error; f.nnz_L = r.nnz_L;
+    f.ms_device_linearize = r.ms_device_linearize; f.ms_device_try = r.ms_device_try;
+    f.ms_analyze = r.ms_analyze; f.ms_factorize = r.ms_factorize; f.ms_total = r.ms_total;
+    f.pcg_iterations = r.pcg_iterations; f.pcg_max_iterations_seen = r.pcg_max_iterations_seen;
+    f.pcg_fallbacks = r.pcg_fallbacks; f.ms_device_solve = r.ms_device_solve;
+    std::memcpy(report, &f, std::min<size_t>(report->struct_bytes, sizeof(f)));
+}
+
 int lama_pgo_optimize_with(const double* nodes4, uint32_t n, const int32_t* edge_from, const int32_t* edge_to, const double* edge4,
                            uint32_t ne, const int32_t* fixed_idx, const double* fixed4, uint32_t nf, const lama_pgo_options* options,
                            double* out4, lama_pgo_report2* report, int8_t* trace, uint32_t trace_cap, char* err, int errcap)
@@ -834,18 +850,45 @@ int lama_pgo_optimize_with(const double* nodes4, uint32_t n, const int32_t* edge
         const bool ok = p.optimize();
         if (out4) for (uint32_t i = 0; i < n; ++i) p.node_list[i].state.toArray(out4 + 4 * i);
         if (report) {
-            const SimplePGO::Report& r = p.report;
-            lama_pgo_report2 f;
-            std::memset(&f, 0, sizeof(f));
-            f.struct_bytes = report->struct_bytes;
-            f.status = r.status; f.iterations = r.iterations; f.tries = r.tries;
-            f.initial_error = r.initial_error; f.final_error = r.final_error; f.nnz_L = r.nnz_L;
-            f.ms_device_linearize = r.ms_device_linearize; f.ms_device_try = r.ms_device_try;
-            f.ms_analyze = r.ms_analyze; f.ms_factorize = r.ms_factorize; f.ms_total = r.ms_total;
-            f.pcg_iterations = r.pcg_iterations; f.pcg_max_iterations_seen = r.pcg_max_iterations_seen;
-            f.pcg_fallbacks = r.pcg_fallbacks; f.ms_device_solve = r.ms_device_solve;
-            std::memcpy(report, &f, std::min<size_t>(report->struct_bytes, sizeof(f)));
+            fill_report2(p.report, report);
         }
+        if (trace) for (size_t q = 0; q < p.report.trace.size() && q < trace_cap; ++q) trace[q] = p.report.trace[q];
+        return ok ? 1 : 0;
+    } catch (const std::exception& e) {
+        if (err && errcap > 0) { std::strncpy(err, e.what(), (size_t)errcap - 1); err[errcap - 1] = 0; }
+        return -1;
+    }
+}
+
+int lama_pose_graph_optimize(const double* nodes4, uint32_t n, const int32_t* fi, const int32_t* fj, const double* meas4,
+                             const double* sigmas3, const int32_t* loss_kind, const double* loss_param, uint32_t nf,
+                             const lama_pgo_options* options, double* out4, double* weights, lama_pgo_report2* report, int8_t* trace,
+                             uint32_t trace_cap, char* err, int errcap)
+{
+    try {
+        lama_pgo_options o;
+        std::memset(&o, 0, sizeof(o));
+        o.pcg_rel_tol = PoseGraph2D().pcg_rel_tol;
+        if (options) std::memcpy(&o, options, std::min<size_t>(options->struct_bytes, sizeof(o)));
+        if (o.linear_solver != PoseGraph2D::HostLDLT && o.linear_solver != PoseGraph2D::DevicePCG)
+            throw std::invalid_argument("lama_pose_graph_optimize: linear_solver must be 0 (host LDL^T) or 1 (device PCG)");
+        PoseGraph2D p;
+        p.device = o.device;
+        p.linear_solver = (PoseGraph2D::LinearSolver)o.linear_solver;
+        p.pcg_rel_tol = o.pcg_rel_tol;
+        p.pcg_max_iterations = o.pcg_max_iterations;
+        for (uint32_t i = 0; i < n; ++i) p.addNode(Pose2D(SE2d::fromArray(nodes4 + 4 * i)));
+        for (uint32_t k = 0; k < nf; ++k) {
+            PoseGraph2D::Loss loss;
+            if (loss_kind) { loss.kind = loss_kind[k]; loss.param = loss_param ? loss_param[k] : 0.0; }
+            const Vector3d sig(sigmas3[3 * k], sigmas3[3 * k + 1], sigmas3[3 * k + 2]);
+            if (fj[k] == -1) p.addPrior(fi[k], Pose2D(SE2d::fromArray(meas4 + 4 * k)), sig, loss);
+            else p.addBetween(fi[k], fj[k], Pose2D(SE2d::fromArray(meas4 + 4 * k)), sig, loss);
+        }
+        const bool ok = p.optimize();
+        if (out4) for (uint32_t i = 0; i < n; ++i) p.nodes[i].state.toArray(out4 + 4 * i);
+        if (weights) std::copy(p.weights.begin(), p.weights.end(), weights);
+        if (report) fill_report2(p.report, report);
         if (trace) for (size_t q = 0; q < p.report.trace.size() && q < trace_cap; ++q) trace[q] = p.report.trace[q];
         return ok ? 1 : 0;
     } catch (const std::exception& e) {

@@ -1,6 +1,7 @@
 // pgo_graph.hpp -- the factor graph lama::SimplePGO::optimize builds (src/simple_pgo.cpp:48-105 of the reference), as the flat
 // arrays of the device C-ABI: factor k on poses fi[k], fj[k] (fj = -1: a prior on fi), measurement {c, s, tx, ty}, sqrt_info = 1 / sigma
-// (DiagonalLoss::Sigmas, vendor/minisam/minisam/core/LossFunction.cpp:71-74).
+// (DiagonalLoss::Sigmas, vendor/minisam/minisam/core/LossFunction.cpp:71-74).  lama::PoseGraph2D (pose_graph_2d.cpp) fills the same
+// arrays from its own factor list.
 #pragma once
 
 #include <cstdint>
@@ -15,6 +16,10 @@ struct Graph {
     uint32_t N = 0;
     std::vector<int32_t> fi, fj;
     std::vector<double> meas4, sqrt_info3, init4;
+    // per-factor robust losses (lama::PoseGraph2D): both empty (what SimplePGO builds: lama_hip_pgo_create), or one entry per factor,
+    // LAMA_HIP_PGO_LOSS_* and its parameter (lama_hip_pgo_create_robust)
+    std::vector<int32_t> loss_kind;
+    std::vector<double> loss_param;
     void add(int32_t i, int32_t j, const SE2d& z, double s0, double s1, double s2)
     {
         fi.push_back(i); fj.push_back(j);
