@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "correlative_search_2d.h"
 #include "pose2d.h"
 #include "sdm/dynamic_distance_map.h"
 #include "sdm/simple_occupancy_map.h"
@@ -50,6 +51,16 @@ public:
     bool enoughMotion(const Pose2D& odometry);
     bool update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, double timestamp, bool force_update = false);
     void triggerGlobalLocalization();
+    // An addition (the reference has none): global localisation by exhaustive search instead of random samples.  The scan is scored at
+    // every node of a pose lattice over occupancy_map's bounds() on the device (lama::CorrelativeSearch2D on this object's own
+    // context); tile winners whose node is not a FREE cell of occupancy_map are dropped, as the reference draws its candidates from
+    // free cells only (a tile keeps one node: a free node that scored behind a non-free one of its tile is not seen); the rest are
+    // selected and refined as CorrelativeSearch2D::search does.  If the best candidate's rmse (MatchSurface2D::error()) is below
+    // Options::gloc_thresh the pose is set as setPose() sets it and true is returned; otherwise nothing of the object changes.
+    // triggerGlobalLocalization() / update() keep the reference's behaviour.
+    bool relocalize(const PointCloudXYZ::Ptr& surface, const CorrelativeSearch2D::Options& options = CorrelativeSearch2D::Options());
+    // the candidates of the last relocalize(), best first (instrumentation, like lastGlocPoses)
+    const std::vector<CorrelativeSearch2D::Candidate>& lastRelocalizeCandidates() const { return reloc_; }
     void setPose(const Pose2D& pose) { pose_ = pose; has_first_scan = false; }
     const Pose2D& getPose() const { return pose_; }
     const Matrix3d& getCovar() const { return cov_; }     // Eigen::Matrix3d when Eigen is available (lama/types.h)
@@ -86,6 +97,7 @@ private:
     double cov_blend_ = 0.0;
     std::vector<Vector2d> sampling_steps_;
     std::vector<double> gloc_poses_, gloc_errors_, sampling_l_;
+    std::vector<CorrelativeSearch2D::Candidate> reloc_;
 };
 
 } // namespace lama

@@ -276,6 +276,35 @@ int32_t lama_hip_match_solve_batch(lama_hip_ctx* ctx, uint32_t num_problems, con
                                    int32_t strategy, int32_t robust_kind, double robust_param, double* out8, int32_t* iters_out,
                                    uint32_t* status_out);
 
+/* Exhaustive search of a regular pose lattice against `particle`'s distance map (csrc/lama_correlative.h): correlative scan matching
+ * (Olson 2009), the stage that PRODUCES the start pose lama_hip_match_solve_batch refines -- what the reference approaches with 3000
+ * random poses (Loc2D::globalLocalization, src/loc2d.cpp:249-286) and a coarse retry (GraphSlam2D::coarseSearchAndCorrelateCandidateScan).
+ * The lattice: num_headings headings, given as headings_cs [H][2] = {cos, sin} COMPUTED BY THE CALLER, times nx x ny translations;
+ * node (0, 0) is the world position (wx0, wy0), node (ix, iy) is node (0, 0) shifted by cell_step * (ix, iy) whole CELLS.  Of the
+ * scan, points 0, point_step, 2 point_step, ... are used.  Definition:
+ *   for heading h the pose is {c_h, s_h, wx0, wy0}; every used point i has the cell cell_i = w2m(hit_i), with hit_i formed as
+ *   lama_hip_match_cell_distances forms it -- except that the pose's transform is composed on the host (libm): the device does no
+ *   trigonometry, so the cells are the reference's bit for bit at every heading;
+ *   score(h, ix, iy) = sum over i of q(cell_i + cell_step * (ix, iy)) in uint32 arithmetic, where q is the SQUARED distance in cells
+ *   that the map stores for a cell with a valid obstacle, and the map's maximum squared distance (ceil(l2_max / resolution)^2) for a
+ *   cell outside the window, in an absent patch, or without a valid obstacle -- DynamicDistanceMap::distance of the cell, before the
+ *   square root and the resolution;
+ *   best_out [H][ceil(ny / tile)][ceil(nx / tile)]: per tile of tile x tile nodes (partial at the upper edges) the smallest key
+ *   ((uint64) score << 32) | index, index = (h * ny + iy) * nx + ix.  Keys are unique: equal scores go to the smaller index, and the
+ *   result depends on no scheduling;
+ *   scores_out [H][ny][nx] (may be NULL): every score.
+ * No map, pose or counter of the context changes (the scan becomes the resident one, as with lama_hip_match_eval).
+ * LAMA_HIP_E_INVALID, found before anything is uploaded and with every array untouched: n, point_step, num_headings, nx, ny,
+ * cell_step or tile of 0; tile > 8 (a workgroup holds the 64 nodes of a tile, one per lane); a non-finite point, mount, heading entry
+ * or origin; a particle out of range; num_headings * nx * ny >= 2^32; ceil(n / point_step) * max squared distance >= 2^32 (a score
+ * must fit 32 bits: raise point_step); a lattice whose far corner, with the scan's reach around it, would leave the 32-bit range of map
+ * cell coordinates. */
+int32_t lama_hip_match_search_lattice(lama_hip_ctx* ctx, uint32_t particle, const double* pts_xyz, uint32_t n,
+                                      const double* sensor_origin3, const double* sensor_quat_wxyz, uint32_t point_step,
+                                      const double* headings_cs, uint32_t num_headings, double wx0, double wy0,
+                                      uint32_t cell_step, uint32_t nx, uint32_t ny, uint32_t tile,
+                                      uint64_t* best_out, uint32_t* scores_out);
+
 /* Map rebuild from posed key scans (GraphSlam2D::generateOccupancyMap, src/graph_slam2d.cpp:131-164) on `particle`'s FREQUENCY
  * occupancy map, all scans in one order-free pass (csrc/lama_map_build.h).  Per scan k and point p, the reference's loop:
  * tf = T(pose_k) * T(sensor_origin_k) * R(sensor_quat_k); hit = tf * p; setOccupied(w2m(hit)); with flags bit 0 ("full") also

@@ -156,6 +156,15 @@ int lama_slam_solve_batch(lama_slam* s, lama_slam* other, uint32_t num_problems,
                           const double* origins3, const double* quats_wxyz, double* poses4, const uint32_t* max_iterations,
                           const char* strategy, double eps1, const char* weight, double weight_param, double* cov9, uint32_t* iterations,
                           double* errors);
+/* lama::CorrelativeSearch2D::search (lama/correlative_search_2d.h) on this object's distance map over the box box4 = {min x, min y, max
+ * x, max y}; the options are the class's (point_step 0: max(n / 256, 1)).  *num_out = candidates found; the first min(cap, *num_out),
+ * sorted by rmse, are written: coarse4 [cap][4] / poses4 [cap][4] {c, s, tx, ty}, scores, rmse, iterations.  lattice6 (may be NULL) =
+ * cell_step, nx, ny, headings, point_step, tile of the lattice that was searched.  -1: no map yet, -3: std::invalid_argument, -2: any
+ * other failure (the device library lacks the entry, ...). */
+int lama_slam_correlative_search(lama_slam* s, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz, const double* box4,
+                                 double linear_step, double angular_step, uint32_t point_step, uint32_t tile, uint32_t max_candidates, int refine,
+                                 uint32_t refine_iterations, uint32_t cap, double* coarse4, uint32_t* scores, double* poses4, double* rmse,
+                                 uint32_t* iterations, uint32_t* lattice6, uint32_t* num_out);
 const char* lama_slam_engine_origin(const lama_slam* s);
 
 /* ---- lama::Loc2D (include/lama/loc2d.h), flattened ---- */
@@ -193,6 +202,13 @@ void lama_loc_trigger_global_localization(lama_loc* l);
 int lama_loc_global_localization_active(const lama_loc* l);
 uint32_t lama_loc_gloc_candidates(const lama_loc* l, double* poses4, double* errors, uint32_t cap);
 uint32_t lama_loc_sampling_likelihoods(const lama_loc* l, double* out, uint32_t cap);
+/* Loc2D::relocalize with the given CorrelativeSearch2D options: 1 = a candidate's rmse was below gloc_thresh and the pose was set, 0 =
+ * none was (nothing changed), -1 = failure.  lama_loc_relocalize_candidates: the candidates of the last call, best first (returns their
+ * number; the first min(cap, number) are written, arrays as lama_slam_correlative_search's). */
+int lama_loc_relocalize(lama_loc* l, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz, double linear_step,
+                        double angular_step, uint32_t point_step, uint32_t tile, uint32_t max_candidates, uint32_t refine_iterations);
+uint32_t lama_loc_relocalize_candidates(const lama_loc* l, uint32_t cap, double* coarse4, uint32_t* scores, double* poses4, double* rmse,
+                                        uint32_t* iterations);
 /* ---- lama::LidarOdometry2D (include/lama/lidar_odometry_2d.h), flattened ---- */
 typedef struct lama_lo lama_lo;
 lama_lo* lama_lo_create(double resolution, uint32_t max_iter, int32_t gpu_device, char* err, int errcap);

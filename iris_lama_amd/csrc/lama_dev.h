@@ -560,16 +560,34 @@ __device__ inline uint32_t w2m(const DevParams& prm, double v) { return (uint32_
 // DynamicDistanceMap::distance(Vector3ui) (src/sdm/dynamic_distance_map.cpp:140-147) through the const
 // Map::get (src/sdm/map.cpp:414-455): absent patch / mask bit off / !valid_obstacle -> max distance.
 // An off-bit cell is still all-zero, hence reads as !valid: the mask needs no separate test.
+// (the window test and the directory walk: v = plane A's record of map cell (x, y); false outside the window / in an absent patch)
+__device__ __forceinline__ bool dm_cell_sv(const DevParams& prm, const int16_t* __restrict__ dir, const sv_t* __restrict__ sv,
+                                           uint32_t x, uint32_t y, sv_t& v)
+{
+    const uint32_t rx = x - prm.wx0, ry = y - prm.wy0;
+    if (rx >= prm.WC || ry >= prm.WC) return false;
+    const int slot = dir[(ry >> 5) * prm.W + (rx >> 5)];
+    if (slot < 0) return false;
+    v = sv[(uint32_t)slot * 1024u + ((rx & 31u) | ((ry & 31u) << 5))];
+    return true;
+}
 __device__ inline double dm_distance_cell(const DevParams& prm, const int16_t* __restrict__ dir,
                                           const sv_t* __restrict__ sv, uint32_t x, uint32_t y)
 {
-    const uint32_t rx = x - prm.wx0, ry = y - prm.wy0;
-    if (rx >= prm.WC || ry >= prm.WC) return prm.maxdist;
-    const int slot = dir[(ry >> 5) * prm.W + (rx >> 5)];
-    if (slot < 0) return prm.maxdist;
-    const sv_t v = sv[(uint32_t)slot * 1024u + ((rx & 31u) | ((ry & 31u) << 5))];
+    sv_t v;
+    if (!dm_cell_sv(prm, dir, sv, x, y, v)) return prm.maxdist;
     if (!(v & SV_VALID)) return prm.maxdist;
     return sqrt((double)(v & SV_SQMASK)) * prm.resolution;
+}
+// The same without the square root and the resolution: the stored squared distance in cells, max_sqdist where dm_distance_cell
+// answers the maximum distance (k_search_lattice sums these as integers, lama_correlative.h)
+__device__ inline uint32_t dm_sqdist_cell(const DevParams& prm, const int16_t* __restrict__ dir,
+                                          const sv_t* __restrict__ sv, uint32_t x, uint32_t y)
+{
+    sv_t v;
+    if (!dm_cell_sv(prm, dir, sv, x, y, v)) return prm.max_sqdist;
+    if (!(v & SV_VALID)) return prm.max_sqdist;
+    return (uint32_t)(v & SV_SQMASK);
 }
 
 // DynamicDistanceMap::distance(Vector3d, Vector3d*) 2-D branch (src/sdm/dynamic_distance_map.cpp:66-91)

@@ -20,6 +20,7 @@
 #include "lama_pgo_pcg.h"
 #include "lama_map_build.h"
 #include "lama_match_batch.h"
+#include "lama_correlative.h"
 #include "../host/pgo_pattern.hpp"
 
 using namespace lama_dev;
@@ -236,6 +237,9 @@ struct lama_hip_ctx {
     // [iterations B | status B | problems 4B], with their page-locked staging copies
     DevBuf<double> d_msb_f64; DevBuf<uint32_t> d_msb_u32;
     PinVec<double> h_msb_f64; PinVec<uint32_t> h_msb_u32;
+    // lama_hip_match_search_lattice (lama_correlative.h), grow-only: the headings' transforms [H][12] and the tile keys
+    DevBuf<double> d_cs_tfs; DevBuf<uint64_t> d_cs_best;
+    PinVec<double> h_cs_tfs;
 
     double scan_reach = 0.0;          // largest point distance of the resident scan (sensor frame, metres)
     uint32_t visit_bound = 0;         // upper bound of the largest `visited` counter of any frequency cell (see k_occ_max_visited)
@@ -2661,6 +2665,74 @@ int32_t lama_hip_match_solve_batch(lama_hip_ctx* c, uint32_t B, const uint32_t* 
     std::memcpy(iters_out, hu + L.it, sizeof(int32_t) * B);
     if (status_out) std::memcpy(status_out, hu + L.st, sizeof(uint32_t) * B);
     return rc;
+}
+
+// ---- exhaustive pose-lattice search (lama_correlative.h): every heading's transform is formed HERE (libm, like every map update's),
+// the kernel turns points into cells and sums stored squared distances
+int32_t lama_hip_match_search_lattice(lama_hip_ctx* c, uint32_t particle, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                                      uint32_t point_step, const double* headings_cs, uint32_t H, double wx0, double wy0,
+                                      uint32_t cell_step, uint32_t nx, uint32_t ny, uint32_t tile, uint64_t* best_out, uint32_t* scores_out)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // ---- everything that can refuse the call, before anything is uploaded
+    const char* const me = "lama_hip_match_search_lattice: ";
+    if (!pts || !headings_cs || !best_out) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a required array is NULL");
+    if (n == 0 || point_step == 0 || H == 0) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "no point, no heading, or a point step of 0");
+    if (nx == 0 || ny == 0 || cell_step == 0 || tile == 0) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "nx, ny, cell_step and tile are at least 1");
+    if (tile > 8u || tile * tile > (uint32_t)CS_NODES)
+        return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a tile holds at most " + std::to_string(CS_NODES) + " nodes (tile <= 8)");
+    if (particle >= c->P) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "particle out of range");
+    const uint64_t nodes = (uint64_t)nx * ny;
+    if (nodes >= (1ull << 32) || nodes * H >= (1ull << 32)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the lattice has 2^32 nodes or more (a key carries a 32-bit index)");
+    const uint32_t n_used = (n - 1u) / point_step + 1u;
+    if ((uint64_t)n_used * c->max_sqdist >= (1ull << 32)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a score could exceed 32 bits (points used x max_sqdist); raise point_step");
+    for (int k = 0; origin3 && k < 3; ++k) if (!std::isfinite(origin3[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the sensor origin is not finite");
+    for (int k = 0; quat && k < 4; ++k) if (!std::isfinite(quat[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the sensor orientation is not finite");
+    if (!std::isfinite(wx0) || !std::isfinite(wy0)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the lattice origin is not finite");
+    for (size_t k = 0; k < 2 * (size_t)H; ++k) if (!std::isfinite(headings_cs[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a heading entry is not finite");
+    double r2 = 0.0, nan_acc = 0.0;                               // (std::max drops a NaN: the sum of products with zero keeps it)
+    for (size_t i = 0; i < n; ++i) {
+        const double d2 = pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2];
+        r2 = std::max(r2, d2); nan_acc += d2 * 0.0;
+    }
+    if (!std::isfinite(r2) || !(nan_acc == 0.0)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)");
+    // no cell coordinate of any node may leave [0, 2^32): per heading, the hits lie within |row of R| * reach of the transform's
+    // translation, and the far corner adds cell_step * (nx - 1, ny - 1) cells
+    const Affine mtf = moving_tf(origin3, quat);
+    const double reach = std::sqrt(r2);
+    c->h_cs_tfs.resize(12 * (size_t)H);
+    for (uint32_t h = 0; h < H; ++h) {
+        const double pose4[4] = {headings_cs[2 * (size_t)h], headings_cs[2 * (size_t)h + 1], wx0, wy0};
+        double* const t = &c->h_cs_tfs[12 * (size_t)h];
+        host_scan_tf(pose4, mtf, t);
+        for (int a = 0; a < 2; ++a) {
+            const double row = std::sqrt(t[3 * a] * t[3 * a] + t[3 * a + 1] * t[3 * a + 1] + t[3 * a + 2] * t[3 * a + 2]) * reach;
+            const double lo = c->scale * (t[9 + a] - row) + c->off, hi = c->scale * (t[9 + a] + row) + c->off + 1.0 + (double)cell_step * (double)((a == 0 ? nx : ny) - 1u);
+            if (!(lo >= 0.0) || !(hi < 4294967295.0))
+                return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the lattice, with the scan's reach around it, leaves the 32-bit range of map cell coordinates");
+        }
+    }
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_match_search_lattice before a map exists");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int32_t rc = upload_scan(c, pts, n);
+    if (rc) return rc;
+    const uint32_t tiles_x = (nx - 1u) / tile + 1u, tiles_y = (ny - 1u) / tile + 1u;
+    const uint64_t total = (uint64_t)tiles_x * tiles_y * H;
+    HIPCHK(c, c->d_cs_tfs.grow(12 * (size_t)H, 12 * 128));
+    HIPCHK(c, c->d_cs_best.grow(total, (size_t)1 << 12));
+    DevBuf<uint32_t> scores;                                        // (only a caller who asks for every score pays for them)
+    if (scores_out) HIPCHK(c, scores.alloc(nodes * H));
+    double* const d_tfs = c->d_cs_tfs; uint64_t* const d_best = c->d_cs_best; uint32_t* const d_scores = scores;
+    HIPCHK(c, hipMemcpyAsync(d_tfs, c->h_cs_tfs.data(), sizeof(double) * 12 * (size_t)H, hipMemcpyHostToDevice, c->stream));
+    const DevParams prm = make_params(c);
+    hipLaunchKernelGGL(k_search_lattice, dim3((unsigned)std::min<uint64_t>(total, (uint64_t)1 << 20)), dim3(CS_BLOCK), 0, c->stream, prm, (int)particle,
+                       (const double*)c->d_pts, n_used, point_step, (const double*)d_tfs, cell_step, nx, ny, tile, tiles_x, tiles_y, total, d_best, d_scores);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(best_out, d_best, sizeof(uint64_t) * total, hipMemcpyDeviceToHost, c->stream));
+    if (scores_out) HIPCHK(c, hipMemcpyAsync(scores_out, d_scores, sizeof(uint32_t) * nodes * H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LAMA_HIP_OK;
 }
 
 // Particle blob layout: [pose 4 f64][header 8 i32][dm_dir][occ_dir][dm_sv used][dm_obs used][dm_mask used][occ used][occ_mask used]

@@ -70,7 +70,7 @@ HIP_SYMBOLS = [
     "lama_hip_pgo_pattern", "lama_hip_pgo_set_poses", "lama_hip_pgo_get_poses", "lama_hip_pgo_linearize_system",
     "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
     "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
-    "lama_hip_match_solve_batch",
+    "lama_hip_match_solve_batch", "lama_hip_match_search_lattice",
     "lama_hip_pgo_solve_pcg", "lama_hip_pgo_try_solved_step",
     "lama_hip_pgo_create_robust", "lama_hip_pgo_factor_weights",
 ]
@@ -192,6 +192,9 @@ def _bind_hip(L):
         has_msb = hasattr(L, "lama_hip_match_solve_batch")   # batched registration (absent from the engine test double)
         if has_msb:
             L.lama_hip_match_solve_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
+        has_csl = hasattr(L, "lama_hip_match_search_lattice")   # pose-lattice search (absent from the engine test double)
+        if has_csl:
+            L.lama_hip_match_search_lattice.argtypes = [vp, u32, vp, u32, vp, vp, u32, vp, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp]
         has_cks = hasattr(L, "lama_hip_pf_map_checksums")   # device-only diagnostic (absent from the engine test double)
         if has_cks:
             L.lama_hip_pf_map_checksums.argtypes = [vp, i32, vp]
@@ -221,6 +224,8 @@ def _bind_hip(L):
             if s in ("lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells") and not has_mb:
                 continue
             if s == "lama_hip_match_solve_batch" and not has_msb:
+                continue
+            if s == "lama_hip_match_search_lattice" and not has_csl:
                 continue
             if s not in ("lama_hip_default_cfg", "lama_hip_ctx_destroy", "lama_hip_last_error", "lama_hip_pgo_destroy",
                          "lama_hip_pgo_last_error"):
@@ -512,6 +517,23 @@ class HipContext:
             self._chk(rc)
         return poses, out8, it, st
 
+    def search_lattice(self, particle, pts, headings, wx0, wy0, cell_step, nx, ny, tile=8, point_step=1, origin=None, quat=None, scores=True):
+        """lama_hip_match_search_lattice: the score of every node of a pose lattice and the best key of every tile.  `headings` are
+        angles in radians (their cos / sin are taken here, on the host) or an (H, 2) array of {cos, sin}; node (0, 0) is at the
+        world position (wx0, wy0), node (ix, iy) cell_step * (ix, iy) cells further.
+        -> (best (H, ceil(ny / tile), ceil(nx / tile)) uint64 keys score << 32 | index, scores (H, ny, nx) uint32 or None)"""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        hd = np.asarray(headings, dtype=np.float64)
+        cs = np.ascontiguousarray(hd if hd.ndim == 2 else np.stack([np.cos(hd), np.sin(hd)], axis=1).reshape(-1, 2))
+        H, nx, ny, tile = len(cs), int(nx), int(ny), int(tile)
+        if nx < 1 or ny < 1 or tile < 1:
+            raise ValueError("nx, ny and tile are at least 1")
+        best = np.zeros((H, (ny + tile - 1) // tile, (nx + tile - 1) // tile), dtype=np.uint64)
+        sc = np.zeros((H, ny, nx), dtype=np.uint32) if scores else None
+        self._chk(self.L.lama_hip_match_search_lattice(self.h, particle, _p(pts), len(pts), _p(origin), _p(quat), int(point_step), _p(cs), H,
+                                                       float(wx0), float(wy0), int(cell_step), nx, ny, tile, _p(best), _p(sc)))
+        return best, sc
+
     def match_eval(self, particle, pts, pose4, origin=None, quat=None, jac=True):
         """-> (residuals[n], Jacobian n x 3 or None): MatchSurface2D::eval on the particle's distance map, no robust weight"""
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -629,6 +651,7 @@ HOST_SYMBOLS = [
     "lama_slam_iterations", "lama_slam_device_context", "lama_slam_engine_origin", "lama_slam_deleted_patches", "lama_loc_create3",
     "lama_slam_view_bounds", "lama_slam_view_cells", "lama_slam_view_occupancy", "lama_slam_view_distance_cells", "lama_slam_view_distance_points",
     "lama_slam_match_eval", "lama_slam_match_solve", "lama_slam_match_solve_generic", "lama_slam_solve_batch",
+    "lama_slam_correlative_search", "lama_loc_relocalize", "lama_loc_relocalize_candidates",
     "lama_loc_create", "lama_loc_destroy", "lama_loc_last_error", "lama_loc_engine_origin", "lama_loc_set_obstacles_world",
     "lama_loc_write_distance_map", "lama_loc_read_distance_map", "lama_loc_device_context",
     "lama_loc_set_pose", "lama_loc_get_pose", "lama_loc_update", "lama_loc_covar", "lama_loc_rmse", "lama_loc_iterations",
@@ -678,6 +701,9 @@ def _bind_host(L):
         "lama_slam_match_solve": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, d, u32, vp, vp]),
         "lama_slam_match_solve_generic": (i32, [vp, vp, u32, vp, vp, vp, C.c_char_p, C.c_char_p, d, u32, vp, vp]),
         "lama_slam_solve_batch": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_char_p, d, C.c_char_p, d, vp, vp, vp]),
+        "lama_slam_correlative_search": (i32, [vp, vp, u32, vp, vp, vp, d, d, u32, u32, u32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "lama_loc_relocalize": (i32, [vp, vp, u32, vp, vp, d, d, u32, u32, u32, u32]),
+        "lama_loc_relocalize_candidates": (u32, [vp, u32, vp, vp, vp, vp, vp]),
         "lama_loc_create": (vp, [d, d, d, d, u32, i32, vp, i32]), "lama_loc_destroy": (None, [vp]),
         "lama_loc_last_error": (C.c_char_p, [vp]), "lama_loc_engine_origin": (C.c_char_p, [vp]),
         "lama_loc_set_obstacles_world": (i32, [vp, vp, u32]), "lama_loc_write_distance_map": (i32, [vp, C.c_char_p]), "lama_loc_read_distance_map": (i32, [vp, C.c_char_p]), "lama_loc_device_context": (vp, [vp]), "lama_loc_set_pose": (None, [vp, d, d, d]),
@@ -1062,6 +1088,26 @@ class Slam2D:
             raise LamaError(self.L.lama_slam_last_error(self.h).decode())
         return poses, cov.reshape(B, 3, 3), it, err
 
+    def correlative_search(self, pts, box_min, box_max, linear_step=0.2, angular_step=math.radians(5.0), point_step=0, tile=8, max_candidates=16,
+                           refine=True, refine_iterations=100, origin=None, quat=None):
+        """lama::CorrelativeSearch2D::search on getDistanceMap() over the box -> (dict of the candidates' arrays, sorted by rmse:
+        coarse (B, 4), score (B,), pose (B, 4), rmse (B,), iterations (B,); dict of the lattice: cell_step, nx, ny, headings,
+        point_step, tile)"""
+        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        box = np.array([box_min[0], box_min[1], box_max[0], box_max[1]], dtype=np.float64)
+        cap = int(max_candidates)
+        coarse, poses = np.zeros((cap, 4)), np.zeros((cap, 4))
+        score, it, rmse = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap)
+        lat, num = np.zeros(6, dtype=np.uint32), C.c_uint32(0)
+        rc = self.L.lama_slam_correlative_search(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(box), float(linear_step), float(angular_step),
+                                                 int(point_step), int(tile), cap, 1 if refine else 0, int(refine_iterations), cap, _p(coarse), _p(score),
+                                                 _p(poses), _p(rmse), _p(it), _p(lat), C.byref(num))
+        if rc < 0:
+            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+        B = min(num.value, cap)
+        return (dict(coarse=coarse[:B], score=score[:B], pose=poses[:B], rmse=rmse[:B], iterations=it[:B]),
+                dict(zip(("cell_step", "nx", "ny", "headings", "point_step", "tile"), (int(v) for v in lat))))
+
     def hip_context(self):
         ctx = HipContext.__new__(HipContext)
         ctx.L = _lib_of_origin(self.engine_origin())
@@ -1162,6 +1208,22 @@ class Loc2D:
 
     def global_localization_active(self):
         return bool(self.L.lama_loc_global_localization_active(self.h))
+
+    def relocalize(self, pts, linear_step=0.2, angular_step=math.radians(5.0), point_step=0, tile=8, max_candidates=16, refine_iterations=100,
+                   origin=None, quat=None):
+        """Loc2D::relocalize: lattice search over the occupancy map's bounds, free nodes only -> True when the pose was set"""
+        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        return bool(self._chk(self.L.lama_loc_relocalize(self.h, _p(pts), len(pts), _p(origin), _p(quat), float(linear_step), float(angular_step),
+                                                         int(point_step), int(tile), int(max_candidates), int(refine_iterations))))
+
+    def relocalize_candidates(self):
+        """the candidates of the last relocalize(), best first: dict of coarse (B, 4), score, pose (B, 4), rmse, iterations"""
+        B = self.L.lama_loc_relocalize_candidates(self.h, 0, None, None, None, None, None)
+        coarse, poses = np.zeros((B, 4)), np.zeros((B, 4))
+        score, it, rmse = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32), np.zeros(B)
+        if B:
+            self.L.lama_loc_relocalize_candidates(self.h, B, _p(coarse), _p(score), _p(poses), _p(rmse), _p(it))
+        return dict(coarse=coarse, score=score, pose=poses, rmse=rmse, iterations=it)
 
     def gloc_candidates(self):
         n = self.L.lama_loc_gloc_candidates(self.h, None, None, 0)

@@ -98,6 +98,7 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     e->map_integrate_scans = reinterpret_cast<decltype(e->map_integrate_scans)>(dlsym(dl, "lama_hip_map_integrate_scans"));
     e->map_occupied_cells = reinterpret_cast<decltype(e->map_occupied_cells)>(dlsym(dl, "lama_hip_map_occupied_cells"));
     e->match_solve_batch = reinterpret_cast<decltype(e->match_solve_batch)>(dlsym(dl, "lama_hip_match_solve_batch"));
+    e->match_search_lattice = reinterpret_cast<decltype(e->match_search_lattice)>(dlsym(dl, "lama_hip_match_search_lattice"));
     return e;
 }
 

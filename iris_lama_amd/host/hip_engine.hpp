@@ -55,6 +55,8 @@ struct HipEngine {
     decltype(&lama_hip_map_occupied_cells) map_occupied_cells = nullptr;
     // batched registration (lama::SolveBatch); optional in the same way: SolveBatch refuses to run on a library without it
     decltype(&lama_hip_match_solve_batch) match_solve_batch = nullptr;
+    // pose-lattice search (lama::CorrelativeSearch2D, Loc2D::relocalize); optional in the same way
+    decltype(&lama_hip_match_search_lattice) match_search_lattice = nullptr;
     ~HipEngine();
 };
 

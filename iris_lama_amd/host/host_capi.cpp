@@ -21,6 +21,7 @@
 #include "lama/pose_graph_2d.h"
 #include "lama/simple_pgo.h"
 #include "lama/map_builder_2d.h"
+#include "lama/correlative_search_2d.h"
 
 using namespace lama;
 
@@ -533,6 +534,53 @@ int lama_slam_solve_batch(lama_slam* h, lama_slam* other, uint32_t num_problems,
     } catch (const std::exception& e) { h->error = e.what(); return -2; }
 }
 
+namespace {
+CorrelativeSearch2D::Options correlative_options(double linear_step, double angular_step, uint32_t point_step, uint32_t tile, uint32_t max_candidates,
+                                                 bool refine, uint32_t refine_iterations)
+{
+    CorrelativeSearch2D::Options o;
+    o.linear_step = linear_step; o.angular_step = angular_step; o.point_step = point_step; o.tile = tile; o.max_candidates = max_candidates;
+    o.refine = refine; o.refine_iterations = refine_iterations;
+    return o;
+}
+uint32_t write_candidates(const std::vector<CorrelativeSearch2D::Candidate>& c, uint32_t cap, double* coarse4, uint32_t* scores, double* poses4, double* rmse,
+                          uint32_t* iterations)
+{
+    for (uint32_t i = 0; i < c.size() && i < cap; ++i) {
+        if (coarse4) c[i].coarse.state.toArray(coarse4 + 4 * (size_t)i);
+        if (poses4) c[i].pose.state.toArray(poses4 + 4 * (size_t)i);
+        if (scores) scores[i] = c[i].score;
+        if (rmse) rmse[i] = c[i].rmse;
+        if (iterations) iterations[i] = c[i].iterations;
+    }
+    return (uint32_t)c.size();
+}
+}
+
+int lama_slam_correlative_search(lama_slam* h, const double* pts, uint32_t n, const double* o, const double* q, const double* box4, double linear_step,
+                                 double angular_step, uint32_t point_step, uint32_t tile, uint32_t max_candidates, int refine, uint32_t refine_iterations,
+                                 uint32_t cap, double* coarse4, uint32_t* scores, double* poses4, double* rmse, uint32_t* iterations, uint32_t* lattice6,
+                                 uint32_t* num_out)
+{
+    try {
+        const DynamicDistanceMap* dm = h->s->getDistanceMap();
+        if (!dm) return -1;
+        const CorrelativeSearch2D cs(correlative_options(linear_step, angular_step, point_step, tile, max_candidates, refine != 0, refine_iterations));
+        const Vector2d bmin(box4[0], box4[1]), bmax(box4[2], box4[3]);
+        std::vector<CorrelativeSearch2D::Candidate> c;
+        try {
+            if (lattice6) {
+                const CorrelativeSearch2D::Lattice L = cs.lattice(dm->resolution, n, bmin, bmax);
+                lattice6[0] = L.cell_step; lattice6[1] = L.nx; lattice6[2] = L.ny; lattice6[3] = L.num_headings; lattice6[4] = L.point_step; lattice6[5] = L.tile;
+            }
+            c = cs.search(dm, cloud_of(pts, n, o, q), bmin, bmax);
+        } catch (const std::invalid_argument& e) { h->error = e.what(); return -3; }
+        const uint32_t count = write_candidates(c, cap, coarse4, scores, poses4, rmse, iterations);
+        if (num_out) *num_out = count;
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+
 int lama_slam_view_distance_points(lama_slam* h, uint64_t n, const double* xy, double* out)
 {
     try {
@@ -682,6 +730,17 @@ uint32_t lama_loc_sampling_likelihoods(const lama_loc* h, double* out, uint32_t 
     const uint32_t n = (uint32_t)h->l.lastSamplingLikelihoods().size();
     for (uint32_t i = 0; i < n && i < cap; ++i) out[i] = h->l.lastSamplingLikelihoods()[i];
     return n;
+}
+int lama_loc_relocalize(lama_loc* h, const double* pts, uint32_t n, const double* origin3, const double* quat, double linear_step, double angular_step,
+                        uint32_t point_step, uint32_t tile, uint32_t max_candidates, uint32_t refine_iterations)
+{
+    try {
+        return h->l.relocalize(make_cloud(pts, n, origin3, quat), correlative_options(linear_step, angular_step, point_step, tile, max_candidates, true, refine_iterations)) ? 1 : 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -1; }
+}
+uint32_t lama_loc_relocalize_candidates(const lama_loc* h, uint32_t cap, double* coarse4, uint32_t* scores, double* poses4, double* rmse, uint32_t* iterations)
+{
+    return write_candidates(h->l.lastRelocalizeCandidates(), cap, coarse4, scores, poses4, rmse, iterations);
 }
 // ------------------------------------------------------------------ LidarOdometry2D
 struct lama_lo {

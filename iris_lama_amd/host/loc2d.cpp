@@ -7,6 +7,7 @@
 #include <limits>
 #include <stdexcept>
 
+#include "correlative_impl.hpp"
 #include "covariance3.hpp"
 #include "dm_builder.hpp"
 #include "hip_engine.hpp"
@@ -172,6 +173,25 @@ bool Loc2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, do
 }
 
 void Loc2D::triggerGlobalLocalization() { do_global_localization_ = true; }      // :194-197
+
+// An addition: the lattice search of lama::CorrelativeSearch2D over the occupancy map's extent, on this object's context.
+bool Loc2D::relocalize(const PointCloudXYZ::Ptr& surface, const CorrelativeSearch2D::Options& options)
+{
+    if (!surface || surface->points.empty()) throw std::runtime_error("lama::Loc2D::relocalize: empty scan");
+    if (!distance_map || !occupancy_map) throw std::runtime_error("lama::Loc2D: Init() must be called first");
+    if (distance_map->hasPending()) distance_map->update();
+    ensureContext();
+    Vector3d mn, mx;
+    occupancy_map->bounds(mn, mx);
+    detail::CorrelativeDevice dev;
+    dev.engine = eng_.get(); dev.ctx = ctx_; dev.particle = 0; dev.resolution = distance_map->resolution;
+    const SimpleOccupancyMap* occ = occupancy_map;
+    reloc_ = detail::correlative_search(CorrelativeSearch2D(options), dev, *surface, Vector2d(mn[0], mn[1]), Vector2d(mx[0], mx[1]),
+                                        [occ](double x, double y) { return occ->isFree(Vector3d(x, y, 0.0)); });
+    if (reloc_.empty() || !(reloc_[0].rmse < opt_.gloc_thresh)) return false;
+    setPose(reloc_[0].pose);
+    return true;
+}
 
 // :249-286.  The candidates are drawn exactly like the reference (x, y until the cell is free in the occupancy map,
 // then the heading; lama::random's stream); their squared residual norms come from the device in one batch and the
