@@ -1,0 +1,51 @@
+// lama/device_context.h -- lama::DeviceContext: the device context of a host class (Slam2D, Loc2D, LidarOdometry2D, MapBuilder2D,
+// PFSlam2D), owned by type: created once, destroyed exactly once, and the one place that turns a refused device call into the
+// exception those classes throw.  Only forward declarations of the device C-ABI (include/lama_hip.h), like the class headers.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+struct lama_hip_ctx;
+struct lama_hip_cfg;
+
+namespace lama {
+
+struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
+
+class DeviceContext {
+public:
+    // layout of a downloaded patch (the reference's records): 32 x 32 cells of 10 bytes (distance_t) or 4 bytes
+    // (frequency / float log-odds), and one presence bit per cell
+    static constexpr size_t kCellsPerPatch = 1024, kMaskWordsPerPatch = 16, kDistanceCellBytes = 10, kOccupancyCellBytes = 4;
+
+    explicit DeviceContext(const char* owner) : owner_(owner) {}              // owner: "lama::Slam2D", ... (a string literal)
+    DeviceContext(DeviceContext&& o) noexcept : eng_(std::move(o.eng_)), ctx_(o.ctx_), owner_(o.owner_) { o.ctx_ = nullptr; }
+    DeviceContext& operator=(DeviceContext&& o) noexcept
+    {
+        if (this != &o) { reset(); eng_ = std::move(o.eng_); ctx_ = o.ctx_; owner_ = o.owner_; o.ctx_ = nullptr; }
+        return *this;
+    }
+    ~DeviceContext() { reset(); }
+
+    // a context of `engine` from cfg; throws std::runtime_error when the device library refuses (no device, unsupported options)
+    void create(std::shared_ptr<HipEngine> engine, const lama_hip_cfg& cfg);
+    void reset();                                                             // destroys the context, if any
+    explicit operator bool() const { return ctx_ != nullptr; }
+    lama_hip_ctx* get() const { return ctx_; }
+    const std::shared_ptr<HipEngine>& engine() const { return eng_; }
+    const HipEngine* operator->() const { return eng_.get(); }
+    // rc != 0: throws std::runtime_error "<owner>: <what> failed (status <rc>): <the context's last error>"
+    void check(int32_t rc, const char* what) const;
+    // one particle's map of a kind (LAMA_HIP_MAP_*) in the reference's record formats; true with empty arrays when it has no patch
+    bool download(uint32_t particle, int32_t kind, std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks) const;
+
+private:
+    std::shared_ptr<HipEngine> eng_;
+    lama_hip_ctx* ctx_ = nullptr;
+    const char* owner_;
+};
+
+} // namespace lama

@@ -14,14 +14,11 @@
 #include <memory>
 #include <vector>
 
+#include "device_context.h"
 #include "pose2d.h"
 #include "sdm_io.h"
 
-struct lama_hip_ctx;
-
 namespace lama {
-
-struct HipEngine;
 
 struct LidarOdometry2D {
     bool has_first_scan = false;
@@ -47,14 +44,12 @@ struct LidarOdometry2D {
     bool downloadOccupancyMap(sdm::HostMap& m) const;      // kind = kProbabilisticOccupancyMap: 4-byte float log-odds cells
     uint32_t getLastIterations() const { return last_iterations_; }
     uint32_t getLastDeletedPatches() const { return last_deleted_; }
-    lama_hip_ctx* deviceContext() const { return ctx_; }
-    const HipEngine* engine() const { return eng_.get(); }
+    lama_hip_ctx* deviceContext() const { return dev_.get(); }
+    const HipEngine* engine() const { return dev_.engine().get(); }
 
 private:
-    void fail(int32_t rc, const char* what) const;
     Options opt_;
-    std::shared_ptr<HipEngine> eng_;
-    lama_hip_ctx* ctx_ = nullptr;
+    DeviceContext dev_{"lama::LidarOdometry2D"};
     bool device_initialised_ = false;
     uint32_t last_iterations_ = 0, last_deleted_ = 0;
 };

@@ -19,15 +19,12 @@
 #include <vector>
 
 #include "correlative_search_2d.h"
+#include "device_context.h"
 #include "pose2d.h"
 #include "sdm/dynamic_distance_map.h"
 #include "sdm/simple_occupancy_map.h"
 
-struct lama_hip_ctx;
-
 namespace lama {
-
-struct HipEngine;
 
 class Loc2D {
 public:
@@ -73,19 +70,17 @@ public:
     uint32_t getLastIterations() const { return last_iterations_; }
     // true when the first build of the distance map was replayed on the host and uploaded (iris_lama_amd/host/dm_builder.hpp)
     bool distanceMapBuiltOnHost() const { return host_built_; }
-    lama_hip_ctx* deviceContext() const { return ctx_; }
-    const HipEngine* engine() const { return eng_.get(); }
+    lama_hip_ctx* deviceContext() const { return dev_.get(); }
+    const HipEngine* engine() const { return dev_.engine().get(); }
 
 private:
     void ensureContext();
     void solve(const PointCloudXYZ& surface, bool do_solve);
     void globalLocalization(const PointCloudXYZ& surface);
     void addSamplingCovariance(const PointCloudXYZ& surface);
-    void fail(int32_t rc, const char* what) const;
 
     Options opt_;
-    std::shared_ptr<HipEngine> eng_;
-    lama_hip_ctx* ctx_ = nullptr;
+    DeviceContext dev_{"lama::Loc2D"};       // outlives distance_map, whose writer works on it (deleted in the destructor's body)
     Pose2D odom_, pose_;
     Matrix3d cov_;
     double rmse_ = 0.0;

@@ -19,15 +19,12 @@
 #include <memory>
 #include <vector>
 
+#include "device_context.h"
 #include "pose2d.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
-struct lama_hip_ctx;
-
 namespace lama {
-
-struct HipEngine;
 
 class MapBuilder2D {
 public:
@@ -69,14 +66,12 @@ public:
     const FrequencyOccupancyMap* getOccupancyMap() const;
     const DynamicDistanceMap* getDistanceMap() const;
 
-    lama_hip_ctx* deviceContext() const { return ctx_; }
-    const HipEngine* engine() const { return eng_.get(); }
+    lama_hip_ctx* deviceContext() const { return dev_.get(); }
+    const HipEngine* engine() const { return dev_.engine().get(); }
 
 private:
-    void fail(int32_t rc, const char* what) const;
     Options opt_;
-    std::shared_ptr<HipEngine> eng_;
-    lama_hip_ctx* ctx_ = nullptr;
+    DeviceContext dev_{"lama::MapBuilder2D"};        // declared before dm_view_, which holds its raw handle: destroyed after it
     std::vector<Pose2D> poses_;
     std::vector<double> pts_, origins_, quats_;      // all key scans: points concatenated, per-scan sensor origin / orientation
     std::vector<uint32_t> offsets_{0u};

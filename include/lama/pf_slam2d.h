@@ -29,15 +29,12 @@
 #include <string>
 #include <vector>
 
+#include "device_context.h"
 #include "pose2d.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
-struct lama_hip_ctx;
-
 namespace lama {
-
-struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
 
 class PFSlam2D {
 public:
@@ -178,7 +175,7 @@ public:
             dm_view_.reset(new DynamicDistanceMap(std::move(m)));
             const uint32_t b = (uint32_t)getBestParticleIdx();
             const PFSlam2D* o = ownerOf(b);
-            dm_view_->bindDevice(o->eng_, o->ctx_, b - o->lo_);
+            dm_view_->bindDevice(o->dev_.engine(), o->dev_.get(), b - o->lo_);
         }
         return dm_view_.get();
     }
@@ -223,13 +220,11 @@ private:
     const PFSlam2D* ownerOf(uint32_t i) const;
     void syncDevice();
     double normal(double stddev);
-    void fail(int32_t rc, const char* what) const;
     void uploadLocalPoses();
     void scanToArrays(const PointCloudXYZ& s);
 
     Options options_;
-    std::shared_ptr<HipEngine> eng_;
-    lama_hip_ctx* ctx_ = nullptr;
+    DeviceContext dev_{"lama::PFSlam2D"};   // declared before dm_view_, which holds its raw handle: destroyed after it (gpus > 1: the shards have one each)
     std::mt19937 gen_;
     std::vector<Particle> particles_;       // all P (weights replicated on every shard)
     uint32_t lo_ = 0, hi_ = 0;              // locally owned block [lo, hi)

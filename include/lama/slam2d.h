@@ -14,15 +14,12 @@
 #include <string>
 #include <vector>
 
+#include "device_context.h"
 #include "pose2d.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
-struct lama_hip_ctx;
-
 namespace lama {
-
-struct HipEngine;
 
 class Slam2D {
 public:
@@ -101,7 +98,7 @@ public:
             sdm::HostMap m;
             if (!downloadDistanceMap(m)) return nullptr;
             dm_view_.reset(new DynamicDistanceMap(std::move(m)));
-            dm_view_->bindDevice(eng_, ctx_, 0u);
+            dm_view_->bindDevice(dev_.engine(), dev_.get(), 0u);
         }
         return dm_view_.get();
     }
@@ -116,15 +113,13 @@ public:
         occmem = o ? (uint64_t)o->patches() * 4096ull : 0; dmmem = d ? (uint64_t)d->patches() * 10240ull : 0;
         return occmem + dmmem;
     }
-    lama_hip_ctx* deviceContext() const { return ctx_; }
-    const HipEngine* engine() const { return eng_.get(); }
+    lama_hip_ctx* deviceContext() const { return dev_.get(); }
+    const HipEngine* engine() const { return dev_.engine().get(); }
 
 private:
-    void fail(int32_t rc, const char* what) const;
+    DeviceContext dev_{"lama::Slam2D"};                       // declared before dm_view_, which holds its raw handle: destroyed after it
     mutable std::unique_ptr<FrequencyOccupancyMap> occ_view_;
     mutable std::unique_ptr<DynamicDistanceMap> dm_view_;
-    std::shared_ptr<HipEngine> eng_;
-    lama_hip_ctx* ctx_ = nullptr;
     Pose2D odom_, pose_;
     double trans_thresh_, rot_thresh_;
     double resolution_ = 0.05, l2_max_ = 0.5, truncated_range_ = 0.0;

@@ -56,24 +56,47 @@ class HipCounters(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-HIP_SYMBOLS = [
-    "lama_hip_default_cfg", "lama_hip_device_count", "lama_hip_ctx_create", "lama_hip_ctx_destroy",
-    "lama_hip_last_error", "lama_hip_pf_init", "lama_hip_pf_set_poses", "lama_hip_pf_get_poses",
-    "lama_hip_pf_scan_match", "lama_hip_pf_resample", "lama_hip_pf_update_maps", "lama_hip_pf_map_patches",
-    "lama_hip_pf_download_map", "lama_hip_pf_upload_map", "lama_hip_match_batch", "lama_hip_pf_export_particle",
-    "lama_hip_pf_import_particle", "lama_hip_get_counters", "lama_hip_get_counters_sized", "lama_hip_counters_bytes", "lama_hip_reset_counters",
-    "lama_hip_map_add_obstacles", "lama_hip_match_solve", "lama_hip_eval_batch", "lama_hip_map_sample_likelihood",
-    "lama_hip_pgo_create", "lama_hip_pgo_destroy", "lama_hip_pgo_last_error", "lama_hip_pgo_linearize",
-    "lama_hip_pf_patch_ids", "lama_hip_pf_delete_patches", "lama_hip_pf_update_maps_begin", "lama_hip_sync", "lama_hip_ctx_device",
-    "lama_hip_pf_map_checksums", "lama_hip_match_eval", "lama_hip_match_cell_distances", "lama_hip_match_solve_with",
-    "lama_hip_blob_alloc", "lama_hip_blob_free", "lama_hip_blob_copy", "lama_hip_pf_export_particles", "lama_hip_pf_import_particles",
-    "lama_hip_pgo_pattern", "lama_hip_pgo_set_poses", "lama_hip_pgo_get_poses", "lama_hip_pgo_linearize_system",
-    "lama_hip_pgo_try_step", "lama_hip_pgo_accept",
-    "lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells",
-    "lama_hip_match_solve_batch", "lama_hip_match_search_lattice",
-    "lama_hip_pgo_solve_pcg", "lama_hip_pgo_try_solved_step",
-    "lama_hip_pgo_create_robust", "lama_hip_pgo_factor_weights",
-]
+def _hip_signatures():
+    vp, i32, u32, u64, d = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
+    required = {
+        "lama_hip_default_cfg": [vp], "lama_hip_device_count": [vp], "lama_hip_ctx_create": [vp, vp], "lama_hip_ctx_destroy": [vp],
+        "lama_hip_last_error": [vp], "lama_hip_pf_init": [vp, vp, u32, vp, vp, vp], "lama_hip_pf_set_poses": [vp, vp],
+        "lama_hip_pf_get_poses": [vp, vp], "lama_hip_pf_scan_match": [vp, vp, u32, vp, vp, vp, vp, vp], "lama_hip_pf_resample": [vp, vp],
+        "lama_hip_pf_update_maps": [vp, vp, u32, vp, vp], "lama_hip_pf_update_maps_begin": [vp, vp, u32, vp, vp], "lama_hip_sync": [vp],
+        "lama_hip_ctx_device": [vp], "lama_hip_pf_map_patches": [vp, u32, i32, vp],
+        "lama_hip_pf_download_map": [vp, u32, i32, u32, vp, vp, vp, vp], "lama_hip_pf_upload_map": [vp, u32, i32, u32, vp, vp, vp],
+        "lama_hip_match_batch": [vp, u32, vp, u32, vp, vp, vp, u32, vp], "lama_hip_pf_export_particle": [vp, u32, vp, u64, vp],
+        "lama_hip_pf_import_particle": [vp, u32, vp, u64], "lama_hip_pf_export_particles": [vp, u32, vp, vp, vp, vp],
+        "lama_hip_pf_import_particles": [vp, u32, vp, vp, vp], "lama_hip_get_counters": [vp, vp], "lama_hip_get_counters_sized": [vp, vp, u32],
+        "lama_hip_counters_bytes": [], "lama_hip_reset_counters": [vp], "lama_hip_map_add_obstacles": [vp, u32, vp, u32],
+        "lama_hip_match_solve": [vp, u32, vp, u32, vp, vp, vp, vp, vp, i32], "lama_hip_eval_batch": [vp, u32, vp, u32, vp, vp, vp, u32, vp, vp],
+        "lama_hip_pf_patch_ids": [vp, u32, i32, u32, vp, vp], "lama_hip_pf_delete_patches": [vp, u32, vp, u32, vp],
+        "lama_hip_map_sample_likelihood": [vp, u32, vp, u32, vp, vp, d, vp, u32, u32, vp],
+        "lama_hip_match_eval": [vp, u32, vp, u32, vp, vp, vp, vp, vp], "lama_hip_match_cell_distances": [vp, u32, vp, u32, vp, vp, vp, vp],
+        "lama_hip_match_solve_with": [vp, u32, vp, u32, vp, vp, vp, vp, vp, i32, u32],
+        "lama_hip_blob_alloc": [vp, u64, vp], "lama_hip_blob_free": [vp, vp], "lama_hip_blob_copy": [vp, vp, vp, vp, u64],
+    }
+    # groups the engine test double (tests/cpu_engine) may lack: a library has a whole group or none of it, probed by its first name
+    optional = [
+        {"lama_hip_map_integrate_scans": [vp, u32, u32, vp, vp, vp, vp, vp, u32], "lama_hip_map_occupied_cells": [vp, u32, u32, vp, vp]},
+        {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
+        {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
+        {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
+        {"lama_hip_pgo_create": [i32, u32, vp, vp, vp, vp, u32, vp], "lama_hip_pgo_destroy": [vp], "lama_hip_pgo_last_error": [vp],
+         "lama_hip_pgo_linearize": [vp, vp, vp, vp, vp, vp, vp, vp], "lama_hip_pgo_pattern": [vp, vp, vp, vp], "lama_hip_pgo_set_poses": [vp, vp],
+         "lama_hip_pgo_get_poses": [vp, vp], "lama_hip_pgo_linearize_system": [vp, vp, vp, vp, vp, vp], "lama_hip_pgo_try_step": [vp, vp, vp, vp],
+         "lama_hip_pgo_accept": [vp], "lama_hip_pgo_solve_pcg": [vp, d, d, u32, u32, vp, vp, vp, vp, vp, vp],
+         "lama_hip_pgo_try_solved_step": [vp, vp, vp], "lama_hip_pgo_create_robust": [i32, u32, vp, vp, vp, vp, vp, vp, u32, vp],
+         "lama_hip_pgo_factor_weights": [vp, vp]},
+    ]
+    # every other entry point returns an int32_t status
+    restypes = {"lama_hip_default_cfg": None, "lama_hip_ctx_destroy": None, "lama_hip_last_error": C.c_char_p, "lama_hip_pgo_destroy": None,
+                "lama_hip_pgo_last_error": C.c_char_p}
+    return required, optional, restypes
+
+
+_HIP_REQUIRED, _HIP_OPTIONAL, _HIP_RESTYPES = _hip_signatures()
+HIP_SYMBOLS = list(_HIP_REQUIRED) + [name for group in _HIP_OPTIONAL for name in group]
 
 _hip = None
 _hip_wide = None
@@ -143,93 +166,11 @@ def hip_lib_or_none():
 
 
 def _bind_hip(L):
-    if True:
-        vp, i32, u32, u64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64
-        L.lama_hip_default_cfg.argtypes = [vp]
-        L.lama_hip_default_cfg.restype = None
-        L.lama_hip_device_count.argtypes = [vp]
-        L.lama_hip_ctx_create.argtypes = [vp, vp]
-        L.lama_hip_ctx_destroy.argtypes = [vp]
-        L.lama_hip_ctx_destroy.restype = None
-        L.lama_hip_last_error.argtypes = [vp]
-        L.lama_hip_last_error.restype = C.c_char_p
-        L.lama_hip_pf_init.argtypes = [vp, vp, u32, vp, vp, vp]
-        L.lama_hip_pf_set_poses.argtypes = [vp, vp]
-        L.lama_hip_pf_get_poses.argtypes = [vp, vp]
-        L.lama_hip_pf_scan_match.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
-        L.lama_hip_pf_resample.argtypes = [vp, vp]
-        L.lama_hip_pf_update_maps.argtypes = [vp, vp, u32, vp, vp]
-        L.lama_hip_pf_update_maps_begin.argtypes = [vp, vp, u32, vp, vp]
-        L.lama_hip_sync.argtypes = [vp]
-        L.lama_hip_ctx_device.argtypes = [vp]
-        L.lama_hip_ctx_device.restype = C.c_int32
-        L.lama_hip_pf_map_patches.argtypes = [vp, u32, i32, vp]
-        L.lama_hip_pf_download_map.argtypes = [vp, u32, i32, u32, vp, vp, vp, vp]
-        L.lama_hip_pf_upload_map.argtypes = [vp, u32, i32, u32, vp, vp, vp]
-        L.lama_hip_match_batch.argtypes = [vp, u32, vp, u32, vp, vp, vp, u32, vp]
-        L.lama_hip_pf_export_particle.argtypes = [vp, u32, vp, u64, vp]
-        L.lama_hip_pf_import_particle.argtypes = [vp, u32, vp, u64]
-        L.lama_hip_pf_export_particles.argtypes = [vp, u32, vp, vp, vp, vp]
-        L.lama_hip_pf_import_particles.argtypes = [vp, u32, vp, vp, vp]
-        L.lama_hip_get_counters.argtypes = [vp, vp]
-        L.lama_hip_get_counters_sized.argtypes = [vp, vp, u32]
-        L.lama_hip_counters_bytes.argtypes = []
-        L.lama_hip_counters_bytes.restype = C.c_uint32
-        L.lama_hip_reset_counters.argtypes = [vp]
-        L.lama_hip_map_add_obstacles.argtypes = [vp, u32, vp, u32]
-        L.lama_hip_match_solve.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, i32]
-        L.lama_hip_eval_batch.argtypes = [vp, u32, vp, u32, vp, vp, vp, u32, vp, vp]
-        L.lama_hip_pf_patch_ids.argtypes = [vp, u32, i32, u32, vp, vp]
-        L.lama_hip_pf_delete_patches.argtypes = [vp, u32, vp, u32, vp]
-        L.lama_hip_map_sample_likelihood.argtypes = [vp, u32, vp, u32, vp, vp, C.c_double, vp, u32, u32, vp]
-        L.lama_hip_match_eval.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp]
-        L.lama_hip_match_cell_distances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
-        L.lama_hip_match_solve_with.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, i32, u32]
-        has_mb = hasattr(L, "lama_hip_map_integrate_scans")   # map rebuild from key scans (absent from the engine test double)
-        if has_mb:
-            L.lama_hip_map_integrate_scans.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32]
-            L.lama_hip_map_occupied_cells.argtypes = [vp, u32, u32, vp, vp]
-        has_msb = hasattr(L, "lama_hip_match_solve_batch")   # batched registration (absent from the engine test double)
-        if has_msb:
-            L.lama_hip_match_solve_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_double, vp, vp, vp]
-        has_csl = hasattr(L, "lama_hip_match_search_lattice")   # pose-lattice search (absent from the engine test double)
-        if has_csl:
-            L.lama_hip_match_search_lattice.argtypes = [vp, u32, vp, u32, vp, vp, u32, vp, u32, C.c_double, C.c_double, u32, u32, u32, u32, vp, vp]
-        has_cks = hasattr(L, "lama_hip_pf_map_checksums")   # device-only diagnostic (absent from the engine test double)
-        if has_cks:
-            L.lama_hip_pf_map_checksums.argtypes = [vp, i32, vp]
-        has_pgo = hasattr(L, "lama_hip_pgo_create")       # the engine test double (tests/cpu_engine) has no pose-graph part
-        if has_pgo:
-            L.lama_hip_pgo_create.argtypes = [i32, u32, vp, vp, vp, vp, u32, vp]
-            L.lama_hip_pgo_destroy.argtypes = [vp]
-            L.lama_hip_pgo_destroy.restype = None
-            L.lama_hip_pgo_last_error.argtypes = [vp]
-            L.lama_hip_pgo_last_error.restype = C.c_char_p
-            L.lama_hip_pgo_linearize.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-            L.lama_hip_pgo_pattern.argtypes = [vp, vp, vp, vp]
-            L.lama_hip_pgo_set_poses.argtypes = [vp, vp]
-            L.lama_hip_pgo_get_poses.argtypes = [vp, vp]
-            L.lama_hip_pgo_linearize_system.argtypes = [vp, vp, vp, vp, vp, vp]
-            L.lama_hip_pgo_try_step.argtypes = [vp, vp, vp, vp]
-            L.lama_hip_pgo_accept.argtypes = [vp]
-            L.lama_hip_pgo_solve_pcg.argtypes = [vp, C.c_double, C.c_double, u32, u32, vp, vp, vp, vp, vp, vp]
-            L.lama_hip_pgo_try_solved_step.argtypes = [vp, vp, vp]
-            L.lama_hip_pgo_create_robust.argtypes = [i32, u32, vp, vp, vp, vp, vp, vp, u32, vp]
-            L.lama_hip_pgo_factor_weights.argtypes = [vp, vp]
-        for s in HIP_SYMBOLS:
-            if s.startswith("lama_hip_pgo_") and not has_pgo:
-                continue
-            if s == "lama_hip_pf_map_checksums" and not has_cks:
-                continue
-            if s in ("lama_hip_map_integrate_scans", "lama_hip_map_occupied_cells") and not has_mb:
-                continue
-            if s == "lama_hip_match_solve_batch" and not has_msb:
-                continue
-            if s == "lama_hip_match_search_lattice" and not has_csl:
-                continue
-            if s not in ("lama_hip_default_cfg", "lama_hip_ctx_destroy", "lama_hip_last_error", "lama_hip_pgo_destroy",
-                         "lama_hip_pgo_last_error"):
-                getattr(L, s).restype = i32
+    for group in [_HIP_REQUIRED] + [g for g in _HIP_OPTIONAL if hasattr(L, next(iter(g)))]:
+        for name, argtypes in group.items():
+            f = getattr(L, name)
+            f.argtypes = argtypes
+            f.restype = _HIP_RESTYPES.get(name, C.c_int32)
 
 
 def _p(a):
@@ -292,8 +233,50 @@ def device_count():
     return n.value
 
 
-class HipContext:
+class _Handle:
+    """A native handle `h` of the library `L`: the names of its destroy and last-error entry points and -- for the host classes --
+    of the accessor of the device context, whose particle count is `_ctx_P`."""
+    _destroy = _last_error = _context = None
+    _ctx_P = 1
+
+    def close(self):
+        if getattr(self, "h", None) and not getattr(self, "_is_borrowed", False):
+            getattr(self.L, self._destroy)(self.h)
+        self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _error(self):
+        return getattr(self.L, self._last_error)(self.h).decode()
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise LamaError(self._error())
+        return rc
+
+    @staticmethod
+    def _scan(pts, origin, quat):
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        origin = np.ascontiguousarray(_Z3 if origin is None else origin, dtype=np.float64)
+        quat = np.ascontiguousarray(_IDQ if quat is None else quat, dtype=np.float64)
+        return pts, origin, quat
+
+    def hip_context(self):
+        """Borrowed HipContext view of the object's device context (export/import, counters, map downloads): closing it leaves the
+        context to its owner."""
+        ctx = HipContext.__new__(HipContext)
+        ctx.L = _lib_of_origin(self.engine_origin())
+        ctx.cfg = None
+        ctx.P = self._ctx_P
+        ctx.h = C.c_void_p(getattr(self.L, self._context)(self.h))
+        ctx._is_borrowed = True
+        return ctx
+
+
+class HipContext(_Handle):
     """One device context = one shard of the particle pool (include/lama_hip.h)."""
+    _destroy, _last_error = "lama_hip_ctx_destroy", "lama_hip_last_error"
 
     def __init__(self, cfg):
         self.L = hip_lib(wide=needs_wide(cfg.l2_max, cfg.resolution))
@@ -305,24 +288,9 @@ class HipContext:
             raise LamaError(f"lama_hip_ctx_create failed with status {rc} (no usable HIP device or invalid cfg)")
         self.h = h
 
-    def close(self):
-        if getattr(self, "h", None) and not getattr(self, "_is_borrowed", False):
-            self.L.lama_hip_ctx_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        self.close()
-
     def _chk(self, rc):
         if rc != 0:
-            raise LamaError(f"status {rc}: {self.L.lama_hip_last_error(self.h).decode()}")
-
-    @staticmethod
-    def _scan(pts, origin, quat):
-        pts = np.ascontiguousarray(pts, dtype=np.float64)
-        origin = np.ascontiguousarray(_Z3 if origin is None else origin, dtype=np.float64)
-        quat = np.ascontiguousarray(_IDQ if quat is None else quat, dtype=np.float64)
-        return pts, origin, quat
+            raise LamaError(f"status {rc}: {self._error()}")
 
     def init(self, pts, pose0, origin=None, quat=None):
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -779,8 +747,9 @@ def pose_from_xyr(x, y, yaw):
     return out
 
 
-class PFSlam2D:
+class PFSlam2D(_Handle):
     """ctypes view of the host-side lama::PFSlam2D (include/lama/pf_slam2d.h)."""
+    _destroy, _last_error, _context = "lama_pf_destroy", "lama_pf_last_error", "lama_pf_device_context"
 
     def __init__(self, opts):
         self.L = _hostlib()
@@ -794,32 +763,13 @@ class PFSlam2D:
         lo, hi = C.c_uint32(0), C.c_uint32(0)
         self.L.lama_pf_local_range(self.h, C.byref(lo), C.byref(hi))
         self.lo, self.hi = lo.value, hi.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lama_pf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise LamaError(self.L.lama_pf_last_error(self.h).decode())
-        return rc
+        self._ctx_P = self.hi - self.lo                       # hip_context() views the local shard
 
     def engine_origin(self):
         return self.L.lama_pf_engine_origin(self.h).decode()
 
     def set_prior(self, x, y, yaw):
         self.L.lama_pf_set_prior(self.h, float(x), float(y), float(yaw))
-
-    @staticmethod
-    def _scan(pts, origin, quat):
-        pts = np.ascontiguousarray(pts, dtype=np.float64)
-        origin = np.ascontiguousarray(_Z3 if origin is None else origin, dtype=np.float64)
-        quat = np.ascontiguousarray(_IDQ if quat is None else quat, dtype=np.float64)
-        return pts, origin, quat
 
     def update(self, pts, odom_xyr, ts=0.0, origin=None, quat=None):
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -931,16 +881,6 @@ class PFSlam2D:
         self.L.lama_pf_resample_indices(self.h, float(u), _p(out))
         return out
 
-    def hip_context(self):
-        """Borrowed HipContext view of the local shard's device context (export/import, counters, maps)."""
-        ctx = HipContext.__new__(HipContext)
-        ctx.L = _lib_of_origin(self.engine_origin())
-        ctx.cfg = None
-        ctx.P = self.hi - self.lo
-        ctx.h = C.c_void_p(self.device_context())
-        ctx._is_borrowed = True
-        return ctx
-
 
 class SlamOptions(C.Structure):
     _fields_ = [("trans_thresh", C.c_double), ("rot_thresh", C.c_double), ("l2_max", C.c_double),
@@ -949,8 +889,9 @@ class SlamOptions(C.Structure):
                 ("lm", C.c_int32)]
 
 
-class Slam2D:
+class Slam2D(_Handle):
     """ctypes view of the host-side lama::Slam2D (include/lama/slam2d.h): online SLAM, one pose + one map pair."""
+    _destroy, _last_error, _context = "lama_slam_destroy", "lama_slam_last_error", "lama_slam_device_context"
 
     def __init__(self, **kw):
         self.L = _hostlib()
@@ -963,14 +904,6 @@ class Slam2D:
         if not h:
             raise LamaError(err.value.decode())
         self.h = C.c_void_p(h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lama_slam_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     def deleted_patches(self):
         return self.L.lama_slam_deleted_patches(self.h)
@@ -987,11 +920,11 @@ class Slam2D:
         return out
 
     def update(self, pts, odom_xyr, ts=0.0, origin=None, quat=None):
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         od = np.ascontiguousarray(odom_xyr, dtype=np.float64)
         rc = self.L.lama_slam_update(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(od), float(ts))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         return bool(rc)
 
     def enough_motion(self, odom_xyr):
@@ -1040,35 +973,35 @@ class Slam2D:
 
     # ---- lama::MatchSurface2D / lama::Solve on Slam2D::getDistanceMap() (include/lama/match_surface_2d.h, nlls/solver.h)
     def match_eval(self, pts, pose4, origin=None, quat=None, jac=True):
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         n = len(pts)
         r, J, rmse = np.zeros(n), (np.zeros((3, n)) if jac else None), C.c_double(0)
         rc = self.L.lama_slam_match_eval(self.h, _p(pts), n, _p(origin), _p(quat), _p(np.ascontiguousarray(pose4, dtype=np.float64)),
                                          _p(r), _p(J), C.byref(rmse))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         return r, (J.T.copy() if jac else None), rmse.value
 
     def match_solve(self, pts, pose4, strategy="gn", weight="cauchy", weight_param=0.15, max_iterations=100, origin=None, quat=None):
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         pose = np.array(pose4, dtype=np.float64)
         cov, it = np.zeros(9), C.c_uint32(0)
         rc = self.L.lama_slam_match_solve(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), strategy.encode(), weight.encode(),
                                           float(weight_param), int(max_iterations), _p(cov), C.byref(it))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         return pose, cov.reshape(3, 3), it.value
 
     def match_solve_generic(self, pts, pose4, strategy="gn", weight="cauchy", weight_param=0.15, max_iterations=100, origin=None, quat=None):
         """The same problem through lama::Solver's generic host loop (per-beam evaluation on the device, everything else on the
         host): any of "unit", "tukey", "tdist", "cauchy", "huber" -> (pose, covariance, iterations)"""
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         pose = np.array(pose4, dtype=np.float64)
         cov, it = np.zeros(9), C.c_uint32(0)
         rc = self.L.lama_slam_match_solve_generic(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), strategy.encode(), weight.encode(),
                                                   float(weight_param), int(max_iterations), _p(cov), C.byref(it))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         return pose, cov.reshape(3, 3), it.value
 
     def solve_batch(self, scans, poses4, strategy="gn", weight="huber", weight_param=0.15, max_iterations=None, origins=None, quats=None,
@@ -1085,7 +1018,7 @@ class Slam2D:
         rc = self.L.lama_slam_solve_batch(self.h, other.h if other is not None else None, B, _p(pts), _p(offs), _p(origins), _p(quats), _p(poses),
                                           _p(mi), strategy.encode(), float(eps1), weight.encode(), float(weight_param), _p(cov), _p(it), _p(err))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         return poses, cov.reshape(B, 3, 3), it, err
 
     def correlative_search(self, pts, box_min, box_max, linear_step=0.2, angular_step=math.radians(5.0), point_step=0, tile=8, max_candidates=16,
@@ -1093,7 +1026,7 @@ class Slam2D:
         """lama::CorrelativeSearch2D::search on getDistanceMap() over the box -> (dict of the candidates' arrays, sorted by rmse:
         coarse (B, 4), score (B,), pose (B, 4), rmse (B,), iterations (B,); dict of the lattice: cell_step, nx, ny, headings,
         point_step, tile)"""
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         box = np.array([box_min[0], box_min[1], box_max[0], box_max[1]], dtype=np.float64)
         cap = int(max_candidates)
         coarse, poses = np.zeros((cap, 4)), np.zeros((cap, 4))
@@ -1103,23 +1036,15 @@ class Slam2D:
                                                  int(point_step), int(tile), cap, 1 if refine else 0, int(refine_iterations), cap, _p(coarse), _p(score),
                                                  _p(poses), _p(rmse), _p(it), _p(lat), C.byref(num))
         if rc < 0:
-            raise LamaError(self.L.lama_slam_last_error(self.h).decode())
+            raise LamaError(self._error())
         B = min(num.value, cap)
         return (dict(coarse=coarse[:B], score=score[:B], pose=poses[:B], rmse=rmse[:B], iterations=it[:B]),
                 dict(zip(("cell_step", "nx", "ny", "headings", "point_step", "tile"), (int(v) for v in lat))))
 
-    def hip_context(self):
-        ctx = HipContext.__new__(HipContext)
-        ctx.L = _lib_of_origin(self.engine_origin())
-        ctx.cfg = None
-        ctx.P = 1
-        ctx.h = C.c_void_p(self.L.lama_slam_device_context(self.h))
-        ctx._is_borrowed = True
-        return ctx
 
-
-class Loc2D:
+class Loc2D(_Handle):
     """ctypes view of the host-side lama::Loc2D (include/lama/loc2d.h): localisation on a fixed distance map."""
+    _destroy, _last_error, _context = "lama_loc_destroy", "lama_loc_last_error", "lama_loc_device_context"
 
     def __init__(self, trans_thresh=0.5, rot_thresh=0.5, l2_max=1.0, resolution=0.05, max_iter=100, gpu_device=0,
                  gloc_particles=3000, gloc_iters=10, gloc_thresh=0.15, cov_blend=0.0, strategy="gn"):
@@ -1131,19 +1056,6 @@ class Loc2D:
             raise LamaError(err.value.decode())
         self.h = C.c_void_p(h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lama_loc_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise LamaError(self.L.lama_loc_last_error(self.h).decode())
-        return rc
-
     def engine_origin(self):
         return self.L.lama_loc_engine_origin(self.h).decode()
 
@@ -1153,16 +1065,6 @@ class Loc2D:
 
     def write_distance_map(self, filename):
         self._chk(self.L.lama_loc_write_distance_map(self.h, str(filename).encode()))
-
-    def hip_context(self):
-        """Borrowed HipContext view of the device context (map downloads in tests)."""
-        ctx = HipContext.__new__(HipContext)
-        ctx.L = _lib_of_origin(self.engine_origin())
-        ctx.cfg = None
-        ctx.P = 1
-        ctx.h = C.c_void_p(self.L.lama_loc_device_context(self.h))
-        ctx._is_borrowed = True
-        return ctx
 
     def read_distance_map(self, filename):
         """distance_map->read(file): the file's patches replace the device map (no addObstacle / update() replay)."""
@@ -1177,7 +1079,7 @@ class Loc2D:
         return out
 
     def update(self, pts, odom_xyr, ts=0.0, force=False, origin=None, quat=None):
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         od = np.ascontiguousarray(odom_xyr, dtype=np.float64)
         return bool(self._chk(self.L.lama_loc_update(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(od), float(ts), 1 if force else 0)))
 
@@ -1212,7 +1114,7 @@ class Loc2D:
     def relocalize(self, pts, linear_step=0.2, angular_step=math.radians(5.0), point_step=0, tile=8, max_candidates=16, refine_iterations=100,
                    origin=None, quat=None):
         """Loc2D::relocalize: lattice search over the occupancy map's bounds, free nodes only -> True when the pose was set"""
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         return bool(self._chk(self.L.lama_loc_relocalize(self.h, _p(pts), len(pts), _p(origin), _p(quat), float(linear_step), float(angular_step),
                                                          int(point_step), int(tile), int(max_candidates), int(refine_iterations))))
 
@@ -1555,8 +1457,9 @@ def pose_graph_optimize(nodes, factors, device=0, solver=None, pcg_rel_tol=1e-10
     return rc == 1, out, r
 
 
-class LidarOdometry2D:
+class LidarOdometry2D(_Handle):
     """ctypes view of the host-side lama::LidarOdometry2D (include/lama/lidar_odometry_2d.h)."""
+    _destroy, _last_error, _context = "lama_lo_destroy", "lama_lo_last_error", "lama_lo_device_context"
 
     def __init__(self, resolution=0.05, max_iter=100, gpu_device=0):
         self.L = _hostlib()
@@ -1566,23 +1469,12 @@ class LidarOdometry2D:
             raise LamaError(err.value.decode())
         self.h = C.c_void_p(h)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lama_lo_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
     def engine_origin(self):
         return self.L.lama_lo_engine_origin(self.h).decode()
 
     def update(self, pts, ts=0.0, origin=None, quat=None):
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
-        rc = self.L.lama_lo_update(self.h, _p(pts), len(pts), _p(origin), _p(quat), float(ts))
-        if rc < 0:
-            raise LamaError(self.L.lama_lo_last_error(self.h).decode())
-        return bool(rc)
+        pts, origin, quat = self._scan(pts, origin, quat)
+        return bool(self._chk(self.L.lama_lo_update(self.h, _p(pts), len(pts), _p(origin), _p(quat), float(ts))))
 
     def odom(self):
         out = np.zeros(4)
@@ -1595,24 +1487,15 @@ class LidarOdometry2D:
     def deleted_patches(self):
         return self.L.lama_lo_deleted_patches(self.h)
 
-    def hip_context(self):
-        """Borrowed HipContext view of the device context (map downloads in tests)."""
-        ctx = HipContext.__new__(HipContext)
-        ctx.L = _lib_of_origin(self.engine_origin())
-        ctx.cfg = None
-        ctx.P = 1
-        ctx.h = C.c_void_p(self.L.lama_lo_device_context(self.h))
-        ctx._is_borrowed = True
-        return ctx
-
 
 class MapBuilderOptions(C.Structure):
     _fields_ = [("resolution", C.c_double), ("l2_max", C.c_double), ("patch_size", C.c_uint32), ("full", C.c_int32), ("prune", C.c_int32),
                 ("gpu_device", C.c_int32), ("window_patches", C.c_uint32), ("occ_patch_capacity", C.c_uint32), ("dm_patch_capacity", C.c_uint32)]
 
 
-class MapBuilder2D:
+class MapBuilder2D(_Handle):
     """ctypes view of the host-side lama::MapBuilder2D (include/lama/map_builder_2d.h): a map rebuilt from posed key scans."""
+    _destroy, _last_error, _context = "lama_mapbuilder_destroy", "lama_mapbuilder_last_error", "lama_mapbuilder_device_context"
 
     def __init__(self, **kw):
         self.L = _hostlib()
@@ -1625,19 +1508,6 @@ class MapBuilder2D:
         if not h:
             raise LamaError(err.value.decode())
         self.h = C.c_void_p(h)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.lama_mapbuilder_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise LamaError(self.L.lama_mapbuilder_last_error(self.h).decode())
-        return rc
 
     def engine_origin(self):
         return self.L.lama_mapbuilder_engine_origin(self.h).decode()
@@ -1685,20 +1555,10 @@ class MapBuilder2D:
 
     def match_solve(self, pts, pose4, max_iterations=100, origin=None, quat=None):
         """lama::Solve(GaussNewton + Cauchy(0.15)) of MatchSurface2D on getDistanceMap() -> (pose4, iterations)"""
-        pts, origin, quat = PFSlam2D._scan(pts, origin, quat)
+        pts, origin, quat = self._scan(pts, origin, quat)
         pose = np.ascontiguousarray(pose4, dtype=np.float64).copy()
         it = C.c_uint32(0)
         rc = self.L.lama_mapbuilder_match_solve(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), int(max_iterations), C.byref(it))
         if rc != 0:
-            raise LamaError(self.L.lama_mapbuilder_last_error(self.h).decode() or "no distance map")
+            raise LamaError(self._error() or "no distance map")
         return pose, it.value
-
-    def hip_context(self):
-        """Borrowed HipContext view of the device context (map downloads in tests)."""
-        ctx = HipContext.__new__(HipContext)
-        ctx.L = _lib_of_origin(self.engine_origin())
-        ctx.cfg = None
-        ctx.P = 1
-        ctx.h = C.c_void_p(self.L.lama_mapbuilder_device_context(self.h))
-        ctx._is_borrowed = True
-        return ctx

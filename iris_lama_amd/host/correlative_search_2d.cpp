@@ -48,8 +48,7 @@ std::vector<CorrelativeSearch2D::Candidate> correlative_search(const Correlative
     const uint32_t H = L.num_headings, tile = L.tile;
     if (tile == 0) throw std::invalid_argument("lama::CorrelativeSearch2D: tile is at least 1");
     auto refuse = [&](int32_t rc, const char* what) {
-        const char* msg = dev.engine->last_error ? dev.engine->last_error(dev.ctx) : "";
-        const std::string text = std::string("lama::CorrelativeSearch2D: ") + what + " failed (status " + std::to_string(rc) + "): " + (msg ? msg : "");
+        const std::string text = deviceFailure(*dev.engine, dev.ctx, "lama::CorrelativeSearch2D", what, rc);
         if (rc == LAMA_HIP_E_INVALID) throw std::invalid_argument(text);
         throw std::runtime_error(text);
     };

@@ -70,6 +70,10 @@ std::shared_ptr<HipEngine> defaultEngine();
 // 255 cells the reference's uint16_t sqdist can hold, liblama_hip_wide.so (the same sources compiled with -DLAMA_WIDE_DM: a 4-byte
 // distance plane, 9-bit obstacle offsets in the queue entries; csrc/lama_dev.h).  More than 255 cells is refused by ctx_create.
 std::shared_ptr<HipEngine> defaultEngine(double l2_max, double resolution);
+// The context's last error (never null), and the text the host classes throw for a device call that returned rc != 0:
+// "<who>: <what> failed (status <rc>): <last error>" (device_context.cpp).
+const char* lastDeviceError(const HipEngine& e, const lama_hip_ctx* ctx);
+std::string deviceFailure(const HipEngine& e, const lama_hip_ctx* ctx, const char* who, const char* what, int32_t rc);
 #ifdef LAMA_TESTING
 // Test builds of the host library only (-DLAMA_TESTING, tests/cpu_engine/Makefile): an engine that the objects constructed
 // afterwards bind instead (nullptr = default loader).  The shipped liblama_host.so is compiled without it.

@@ -3,7 +3,6 @@
 
 #include <cmath>
 #include <algorithm>
-#include <cstdio>
 #include <limits>
 #include <stdexcept>
 
@@ -27,7 +26,7 @@ void Loc2D::Init(const Options& o)
     opt_ = o;
     // a second Init() (new map, resolution, l2_max or strategy) starts from fresh maps like the reference's (src/loc2d.cpp:61-78):
     // the device context is rebuilt from the new options by the next ensureContext()
-    if (ctx_) { eng_->ctx_destroy(ctx_); ctx_ = nullptr; }
+    dev_.reset();
     delete occupancy_map; delete distance_map;
     occupancy_map = new SimpleOccupancyMap(o.resolution, o.patch_size);                // src/loc2d.cpp:63-66
     distance_map = new DynamicDistanceMap(o.resolution, o.patch_size);
@@ -38,24 +37,20 @@ void Loc2D::Init(const Options& o)
         ensureContext();
         // an empty map is built on the host and uploaded, a map that exists is updated on the device (dm_builder.hpp)
         bool host_built = false; uint32_t processed = 0; const char* what = "";
-        const int32_t rc = detail::add_obstacles_to_map(*eng_, ctx_, cells_xy.data(), cells_xy.size() / 2, distance_map->resolution, distance_map->patch_length,
-                                                        distance_map->maxSqDist(), host_built, processed, what);
-        if (rc) fail(rc, what);
+        const int32_t rc = detail::add_obstacles_to_map(*dev_.engine(), dev_.get(), cells_xy.data(), cells_xy.size() / 2, distance_map->resolution,
+                                                        distance_map->patch_length, distance_map->maxSqDist(), host_built, processed, what);
+        dev_.check(rc, what);
         if (host_built) host_built_ = true;
         return processed;
     };
     w.download = [this](sdm::HostMap& m) -> bool {
-        if (!ctx_) return false;
-        uint32_t n = 0, got = 0;
-        if (eng_->pf_map_patches(ctx_, 0, 0 /* distance map */, &n) != 0) return false;
         m.kind = sdm::kDistanceMap; m.max_sqdist = distance_map->maxSqDist();
-        m.ids.assign(n, 0); m.cells.assign((size_t)n * 10 * 1024, 0); m.masks.assign((size_t)n * 16, 0);
-        return eng_->pf_download_map(ctx_, 0, 0, n, m.ids.data(), m.cells.data(), m.masks.data(), &got) == 0 && got == n;
+        return dev_.download(0, LAMA_HIP_MAP_DISTANCE, m.ids, m.cells, m.masks);         // false while there is no context
     };
     w.upload = [this](const sdm::HostMap& m) {
         ensureContext();
-        const int32_t rc = eng_->pf_upload_map(ctx_, 0, 0 /* distance map */, (uint32_t)m.ids.size(), m.ids.data(), m.cells.data(), m.masks.data());
-        if (rc) fail(rc, "lama_hip_pf_upload_map");
+        dev_.check(dev_->pf_upload_map(dev_.get(), 0, LAMA_HIP_MAP_DISTANCE, (uint32_t)m.ids.size(), m.ids.data(), m.cells.data(), m.masks.data()),
+                   "lama_hip_pf_upload_map");
     };
     distance_map->bindWriter(std::move(w));
     rmse_ = 0.0;
@@ -78,25 +73,17 @@ void Loc2D::Init(const Options& o)
 
 Loc2D::~Loc2D()
 {
-    if (ctx_) eng_->ctx_destroy(ctx_);
     delete occupancy_map;
     delete distance_map;
 }
 
-void Loc2D::fail(int32_t rc, const char* what) const
-{
-    char msg[512];
-    std::snprintf(msg, sizeof(msg), "lama::Loc2D: %s failed (status %d): %s", what, rc, eng_->last_error(ctx_));
-    throw std::runtime_error(msg);
-}
-
 void Loc2D::ensureContext()
 {
-    if (ctx_) return;
+    if (dev_) return;
     if (!distance_map) throw std::runtime_error("lama::Loc2D: Init() must be called first");
-    eng_ = defaultEngine(distance_map->maxDistanceOption(), opt_.resolution);
+    std::shared_ptr<HipEngine> eng = defaultEngine(distance_map->maxDistanceOption(), opt_.resolution);
     lama_hip_cfg cfg;
-    eng_->default_cfg(&cfg);
+    eng->default_cfg(&cfg);
     cfg.particles = 1;
     cfg.resolution = opt_.resolution; cfg.patch_size = opt_.patch_size; cfg.l2_max = distance_map->maxDistanceOption(); cfg.max_iter = opt_.max_iter;
     cfg.device = opt_.gpu_device;
@@ -104,12 +91,7 @@ void Loc2D::ensureContext()
     cfg.dm_patch_capacity = 4096;            // a static building-scale map; occupancy is not kept on the device
     cfg.occ_patch_capacity = 8;
     cfg.queue_capacity = 1u << 20;
-    const int32_t rc = eng_->ctx_create(&cfg, &ctx_);
-    if (rc != 0 || !ctx_) {
-        char msg[200];
-        std::snprintf(msg, sizeof(msg), "lama::Loc2D: lama_hip_ctx_create failed (status %d): no usable MI355X / HIP device; there is no CPU fallback", rc);
-        throw std::runtime_error(msg);
-    }
+    dev_.create(std::move(eng), cfg);
 }
 
 bool Loc2D::enoughMotion(const Pose2D& odometry)               // src/loc2d.cpp:113-124
@@ -127,8 +109,7 @@ void Loc2D::solve(const PointCloudXYZ& s, bool do_solve)
     double p[4], out7[7];
     int32_t iters = 0;
     pose_.state.toArray(p);
-    const int32_t rc = eng_->match_solve(ctx_, 0, a.pts.data(), (uint32_t)s.points.size(), a.o, a.q, p, out7, &iters, do_solve ? 1 : 0);
-    if (rc) fail(rc, "lama_hip_match_solve");
+    dev_.check(dev_->match_solve(dev_.get(), 0, a.pts.data(), (uint32_t)s.points.size(), a.o, a.q, p, out7, &iters, do_solve ? 1 : 0), "lama_hip_match_solve");
     if (do_solve) {
         pose_.state = SE2d::fromArray(p);
         last_iterations_ = (uint32_t)iters;
@@ -184,7 +165,7 @@ bool Loc2D::relocalize(const PointCloudXYZ::Ptr& surface, const CorrelativeSearc
     Vector3d mn, mx;
     occupancy_map->bounds(mn, mx);
     detail::CorrelativeDevice dev;
-    dev.engine = eng_.get(); dev.ctx = ctx_; dev.particle = 0; dev.resolution = distance_map->resolution;
+    dev.engine = dev_.engine().get(); dev.ctx = dev_.get(); dev.particle = 0; dev.resolution = distance_map->resolution;
     const SimpleOccupancyMap* occ = occupancy_map;
     reloc_ = detail::correlative_search(CorrelativeSearch2D(options), dev, *surface, Vector2d(mn[0], mn[1]), Vector2d(mx[0], mx[1]),
                                         [occ](double x, double y) { return occ->isFree(Vector3d(x, y, 0.0)); });
@@ -221,8 +202,8 @@ void Loc2D::globalLocalization(const PointCloudXYZ& surface)
         Pose2D(x, y, a).state.toArray(&gloc_poses_[4 * i]);
     }
     const detail::ScanArrays a(surface);
-    const int32_t rc = eng_->eval_batch(ctx_, 0, a.pts.data(), (uint32_t)surface.points.size(), a.o, a.q, gloc_poses_.data(), B, gloc_errors_.data(), nullptr);
-    if (rc) fail(rc, "lama_hip_eval_batch");
+    dev_.check(dev_->eval_batch(dev_.get(), 0, a.pts.data(), (uint32_t)surface.points.size(), a.o, a.q, gloc_poses_.data(), B, gloc_errors_.data(), nullptr),
+               "lama_hip_eval_batch");
     double best_error = std::numeric_limits<double>::max();
     for (uint32_t i = 0; i < B; ++i)
         if (gloc_errors_[i] < best_error) { best_error = gloc_errors_[i]; pose_.state = SE2d::fromArray(&gloc_poses_[4 * i]); }
@@ -239,9 +220,8 @@ void Loc2D::addSamplingCovariance(const PointCloudXYZ& surface)
     for (size_t i = 0; i < K; ++i) { xy[2 * i] = pose_.x() + sampling_steps_[i].x(); xy[2 * i + 1] = pose_.y() + sampling_steps_[i].y(); }
     sampling_l_.assign(K, 0.0);
     const detail::ScanArrays a(surface);
-    const int32_t rc = eng_->map_sample_likelihood(ctx_, 0, a.pts.data(), (uint32_t)num_points, a.o, a.q, pose_.rotation(), xy.data(), (uint32_t)K,
-                                                   (uint32_t)step, sampling_l_.data());
-    if (rc) fail(rc, "lama_hip_map_sample_likelihood");
+    dev_.check(dev_->map_sample_likelihood(dev_.get(), 0, a.pts.data(), (uint32_t)num_points, a.o, a.q, pose_.rotation(), xy.data(), (uint32_t)K,
+                                           (uint32_t)step, sampling_l_.data()), "lama_hip_map_sample_likelihood");
     double Km[2][2] = {{0, 0}, {0, 0}}, u[2] = {0, 0}, s = 0;
     for (size_t i = 0; i < K; ++i) {
         const double x = xy[2 * i], y = xy[2 * i + 1], l = sampling_l_[i];

@@ -3,7 +3,6 @@
 #include "lama/map_builder_2d.h"
 
 #include <chrono>
-#include <cstdio>
 #include <stdexcept>
 
 #include "dm_builder.hpp"
@@ -23,32 +22,20 @@ uint32_t max_sqdist_of(double l2_max, double resolution)
 MapBuilder2D::MapBuilder2D(const Options& o) : opt_(o)
 {
     const double reach = o.l2_max > 0.0 ? o.l2_max : 0.5;           // (a context always has a distance map; with l2_max == 0 it stays empty)
-    eng_ = defaultEngine(reach, o.resolution);
-    if (!eng_->map_integrate_scans || !eng_->map_occupied_cells)
-        throw std::runtime_error("lama::MapBuilder2D: the device library " + eng_->origin + " has no lama_hip_map_integrate_scans");
+    std::shared_ptr<HipEngine> eng = defaultEngine(reach, o.resolution);
+    if (!eng->map_integrate_scans || !eng->map_occupied_cells)
+        throw std::runtime_error("lama::MapBuilder2D: the device library " + eng->origin + " has no lama_hip_map_integrate_scans");
     lama_hip_cfg cfg;
-    eng_->default_cfg(&cfg);
+    eng->default_cfg(&cfg);
     cfg.particles = 1;
     cfg.resolution = o.resolution; cfg.patch_size = o.patch_size; cfg.l2_max = reach; cfg.device = o.gpu_device;
     if (o.window_patches) cfg.window_patches = o.window_patches;
     if (o.dm_patch_capacity) cfg.dm_patch_capacity = o.dm_patch_capacity;
     if (o.occ_patch_capacity) cfg.occ_patch_capacity = o.occ_patch_capacity;
-    const int32_t rc = eng_->ctx_create(&cfg, &ctx_);
-    if (rc != 0 || !ctx_) {
-        char msg[200];
-        std::snprintf(msg, sizeof(msg), "lama::MapBuilder2D: lama_hip_ctx_create failed (status %d): no usable MI355X / HIP device; there is no CPU fallback", rc);
-        throw std::runtime_error(msg);
-    }
+    dev_.create(std::move(eng), cfg);
 }
 
-MapBuilder2D::~MapBuilder2D() { if (ctx_) eng_->ctx_destroy(ctx_); }
-
-void MapBuilder2D::fail(int32_t rc, const char* what) const
-{
-    char msg[512];
-    std::snprintf(msg, sizeof(msg), "lama::MapBuilder2D: %s failed (status %d): %s", what, rc, eng_->last_error(ctx_));
-    throw std::runtime_error(msg);
-}
+MapBuilder2D::~MapBuilder2D() = default;
 
 size_t MapBuilder2D::add(const PointCloudXYZ::Ptr& cloud, const Pose2D& pose)
 {
@@ -81,10 +68,8 @@ void MapBuilder2D::reset()
     poses_.clear(); pts_.clear(); origins_.clear(); quats_.clear(); offsets_.assign(1, 0u); occupied_.clear();
     occ_view_.reset(); dm_view_.reset();
     if (has_map_) {                                               // an upload of no patches empties the map (Map::read of an empty file)
-        int32_t rc = eng_->pf_upload_map(ctx_, 0, LAMA_HIP_MAP_OCCUPANCY, 0, nullptr, nullptr, nullptr);
-        if (rc) fail(rc, "lama_hip_pf_upload_map (reset)");
-        rc = eng_->pf_upload_map(ctx_, 0, LAMA_HIP_MAP_DISTANCE, 0, nullptr, nullptr, nullptr);
-        if (rc) fail(rc, "lama_hip_pf_upload_map (reset)");
+        dev_.check(dev_->pf_upload_map(dev_.get(), 0, LAMA_HIP_MAP_OCCUPANCY, 0, nullptr, nullptr, nullptr), "lama_hip_pf_upload_map (reset)");
+        dev_.check(dev_->pf_upload_map(dev_.get(), 0, LAMA_HIP_MAP_DISTANCE, 0, nullptr, nullptr, nullptr), "lama_hip_pf_upload_map (reset)");
     }
     built_ = 0; stale_ = false; has_map_ = false;
 }
@@ -95,8 +80,7 @@ void MapBuilder2D::build()
     timing_ = Timing();
     double t0 = now_ms();
     if (stale_) {                                                 // poses of integrated keys changed: start from an empty occupancy map
-        const int32_t rc = eng_->pf_upload_map(ctx_, 0, LAMA_HIP_MAP_OCCUPANCY, 0, nullptr, nullptr, nullptr);
-        if (rc) fail(rc, "lama_hip_pf_upload_map (rebuild)");
+        dev_.check(dev_->pf_upload_map(dev_.get(), 0, LAMA_HIP_MAP_OCCUPANCY, 0, nullptr, nullptr, nullptr), "lama_hip_pf_upload_map (rebuild)");
         built_ = 0; stale_ = false;
     }
     const size_t K = poses_.size() - built_;
@@ -104,9 +88,8 @@ void MapBuilder2D::build()
         std::vector<double> p4(4 * K);
         for (size_t k = 0; k < K; ++k) poses_[built_ + k].state.toArray(&p4[4 * k]);
         const uint32_t flags = (opt_.full ? LAMA_HIP_MAP_BUILD_FULL : 0u) | (opt_.prune ? LAMA_HIP_MAP_BUILD_PRUNE : 0u);
-        const int32_t rc = eng_->map_integrate_scans(ctx_, 0, (uint32_t)K, p4.data(), pts_.data(), offsets_.data() + built_, origins_.data() + 3 * built_,
-                                                     quats_.data() + 4 * built_, flags);
-        if (rc) fail(rc, "lama_hip_map_integrate_scans");
+        dev_.check(dev_->map_integrate_scans(dev_.get(), 0, (uint32_t)K, p4.data(), pts_.data(), offsets_.data() + built_, origins_.data() + 3 * built_,
+                                             quats_.data() + 4 * built_, flags), "lama_hip_map_integrate_scans");
         built_ = poses_.size();
         has_map_ = true;
     }
@@ -115,41 +98,32 @@ void MapBuilder2D::build()
     if (!(opt_.l2_max > 0.0) || !has_map_) return;
     // the distance map of the occupied cells: addObstacle for each + update() on an empty map
     uint32_t n = 0;
-    int32_t rc = eng_->map_occupied_cells(ctx_, 0, 0, nullptr, &n);
-    if (rc) fail(rc, "lama_hip_map_occupied_cells");
+    dev_.check(dev_->map_occupied_cells(dev_.get(), 0, 0, nullptr, &n), "lama_hip_map_occupied_cells");
     occupied_.assign(2 * (size_t)n, 0u);
-    if (n) { rc = eng_->map_occupied_cells(ctx_, 0, n, occupied_.data(), &n); if (rc) fail(rc, "lama_hip_map_occupied_cells"); }
+    if (n) dev_.check(dev_->map_occupied_cells(dev_.get(), 0, n, occupied_.data(), &n), "lama_hip_map_occupied_cells");
     double t2 = now_ms();
     timing_.occupied_ms = t2 - t1;
-    rc = eng_->pf_upload_map(ctx_, 0, LAMA_HIP_MAP_DISTANCE, 0, nullptr, nullptr, nullptr);
-    if (rc) fail(rc, "lama_hip_pf_upload_map (distance map)");
+    dev_.check(dev_->pf_upload_map(dev_.get(), 0, LAMA_HIP_MAP_DISTANCE, 0, nullptr, nullptr, nullptr), "lama_hip_pf_upload_map (distance map)");
     if (n) {
         bool host_built = false; uint32_t processed = 0; const char* what = "";
-        rc = detail::add_obstacles_to_map(*eng_, ctx_, occupied_.data(), n, opt_.resolution, opt_.patch_size, max_sqdist_of(opt_.l2_max, opt_.resolution), host_built, processed, what);
-        if (rc) fail(rc, what);
+        const int32_t rc = detail::add_obstacles_to_map(*dev_.engine(), dev_.get(), occupied_.data(), n, opt_.resolution, opt_.patch_size,
+                                                        max_sqdist_of(opt_.l2_max, opt_.resolution), host_built, processed, what);
+        dev_.check(rc, what);
     }
     timing_.distance_ms = now_ms() - t2;
-}
-
-static bool dl(const HipEngine* e, lama_hip_ctx* ctx, int kind, size_t cell_bytes, sdm::HostMap& m)
-{
-    uint32_t n = 0, got = 0;
-    if (e->pf_map_patches(ctx, 0, kind, &n) != 0) return false;
-    m.ids.assign(n, 0); m.cells.assign((size_t)n * cell_bytes * 1024, 0); m.masks.assign((size_t)n * 16, 0);
-    return e->pf_download_map(ctx, 0, kind, n, m.ids.data(), m.cells.data(), m.masks.data(), &got) == 0 && got == n;
 }
 
 bool MapBuilder2D::downloadOccupancyMap(sdm::HostMap& m) const
 {
     m.kind = sdm::kFrequencyOccupancyMap; m.resolution = opt_.resolution;
-    return has_map_ && dl(eng_.get(), ctx_, LAMA_HIP_MAP_OCCUPANCY, 4, m);
+    return has_map_ && dev_.download(0, LAMA_HIP_MAP_OCCUPANCY, m.ids, m.cells, m.masks);
 }
 
 bool MapBuilder2D::downloadDistanceMap(sdm::HostMap& m) const
 {
     if (!(opt_.l2_max > 0.0)) return false;
     m.kind = sdm::kDistanceMap; m.resolution = opt_.resolution; m.max_sqdist = max_sqdist_of(opt_.l2_max, opt_.resolution);
-    return has_map_ && dl(eng_.get(), ctx_, LAMA_HIP_MAP_DISTANCE, 10, m);
+    return has_map_ && dev_.download(0, LAMA_HIP_MAP_DISTANCE, m.ids, m.cells, m.masks);
 }
 
 const FrequencyOccupancyMap* MapBuilder2D::getOccupancyMap() const
@@ -168,7 +142,7 @@ const DynamicDistanceMap* MapBuilder2D::getDistanceMap() const
         sdm::HostMap m;
         if (!downloadDistanceMap(m)) return nullptr;
         dm_view_.reset(new DynamicDistanceMap(std::move(m)));
-        dm_view_->bindDevice(eng_, ctx_, 0u);
+        dm_view_->bindDevice(dev_.engine(), dev_.get(), 0u);
     }
     return dm_view_.get();
 }

@@ -171,8 +171,7 @@ const DynamicDistanceMap::DeviceBinding& device_of(const MatchSurface2D& m)
 
 [[noreturn]] void device_fail(const DynamicDistanceMap::DeviceBinding& d, int32_t rc, const char* what)
 {
-    const char* msg = d.engine->last_error ? d.engine->last_error(d.ctx) : "";
-    throw std::runtime_error(std::string("lama::MatchSurface2D: ") + what + " failed (status " + std::to_string(rc) + "): " + (msg ? msg : ""));
+    throw std::runtime_error(deviceFailure(*d.engine, d.ctx, "lama::MatchSurface2D", what, rc));
 }
 
 } // namespace
@@ -409,10 +408,7 @@ void SolveBatch(const Solver::Options& options, const std::vector<MatchSurface2D
     std::vector<uint32_t> status(B, 0u);
     const int32_t rc = dev->engine->match_solve_batch(dev->ctx, (uint32_t)B, particles.data(), pts.data(), offs.data(), origins.data(), quats.data(),
                                                       poses.data(), max_iterations.data(), strategy, kind, param, out8.data(), iters.data(), status.data());
-    if (rc == LAMA_HIP_E_INVALID) {
-        const char* msg = dev->engine->last_error ? dev->engine->last_error(dev->ctx) : "";
-        throw std::invalid_argument(std::string("lama::SolveBatch: ") + (msg ? msg : ""));
-    }
+    if (rc == LAMA_HIP_E_INVALID) throw std::invalid_argument(std::string("lama::SolveBatch: ") + lastDeviceError(*dev->engine, dev->ctx));
     if (rc && rc != LAMA_HIP_E_NUMERIC) device_fail(*dev, rc, "lama_hip_match_solve_batch");
     for (size_t b = 0; b < B; ++b) {
         problems[b]->state_ = SE2d::fromArray(&poses[4 * b]);

@@ -83,12 +83,11 @@ struct PFSlam2D::Group {
     void reserve_stage(uint32_t r, uint64_t bytes)
     {
         if (bytes <= stage_cap[r]) return;
-        PFSlam2D& s = *shards[r];
-        if (stage[r]) (void)s.eng_->blob_free(s.ctx_, stage[r]);
+        const DeviceContext& d = shards[r]->dev_;
+        if (stage[r]) (void)d->blob_free(d.get(), stage[r]);
         stage[r] = nullptr; stage_cap[r] = 0;
         const uint64_t want = bytes + bytes / 2;
-        const int32_t rc = s.eng_->blob_alloc(s.ctx_, want, &stage[r]);
-        if (rc) s.fail(rc, "lama_hip_blob_alloc");
+        d.check(d->blob_alloc(d.get(), want, &stage[r]), "lama_hip_blob_alloc");
         stage_cap[r] = want;
     }
     ~Group()
@@ -100,7 +99,7 @@ struct PFSlam2D::Group {
         cv_go.notify_all();
         for (auto& t : threads) t.join();
         for (size_t r = 0; r < shards.size(); ++r)
-            if (stage[r]) (void)shards[r]->eng_->blob_free(shards[r]->ctx_, stage[r]);
+            if (stage[r]) (void)shards[r]->dev_->blob_free(shards[r]->dev_.get(), stage[r]);
     }
 };
 
@@ -116,9 +115,8 @@ PFSlam2D::PFSlam2D(const Options& options) : options_(options)
         if ((uint32_t)options_.gpus > options_.particles) throw std::runtime_error("lama::PFSlam2D: more GPUs than particles");
         // all shards replay the same host random stream: settle the seed first (0 = random_device, src/pf_slam2d.cpp:131-134)
         if (options_.seed == 0) options_.seed = std::random_device()() | 1u;
-        eng_ = defaultEngine(options_.l2_max, options_.resolution);
         int32_t ndev = 0;
-        if (eng_->device_count(&ndev) != 0 || ndev <= 0)
+        if (defaultEngine(options_.l2_max, options_.resolution)->device_count(&ndev) != 0 || ndev <= 0)
             throw std::runtime_error("lama::PFSlam2D: no usable MI355X / HIP device; there is no CPU fallback");
         group_.reset(new Group());
         for (int32_t r = 0; r < options_.gpus; ++r) {
@@ -140,9 +138,9 @@ PFSlam2D::PFSlam2D(const Options& options) : options_(options)
     hi_ = (uint32_t)(((r + 1) * P + G - 1) / G);
     if (hi_ <= lo_) throw std::runtime_error("lama::PFSlam2D: more shards than particles");
 
-    eng_ = defaultEngine(options_.l2_max, options_.resolution);
+    std::shared_ptr<HipEngine> eng = defaultEngine(options_.l2_max, options_.resolution);
     lama_hip_cfg cfg;
-    eng_->default_cfg(&cfg);
+    eng->default_cfg(&cfg);
     cfg.particles = hi_ - lo_;
     cfg.resolution = options_.resolution;
     cfg.patch_size = options_.patch_size;
@@ -158,13 +156,7 @@ PFSlam2D::PFSlam2D(const Options& options) : options_(options)
     if (options_.dm_patch_capacity) cfg.dm_patch_capacity = options_.dm_patch_capacity;
     if (options_.occ_patch_capacity) cfg.occ_patch_capacity = options_.occ_patch_capacity;
     if (options_.queue_capacity) cfg.queue_capacity = options_.queue_capacity;
-    const int32_t rc = eng_->ctx_create(&cfg, &ctx_);
-    if (rc != 0 || !ctx_) {
-        char msg[256];
-        std::snprintf(msg, sizeof(msg), "lama::PFSlam2D: lama_hip_ctx_create failed (status %d): no usable MI355X / HIP device "
-                                        "or unsupported options; there is no CPU fallback", rc);
-        throw std::runtime_error(msg);
-    }
+    dev_.create(std::move(eng), cfg);
     particles_.assign(options_.particles, Particle());
     local_loglik_.assign(hi_ - lo_, 0.0);
 
@@ -181,12 +173,11 @@ PFSlam2D::PFSlam2D(const Options& options) : options_(options)
 PFSlam2D::~PFSlam2D()
 {
     group_.reset();                         // joins the shard threads, destroys the shard objects (and their contexts)
-    if (ctx_) eng_->ctx_destroy(ctx_);
     delete summary;
 }
 
-lama_hip_ctx* PFSlam2D::deviceContext() const { return group_ ? group_->shards[0]->ctx_ : ctx_; }
-const HipEngine* PFSlam2D::engine() const { return eng_.get(); }
+lama_hip_ctx* PFSlam2D::deviceContext() const { return (group_ ? group_->shards[0]->dev_ : dev_).get(); }
+const HipEngine* PFSlam2D::engine() const { return (group_ ? group_->shards[0]->dev_ : dev_).engine().get(); }
 size_t PFSlam2D::numShards() const { return group_ ? group_->shards.size() : 0; }
 const PFSlam2D* PFSlam2D::shard(size_t r) const { return group_ && r < group_->shards.size() ? group_->shards[r].get() : nullptr; }
 const PFSlam2D* PFSlam2D::ownerOf(uint32_t i) const
@@ -197,8 +188,7 @@ const PFSlam2D* PFSlam2D::ownerOf(uint32_t i) const
 }
 void PFSlam2D::syncDevice()
 {
-    const int32_t rs = eng_->sync(ctx_);
-    if (rs) fail(rs, "lama_hip_sync");
+    dev_.check(dev_->sync(dev_.get()), "lama_hip_sync");
 }
 
 // Host mirror of a multi-GPU object: weights are replicated on every shard (shard 0's are taken), a particle's pose is its owner's.
@@ -290,8 +280,7 @@ bool PFSlam2D::updateGroup(const PointCloudXYZ::Ptr& surface, const Pose2D& odom
             std::vector<uint64_t> out_bytes(G, 0), in_bytes(G, 0);
             for (auto& x : xf) {
                 const PFSlam2D& sh = *g.shards[x.src_shard];
-                const int32_t rc = sh.eng_->pf_export_particle(sh.ctx_, x.particle - sh.lo_, nullptr, 0, &x.bytes);
-                if (rc) sh.fail(rc, "lama_hip_pf_export_particle (size)");
+                sh.dev_.check(sh.dev_->pf_export_particle(sh.dev_.get(), x.particle - sh.lo_, nullptr, 0, &x.bytes), "lama_hip_pf_export_particle (size)");
                 x.src_off = out_bytes[x.src_shard]; out_bytes[x.src_shard] += (x.bytes + 255) & ~255ull;
             }
             for (auto& x : xf) { x.dst_off = out_bytes[x.dst_shard] + in_bytes[x.dst_shard]; in_bytes[x.dst_shard] += (x.bytes + 255) & ~255ull; }
@@ -304,22 +293,20 @@ bool PFSlam2D::updateGroup(const PointCloudXYZ::Ptr& surface, const Pose2D& odom
                 for (auto& x : xf)
                     if (x.src_shard == r) { parts.push_back(x.particle - sh.lo_); bufs.push_back((uint8_t*)g.stage[r] + x.src_off); caps.push_back(x.bytes); }
                 if (parts.empty()) return;
-                const int32_t rc = sh.eng_->pf_export_particles(sh.ctx_, (uint32_t)parts.size(), parts.data(), bufs.data(), caps.data(), nullptr);
-                if (rc) sh.fail(rc, "lama_hip_pf_export_particles");
+                sh.dev_.check(sh.dev_->pf_export_particles(sh.dev_.get(), (uint32_t)parts.size(), parts.data(), bufs.data(), caps.data(), nullptr),
+                              "lama_hip_pf_export_particles");
             });
             // ... and every destination shard pulls each source's run of blobs with ONE GPU-to-GPU copy (hipMemcpyPeerAsync over
             // xGMI between different devices)
             g.run([&](uint32_t r) {
-                PFSlam2D& dsh = *g.shards[r];
+                const DeviceContext& dst = g.shards[r]->dev_;
                 for (size_t a = 0; a < xf.size();) {
                     if (xf[a].dst_shard != r) { ++a; continue; }
                     size_t b = a;
                     uint64_t run = 0;
                     while (b < xf.size() && xf[b].dst_shard == r && xf[b].src_shard == xf[a].src_shard) { run += (xf[b].bytes + 255) & ~255ull; ++b; }
-                    PFSlam2D& ssh = *g.shards[xf[a].src_shard];
-                    const int32_t rc = dsh.eng_->blob_copy(dsh.ctx_, (uint8_t*)g.stage[r] + xf[a].dst_off, ssh.ctx_,
-                                                           (const uint8_t*)g.stage[xf[a].src_shard] + xf[a].src_off, run);
-                    if (rc) dsh.fail(rc, "lama_hip_blob_copy");
+                    dst.check(dst->blob_copy(dst.get(), (uint8_t*)g.stage[r] + xf[a].dst_off, g.shards[xf[a].src_shard]->dev_.get(),
+                                             (const uint8_t*)g.stage[xf[a].src_shard] + xf[a].src_off, run), "lama_hip_blob_copy");
                     a = b;
                 }
             });
@@ -343,14 +330,12 @@ bool PFSlam2D::updateGroup(const PointCloudXYZ::Ptr& surface, const Pose2D& odom
                     if (x.dst_shard == r && x.particle == sp) { slots.push_back(i - sh.lo_); bufs.push_back((const uint8_t*)g.stage[r] + x.dst_off); nbytes.push_back(x.bytes); break; }
             }
             const bool any = !slots.empty();
-            if (any) {
-                const int32_t rc = sh.eng_->pf_import_particles(sh.ctx_, (uint32_t)slots.size(), slots.data(), bufs.data(), nbytes.data());
-                if (rc) sh.fail(rc, "lama_hip_pf_import_particles");
-            }
+            if (any)
+                sh.dev_.check(sh.dev_->pf_import_particles(sh.dev_.get(), (uint32_t)slots.size(), slots.data(), bufs.data(), nbytes.data()),
+                              "lama_hip_pf_import_particles");
             if (any) {                                           // the pose travels inside the blob: refresh the host mirror
                 std::vector<double> poses((size_t)(sh.hi_ - sh.lo_) * 4);
-                const int32_t rc = sh.eng_->pf_get_poses(sh.ctx_, poses.data());
-                if (rc) sh.fail(rc, "lama_hip_pf_get_poses");
+                sh.dev_.check(sh.dev_->pf_get_poses(sh.dev_.get(), poses.data()), "lama_hip_pf_get_poses");
                 for (uint32_t i = sh.lo_; i < sh.hi_; ++i)
                     if (owner((uint32_t)idx[i]) != r) sh.particles_[i].pose.state = SE2d::fromArray(&poses[4 * (size_t)(i - sh.lo_)]);
             }
@@ -374,13 +359,6 @@ bool PFSlam2D::updateGroup(const PointCloudXYZ::Ptr& surface, const Pose2D& odom
         summary->memory.push_back((double)getMemoryUsage());
     }
     return true;
-}
-
-void PFSlam2D::fail(int32_t rc, const char* what) const
-{
-    char msg[512];
-    std::snprintf(msg, sizeof(msg), "lama::PFSlam2D: %s failed (status %d): %s", what, rc, eng_->last_error(ctx_));
-    throw std::runtime_error(msg);
 }
 
 double PFSlam2D::normal(double stddev)      // src/random.cpp:69-73: a fresh distribution per call
@@ -462,8 +440,7 @@ void PFSlam2D::uploadLocalPoses()
 {
     std::vector<double> buf((size_t)(hi_ - lo_) * 4);
     for (uint32_t i = lo_; i < hi_; ++i) particles_[i].pose.state.toArray(&buf[4 * (size_t)(i - lo_)]);
-    const int32_t rc = eng_->pf_set_poses(ctx_, buf.data());
-    if (rc) fail(rc, "lama_hip_pf_set_poses");
+    dev_.check(dev_->pf_set_poses(dev_.get(), buf.data()), "lama_hip_pf_set_poses");
 }
 
 PFSlam2D::Phase PFSlam2D::updateBegin(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, double timestamp)
@@ -490,8 +467,7 @@ PFSlam2D::Phase PFSlam2D::updateBegin(const PointCloudXYZ::Ptr& surface, const P
         }
         double p0[4];
         pose_.state.toArray(p0);
-        const int32_t rc = eng_->pf_init(ctx_, pts_.data(), n, origin_, quat_, p0);
-        if (rc) fail(rc, "lama_hip_pf_init");
+        dev_.check(dev_->pf_init(dev_.get(), pts_.data(), n, origin_, quat_, p0), "lama_hip_pf_init");
         has_first_scan = true;
         if (summary) {
             const double el = now_s() - t_begin_;
@@ -518,8 +494,7 @@ PFSlam2D::Phase PFSlam2D::updateBegin(const PointCloudXYZ::Ptr& surface, const P
     const double t0 = now_s();
     uploadLocalPoses();
     std::vector<double> poses((size_t)(hi_ - lo_) * 4);
-    const int32_t rc = eng_->pf_scan_match(ctx_, pts_.data(), n, origin_, quat_, poses.data(), local_loglik_.data(), nullptr);
-    if (rc) fail(rc, "lama_hip_pf_scan_match");
+    dev_.check(dev_->pf_scan_match(dev_.get(), pts_.data(), n, origin_, quat_, poses.data(), local_loglik_.data(), nullptr), "lama_hip_pf_scan_match");
     scan_resident_ = true;
     for (uint32_t i = lo_; i < hi_; ++i) {
         particles_[i].pose.state = SE2d::fromArray(&poses[4 * (size_t)(i - lo_)]);
@@ -565,8 +540,7 @@ void PFSlam2D::applyResample(const std::vector<int32_t>& sample_idx)
         const uint32_t src = (uint32_t)sample_idx[i];
         local[i - lo_] = ownsParticle(src) ? (int32_t)(src - lo_) : (int32_t)(i - lo_);
     }
-    const int32_t rc = eng_->pf_resample(ctx_, local.data());
-    if (rc) fail(rc, "lama_hip_pf_resample");
+    dev_.check(dev_->pf_resample(dev_.get(), local.data()), "lama_hip_pf_resample");
     particles_.swap(next);
     ++num_resamples_;
     if (summary) summary->time_resampling.push_back(now_s() - t0);
@@ -581,12 +555,10 @@ void PFSlam2D::updateMaps()
     // the scan is already resident on the device (uploaded by scan_match of this update)
     // queued, not awaited: the host part of the next scan overlaps with the kernels; the status is collected by the next call
     // on the context (a deferred device error makes THAT call fail)
-    const int32_t rc = eng_->pf_update_maps_begin(ctx_, scan_resident_ ? nullptr : pts_.data(), n, origin_, quat_);      // :289-302
-    if (rc) fail(rc, "lama_hip_pf_update_maps");
+    dev_.check(dev_->pf_update_maps_begin(dev_.get(), scan_resident_ ? nullptr : pts_.data(), n, origin_, quat_), "lama_hip_pf_update_maps");      // :289-302
     if (summary) {
         // the Summary's per-update buckets need the real duration: wait for the kernels here
-        const int32_t rs = eng_->sync(ctx_);
-        if (rs) fail(rs, "lama_hip_sync");
+        syncDevice();
         summary->time_mapping.push_back(now_s() - t0);
         summary->time.push_back(now_s() - t_begin_);
         summary->timestamp.push_back(last_timestamp_);              // probeStamp(timestamp), src/pf_slam2d.cpp:306
@@ -623,7 +595,7 @@ uint64_t PFSlam2D::getMemoryUsage() const
 {
     if (group_) { uint64_t t = 0; for (auto& sh : group_->shards) t += sh->getMemoryUsage(); return t; }
     lama_hip_counters c;
-    if (eng_->get_counters(ctx_, &c) != 0) return 0;
+    if (dev_->get_counters(dev_.get(), &c) != 0) return 0;
     // patch payloads in the reference's record sizes (Container::memory, src/sdm/container.cpp:92-95)
     return c.dm_patches * 10240ull + c.occ_patches * 4096ull;
 }
@@ -634,22 +606,10 @@ uint64_t PFSlam2D::getMemoryUsage(uint64_t& occmem, uint64_t& dmmem) const
     if (!has_first_scan) return 0;
     if (group_) return group_->shards[0]->getMemoryUsage(occmem, dmmem);
     uint32_t nd = 0, no = 0;
-    if (eng_->pf_map_patches(ctx_, 0, LAMA_HIP_MAP_DISTANCE, &nd) != 0 || eng_->pf_map_patches(ctx_, 0, LAMA_HIP_MAP_OCCUPANCY, &no) != 0) return 0;
+    if (dev_->pf_map_patches(dev_.get(), 0, LAMA_HIP_MAP_DISTANCE, &nd) != 0 || dev_->pf_map_patches(dev_.get(), 0, LAMA_HIP_MAP_OCCUPANCY, &no) != 0) return 0;
     occmem = (uint64_t)options_.particles * no * 4096ull;
     dmmem = (uint64_t)options_.particles * nd * 10240ull;
     return occmem + dmmem;
-}
-
-static bool download(const HipEngine* e, lama_hip_ctx* ctx, uint32_t particle, int kind, size_t cell_bytes,
-                     std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks)
-{
-    uint32_t n = 0;
-    if (e->pf_map_patches(ctx, particle, kind, &n) != 0) return false;
-    ids.assign(n, 0);
-    cells.assign((size_t)n * cell_bytes * 1024, 0);
-    masks.assign((size_t)n * 16, 0);
-    uint32_t got = 0;
-    return e->pf_download_map(ctx, particle, kind, n, ids.data(), cells.data(), masks.data(), &got) == 0 && got == n;
 }
 
 // Any particle's maps (the reference's public Particle::dm / Particle::occ, include/lama/pf_slam2d.h:83-84) in the reference's
@@ -659,7 +619,7 @@ bool PFSlam2D::downloadParticleDistanceMap(size_t i, std::vector<uint64_t>& ids,
     if (!has_first_scan || i >= particles_.size()) return false;
     if (group_) return ownerOf((uint32_t)i)->downloadParticleDistanceMap(i, ids, cells, masks);
     if (!ownsParticle((uint32_t)i)) return false;
-    return download(eng_.get(), ctx_, (uint32_t)i - lo_, LAMA_HIP_MAP_DISTANCE, 10, ids, cells, masks);
+    return dev_.download((uint32_t)i - lo_, LAMA_HIP_MAP_DISTANCE, ids, cells, masks);
 }
 
 bool PFSlam2D::downloadParticleOccupancyMap(size_t i, std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks) const
@@ -667,7 +627,7 @@ bool PFSlam2D::downloadParticleOccupancyMap(size_t i, std::vector<uint64_t>& ids
     if (!has_first_scan || i >= particles_.size()) return false;
     if (group_) return ownerOf((uint32_t)i)->downloadParticleOccupancyMap(i, ids, cells, masks);
     if (!ownsParticle((uint32_t)i)) return false;
-    return download(eng_.get(), ctx_, (uint32_t)i - lo_, LAMA_HIP_MAP_OCCUPANCY, 4, ids, cells, masks);
+    return dev_.download((uint32_t)i - lo_, LAMA_HIP_MAP_OCCUPANCY, ids, cells, masks);
 }
 
 // the best particle's (its replicated weights name the same best particle on every shard)

@@ -18,9 +18,9 @@ Slam2D::Slam2D(const Options& o) : trans_thresh_(o.trans_thresh), rot_thresh_(o.
     if (o.use_compression) throw std::runtime_error("lama::Slam2D: use_compression is not supported on the device path");
     transient_map_ = o.transient_map; truncated_range_ = o.truncated_range;
     if (o.create_summary) summary = new Summary;                 // src/slam2d.cpp:117-118
-    eng_ = defaultEngine(o.l2_max, o.resolution);
+    std::shared_ptr<HipEngine> eng = defaultEngine(o.l2_max, o.resolution);
     lama_hip_cfg cfg;
-    eng_->default_cfg(&cfg);
+    eng->default_cfg(&cfg);
     cfg.particles = 1;
     cfg.resolution = o.resolution; cfg.patch_size = o.patch_size; cfg.l2_max = o.l2_max; cfg.max_iter = o.max_iter;
     cfg.truncated_ray = o.truncated_ray; cfg.truncated_range = o.truncated_range; cfg.device = o.gpu_device;
@@ -30,15 +30,10 @@ Slam2D::Slam2D(const Options& o) : trans_thresh_(o.trans_thresh), rot_thresh_(o.
     if (o.dm_patch_capacity) cfg.dm_patch_capacity = o.dm_patch_capacity;
     if (o.occ_patch_capacity) cfg.occ_patch_capacity = o.occ_patch_capacity;
     if (o.queue_capacity) cfg.queue_capacity = o.queue_capacity;
-    const int32_t rc = eng_->ctx_create(&cfg, &ctx_);
-    if (rc != 0 || !ctx_) {
-        char msg[200];
-        std::snprintf(msg, sizeof(msg), "lama::Slam2D: lama_hip_ctx_create failed (status %d): no usable MI355X / HIP device; there is no CPU fallback", rc);
-        throw std::runtime_error(msg);
-    }
+    dev_.create(std::move(eng), cfg);
 }
 
-Slam2D::~Slam2D() { if (ctx_) eng_->ctx_destroy(ctx_); delete summary; }
+Slam2D::~Slam2D() { delete summary; }
 
 static double now_s()
 {
@@ -79,13 +74,6 @@ std::string Slam2D::Summary::report() const
     return std::string(buf);
 }
 
-void Slam2D::fail(int32_t rc, const char* what) const
-{
-    char msg[512];
-    std::snprintf(msg, sizeof(msg), "lama::Slam2D: %s failed (status %d): %s", what, rc, eng_->last_error(ctx_));
-    throw std::runtime_error(msg);
-}
-
 bool Slam2D::enoughMotion(const Pose2D& odometry)                 // src/slam2d.cpp:129-141
 {
     if (!has_first_scan) return true;
@@ -107,13 +95,10 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
     if (!has_first_scan) {                                        // :147-160
         odom_ = odometry;
         pose_.state.toArray(p);
-        int32_t rc = eng_->pf_init(ctx_, s.pts.data(), n, s.o, s.q, p); // updateMaps(surface) at pose_
-        if (rc) fail(rc, "lama_hip_pf_init");
-        if (eng_->get_counters(ctx_, &c1) == 0) number_of_proccessed_cells_ = (uint32_t)c1.bf_cells;
-        if (transient_map_) {                                      // :322-379
-            rc = transient::prune(eng_.get(), ctx_, *surface, pose_, resolution_, l2_max_, truncated_range_, 2.0, &last_deleted_);
-            if (rc) fail(rc, "transient map");
-        }
+        dev_.check(dev_->pf_init(dev_.get(), s.pts.data(), n, s.o, s.q, p), "lama_hip_pf_init");   // updateMaps(surface) at pose_
+        if (dev_->get_counters(dev_.get(), &c1) == 0) number_of_proccessed_cells_ = (uint32_t)c1.bf_cells;
+        if (transient_map_)                                        // :322-379
+            dev_.check(transient::prune(dev_.engine().get(), dev_.get(), *surface, pose_, resolution_, l2_max_, truncated_range_, 2.0, &last_deleted_), "transient map");
         if (summary) {                                             // :151-157
             const double el = now_s() - t_begin;
             summary->timestamp.push_back(timestamp); summary->time.push_back(el); summary->time_mapping.push_back(el);
@@ -131,24 +116,19 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
     // 2. optimise                                                 :175-181
     const double t_solve = now_s();
     pose_.state.toArray(p);
-    int32_t rc = eng_->pf_set_poses(ctx_, p);
-    if (rc) fail(rc, "lama_hip_pf_set_poses");
+    dev_.check(dev_->pf_set_poses(dev_.get(), p), "lama_hip_pf_set_poses");
     int32_t iters = 0;
-    rc = eng_->pf_scan_match(ctx_, s.pts.data(), n, s.o, s.q, p, nullptr, &iters);
-    if (rc) fail(rc, "lama_hip_pf_scan_match");
+    dev_.check(dev_->pf_scan_match(dev_.get(), s.pts.data(), n, s.o, s.q, p, nullptr, &iters), "lama_hip_pf_scan_match");
     pose_.state = SE2d::fromArray(p);
     last_iterations_ = (uint32_t)iters;
     if (summary) summary->time_solving.push_back(now_s() - t_solve);
     // 3. update maps                                              :184-186
     const double t_map = now_s();
-    (void)eng_->get_counters(ctx_, &c0);
-    rc = eng_->pf_update_maps(ctx_, s.pts.data(), n, s.o, s.q);
-    if (rc) fail(rc, "lama_hip_pf_update_maps");
-    if (eng_->get_counters(ctx_, &c1) == 0) number_of_proccessed_cells_ = (uint32_t)(c1.bf_cells - c0.bf_cells);
-    if (transient_map_) {                                          // :322-379
-        rc = transient::prune(eng_.get(), ctx_, *surface, pose_, resolution_, l2_max_, truncated_range_, 2.0, &last_deleted_);
-        if (rc) fail(rc, "transient map");
-    }
+    (void)dev_->get_counters(dev_.get(), &c0);
+    dev_.check(dev_->pf_update_maps(dev_.get(), s.pts.data(), n, s.o, s.q), "lama_hip_pf_update_maps");
+    if (dev_->get_counters(dev_.get(), &c1) == 0) number_of_proccessed_cells_ = (uint32_t)(c1.bf_cells - c0.bf_cells);
+    if (transient_map_)                                            // :322-379
+        dev_.check(transient::prune(dev_.engine().get(), dev_.get(), *surface, pose_, resolution_, l2_max_, truncated_range_, 2.0, &last_deleted_), "transient map");
     if (summary) {                                                 // :188-194
         summary->time_mapping.push_back(now_s() - t_map);
         summary->time.push_back(now_s() - t_begin);
@@ -161,24 +141,14 @@ bool Slam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, d
 uint64_t Slam2D::getMemoryUsage() const
 {
     lama_hip_counters c;
-    if (eng_->get_counters(ctx_, &c) != 0) return 0;
+    if (dev_->get_counters(dev_.get(), &c) != 0) return 0;
     return c.dm_patches * 10240ull + c.occ_patches * 4096ull;
 }
 
-static bool dl(const HipEngine* e, lama_hip_ctx* ctx, int kind, size_t cell_bytes, std::vector<uint64_t>& ids,
-               std::vector<uint8_t>& cells, std::vector<uint64_t>& masks)
-{
-    uint32_t n = 0;
-    if (e->pf_map_patches(ctx, 0, kind, &n) != 0) return false;
-    ids.assign(n, 0); cells.assign((size_t)n * cell_bytes * 1024, 0); masks.assign((size_t)n * 16, 0);
-    uint32_t got = 0;
-    return e->pf_download_map(ctx, 0, kind, n, ids.data(), cells.data(), masks.data(), &got) == 0 && got == n;
-}
-
 bool Slam2D::downloadDistanceMap(std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks) const
-{ return has_first_scan && dl(eng_.get(), ctx_, LAMA_HIP_MAP_DISTANCE, 10, ids, cells, masks); }
+{ return has_first_scan && dev_.download(0, LAMA_HIP_MAP_DISTANCE, ids, cells, masks); }
 
 bool Slam2D::downloadOccupancyMap(std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks) const
-{ return has_first_scan && dl(eng_.get(), ctx_, LAMA_HIP_MAP_OCCUPANCY, 4, ids, cells, masks); }
+{ return has_first_scan && dev_.download(0, LAMA_HIP_MAP_OCCUPANCY, ids, cells, masks); }
 
 } // namespace lama

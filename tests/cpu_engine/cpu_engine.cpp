@@ -5,6 +5,8 @@
 // gloo tests.  It lives under tests/, links the oracle, and is never shipped, built or loaded by the product:
 // it is only reachable through lama_host_set_engine_library(), which exists only in the test-suite's own -DLAMA_TESTING build of the host library.
 // "Device buffers" of export/import are plain host pointers here.
+#include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -42,6 +44,29 @@ Scan make_scan(const double* pts, uint32_t n, const double* origin, const double
 SE2 se2_of(const double* p) { SE2 s; s.c = p[0]; s.s = p[1]; s.tx = p[2]; s.ty = p[3]; return s; }
 void se2_to(const SE2& s, double* p) { p[0] = s.c; p[1] = s.s; p[2] = s.tx; p[3] = s.ty; }
 
+// the device library's contract for every scan it takes (csrc/lama_hip.hip, upload of the scan): a non-finite point is refused
+bool scan_refused(lama_hip_ctx* c, const double* pts, uint32_t n)
+{
+    for (size_t i = 0; pts && i < 3 * (size_t)n; ++i)
+        if (!std::isfinite(pts[i])) { c->error = "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"; return true; }
+    return false;
+}
+
+// a context that has seen no scan yet gets empty maps (upload, addObstacle or key scans come first for Loc2D / MapBuilder2D)
+void ensure_maps(lama_hip_ctx* c)
+{
+    if (c->init) return;
+    for (uint32_t i = 0; i < c->cfg.particles; ++i) {
+        c->dm[i] = std::make_shared<DynamicDistanceMap>(c->cfg.resolution, c->cfg.patch_size);
+        c->dm[i]->setMaxDistance(c->cfg.l2_max);
+        c->occ[i] = std::make_shared<FrequencyOccupancyMap>(c->cfg.resolution, c->cfg.patch_size);
+    }
+    c->init = true;
+}
+
+// calls the tests count (lama_cpu_engine_call_counts): contexts created and destroyed, map downloads asked for with cap == 0
+std::atomic<uint64_t> g_created{0}, g_destroyed{0}, g_zero_cap_downloads{0};
+
 template <class M>
 std::vector<uint64_t> sorted_ids(const M& m)
 {
@@ -53,6 +78,8 @@ std::vector<uint64_t> sorted_ids(const M& m)
 } // namespace
 
 extern "C" {
+
+void lama_cpu_engine_call_counts(uint64_t out3[3]) { out3[0] = g_created; out3[1] = g_destroyed; out3[2] = g_zero_cap_downloads; }
 
 void lama_hip_default_cfg(lama_hip_cfg* cfg)
 {
@@ -77,12 +104,14 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg, lama_hip_ctx** out)
     c->dm.resize(cfg->particles);
     c->occ.resize(cfg->particles);
     *out = c;
+    ++g_created;
     return LAMA_HIP_OK;
 }
-void lama_hip_ctx_destroy(lama_hip_ctx* c) { delete c; }
+void lama_hip_ctx_destroy(lama_hip_ctx* c) { if (c) ++g_destroyed; delete c; }
 
 int32_t lama_hip_pf_init(lama_hip_ctx* c, const double* pts, uint32_t n, const double* origin, const double* quat, const double* pose0)
 {
+    if (scan_refused(c, pts, n)) return LAMA_HIP_E_INVALID;
     Scan s = make_scan(pts, n, origin, quat);
     if (c->cfg.occupancy_policy == 1) {          // one-"particle" log-odds context (LidarOdometry2D)
         c->last_scan = s;
@@ -126,6 +155,7 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
                                double* poses_out, double* loglik_out, int32_t* iters_out)
 {
     if (!c->init) { c->error = "scan_match before init"; return LAMA_HIP_E_STATE; }
+    if (scan_refused(c, pts, n)) return LAMA_HIP_E_INVALID;
     Scan s = make_scan(pts, n, origin, quat);
     c->last_scan = s;
     c->tool->stage_set_scan(s);
@@ -168,6 +198,7 @@ int32_t lama_hip_pf_resample(lama_hip_ctx* c, const int32_t* idx)
 // a call through the PLT could bind to that one)
 static int32_t update_maps_impl(lama_hip_ctx* c, const double* pts, uint32_t n, const double* origin, const double* quat)
 {
+    if (scan_refused(c, pts, n)) return LAMA_HIP_E_INVALID;
     Scan s = pts ? make_scan(pts, n, origin, quat) : c->last_scan;
     if (c->cfg.occupancy_policy == 1) {
         double mn[3], mx[3];
@@ -209,6 +240,7 @@ int32_t lama_hip_pf_download_map(lama_hip_ctx* c, uint32_t particle, int32_t kin
                    : (c->cfg.occupancy_policy == 1 ? (const Map&)*c->pocc[particle] : (const Map&)*c->occ[particle]);
     std::vector<uint64_t> v = sorted_ids(m);
     if (num) *num = (uint32_t)v.size();
+    if (cap == 0) ++g_zero_cap_downloads;
     const size_t cb = (kind == LAMA_HIP_MAP_DISTANCE ? 10 : 4) * 1024;
     for (uint32_t k = 0; k < v.size() && k < cap; ++k) {
         const Container& ct = *m.patches.at(v[k]);
@@ -221,14 +253,7 @@ int32_t lama_hip_pf_download_map(lama_hip_ctx* c, uint32_t particle, int32_t kin
 
 int32_t lama_hip_pf_upload_map(lama_hip_ctx* c, uint32_t particle, int32_t kind, uint32_t n, const uint64_t* ids, const uint8_t* cells, const uint64_t* masks)
 {
-    if (!c->init) {
-        for (uint32_t i = 0; i < c->cfg.particles; ++i) {
-            c->dm[i] = std::make_shared<DynamicDistanceMap>(c->cfg.resolution, c->cfg.patch_size);
-            c->dm[i]->setMaxDistance(c->cfg.l2_max);
-            c->occ[i] = std::make_shared<FrequencyOccupancyMap>(c->cfg.resolution, c->cfg.patch_size);
-        }
-        c->init = true;
-    }
+    ensure_maps(c);
     Map& m = kind == LAMA_HIP_MAP_DISTANCE ? (Map&)*c->dm[particle] : (c->cfg.occupancy_policy == 1 ? (Map&)*c->pocc[particle] : (Map&)*c->occ[particle]);
     const size_t cb = (kind == LAMA_HIP_MAP_DISTANCE ? 10 : 4) * 1024;
     m.patches.clear();
@@ -349,14 +374,7 @@ int32_t lama_hip_reset_counters(lama_hip_ctx* c) { std::memset(&c->ctr, 0, sizeo
 
 int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uint32_t* cells_xy, uint32_t n)
 {
-    if (!c->init) {
-        for (uint32_t i = 0; i < c->cfg.particles; ++i) {
-            c->dm[i] = std::make_shared<DynamicDistanceMap>(c->cfg.resolution, c->cfg.patch_size);
-            c->dm[i]->setMaxDistance(c->cfg.l2_max);
-            c->occ[i] = std::make_shared<FrequencyOccupancyMap>(c->cfg.resolution, c->cfg.patch_size);
-        }
-        c->init = true;
-    }
+    ensure_maps(c);
     for (uint32_t k = 0; k < n; ++k) c->dm[particle]->addObstacle(V3u{cells_xy[2 * k], cells_xy[2 * k + 1], 0});
     c->dm[particle]->update();
     return LAMA_HIP_OK;
@@ -401,6 +419,7 @@ static int32_t match_solve_impl(lama_hip_ctx* c, uint32_t particle, const double
                                 double* pose, double* out7, int32_t* iters, int32_t do_solve, int32_t strategy, uint32_t max_iterations)
 {
     const uint32_t max_iter = max_iterations ? max_iterations : c->cfg.max_iter;
+    if (scan_refused(c, pts, n)) return LAMA_HIP_E_INVALID;
     Scan s = make_scan(pts, n, origin, quat);
     MatchSurface2D ms(c->dm[particle].get(), &s, se2_of(pose));
     CauchyWeight cauchy(0.15);
@@ -492,6 +511,56 @@ int32_t lama_hip_map_sample_likelihood(lama_hip_ctx* c, uint32_t particle, const
         }
         l_out[k] = l;
     }
+    return LAMA_HIP_OK;
+}
+
+// MapBuilder2D: every key scan into the occupancy map -- a hit at each point and, with LAMA_HIP_MAP_BUILD_FULL, free cells along the
+// beam from the sensor's cell; LAMA_HIP_MAP_BUILD_PRUNE then forgets the cells seen exactly once (FrequencyOccupancyMap::prune)
+int32_t lama_hip_map_integrate_scans(lama_hip_ctx* c, uint32_t particle, uint32_t num_scans, const double* poses4, const double* pts,
+                                     const uint32_t* offs, const double* origins, const double* quats, uint32_t flags)
+{
+    if (!poses4 || !offs) { c->error = "poses4 / scan_offsets missing"; return LAMA_HIP_E_INVALID; }
+    for (uint32_t k = 0; k < num_scans; ++k)
+        if (offs[k + 1] < offs[k]) { c->error = "scan_offsets must not decrease"; return LAMA_HIP_E_INVALID; }
+    if (scan_refused(c, pts + 3 * (size_t)offs[0], offs[num_scans] - offs[0])) {
+        c->error = "a key scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)";
+        return LAMA_HIP_E_INVALID;
+    }
+    ensure_maps(c);
+    FrequencyOccupancyMap& occ = *c->occ[particle];
+    for (uint32_t k = 0; k < num_scans; ++k) {
+        const Scan s = make_scan(pts + 3 * (size_t)offs[k], offs[k + 1] - offs[k], origins ? origins + 3 * k : nullptr, quats ? quats + 4 * k : nullptr);
+        const Affine3 tf = affine_mul(fixed_tf(se2_of(poses4 + 4 * k)), moving_tf(s));
+        const V3u from = occ.w2m(affine_apply(tf, V3d{0.0, 0.0, 0.0}));
+        for (const V3d& p : s.points) {
+            const V3u hit = occ.w2m(affine_apply(tf, p));
+            occ.setOccupied(hit);
+            if (flags & LAMA_HIP_MAP_BUILD_FULL) occ.computeRay(from, hit, [&](const V3u& cell) { occ.setFree(cell); });
+        }
+    }
+    if (flags & LAMA_HIP_MAP_BUILD_PRUNE) {
+        std::vector<V3u> cells;
+        occ.visit_all_cells([&](const V3u& cell) { cells.push_back(cell); });
+        for (const V3u& cell : cells) {
+            frequency* f = (frequency*)occ.get(cell);
+            if (f->visited == 1 && f->occupied <= 1) f->visited = f->occupied = 0;
+        }
+    }
+    return LAMA_HIP_OK;
+}
+
+// the occupied cells in visit_all_cells order; *num is their number, cells_xy takes the first cap of them
+int32_t lama_hip_map_occupied_cells(lama_hip_ctx* c, uint32_t particle, uint32_t cap, uint32_t* cells_xy, uint32_t* num)
+{
+    ensure_maps(c);
+    const FrequencyOccupancyMap& occ = *c->occ[particle];
+    uint32_t n = 0;
+    occ.visit_all_cells([&](const V3u& cell) {
+        if (!occ.isOccupied(cell)) return;
+        if (cells_xy && n < cap) { cells_xy[2 * n] = cell.x; cells_xy[2 * n + 1] = cell.y; }
+        ++n;
+    });
+    if (num) *num = n;
     return LAMA_HIP_OK;
 }
 
