@@ -221,6 +221,8 @@ private:
     void syncDevice();
     double normal(double stddev);
     void uploadLocalPoses();
+    // updateBegin; whole_step: the device also queues the map update of the matched poses (HipEngine::pf_match_and_map)
+    Phase beginStep(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, double timestamp, bool whole_step);
     void scanToArrays(const PointCloudXYZ& s);
 
     Options options_;
@@ -243,6 +245,7 @@ private:
     // summary bookkeeping
     double t_begin_ = 0, t_solve_ = 0;
     bool scan_resident_ = false;
+    int whole_step_ = -1;                   // update(): the device context splits a step into particle groups (-1: not asked yet)
     mutable std::unique_ptr<FrequencyOccupancyMap> occ_view_;     // snapshots handed out by getOccupancyMap / getDistanceMap
     mutable std::unique_ptr<DynamicDistanceMap> dm_view_;
     void dropMapViews() { occ_view_.reset(); dm_view_.reset(); }

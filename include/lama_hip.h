@@ -169,6 +169,33 @@ int32_t lama_hip_pf_upload_map(lama_hip_ctx* ctx, uint32_t particle, int32_t kin
 int32_t lama_hip_pf_update_maps_begin(lama_hip_ctx* ctx, const double* pts_xyz, uint32_t n,
                                       const double* sensor_origin3, const double* sensor_quat_wxyz);
 int32_t lama_hip_sync(lama_hip_ctx* ctx);
+/* One whole device step of a filter: lama_hip_pf_set_poses(poses_in) + lama_hip_pf_scan_match + lama_hip_pf_update_maps_begin of the
+ * MATCHED poses, i.e. a step in which the resample, if one is due, follows the map update instead of preceding it.  That order gives
+ * the same poses and maps bit for bit (a resample copies a particle's pose and both maps and touches nothing else; a particle's map
+ * update is a function of its own pose, its own maps and the scan), and it lets a pool below the routing threshold (64 particles)
+ * run as contiguous particle groups (three by default), each on a stream of its own: a group goes on to its ray-cast and brushfire as soon
+ * as ITS scan match is back, and the call returns, with all results, while every group's map update is still queued or running.
+ * Nothing in it waits for a map update: the status of a group's update travels with the results of the group's next scan match, so
+ * a deferred error is returned by the next call on the context, as with _begin.  Every other entry point first waits for all groups.
+ * A lama_hip_pf_resample that follows while the groups are still running is likewise only recorded and carried out by the next call
+ * on the context (its error, if any, is that call's), so that the caller's host work of the next step runs beside the map kernels.
+ * Larger pools, and scans or configurations that need more than the plain parallel map update, run the three calls above as they
+ * are.  poses_out [P][4] / loglik_out [P] / iters_out [P] may be NULL.  LAMA_HIP_STEP_GROUPS=n in the environment at context
+ * creation overrides the number of groups (1 .. 4; 1 = the single-stream schedule). */
+int32_t lama_hip_pf_match_and_map(lama_hip_ctx* ctx, const double* pts_xyz, uint32_t n, const double* sensor_origin3,
+                                  const double* sensor_quat_wxyz, const double* poses_in, double* poses_out, double* loglik_out,
+                                  int32_t* iters_out);
+/* After an error return of lama_hip_pf_match_and_map the step is LOST and must not be repeated: the groups taken before the failing one
+ * have queued their map update of this scan already (a second call with the same scan would integrate it twice there), and the
+ * context's poses are a mix of matched and predicted ones.  The context itself takes further calls as after any other failed call.
+ *
+ * *ran: how many particle groups the last lama_hip_pf_match_and_map of the context really ran (empty groups of a pool with fewer
+ * particles than groups do not count; 1: the single-stream schedule; 0: none yet) -- waits for the device like every other entry
+ * point.  *configured: into how many groups a step of this context is split when it can be (0: never -- a pool of 64 particles or
+ * more, or an override of 1: every step is the three calls above), fixed at creation; asking
+ * for it alone (ran == NULL) waits for nothing.  Either pointer may be NULL.  (These two figures are not members of
+ * lama_hip_counters.) */
+int32_t lama_hip_pf_step_groups(lama_hip_ctx* ctx, uint32_t* ran, uint32_t* configured);
 /* HIP device ordinal the context lives on (cfg.device); < 0 for a null context.  Lets a caller of a multi-GPU object check
  * that its shards really sit on distinct devices. */
 int32_t lama_hip_ctx_device(const lama_hip_ctx* ctx);
@@ -491,7 +518,7 @@ typedef struct lama_hip_counters {
     uint32_t struct_bytes;              /* sizeof(lama_hip_counters) of the library that filled the struct (see lama_hip_get_counters_sized) */
     double peer_copy_ms;                /* device time (hipEvents on the destination's stream) of the cross-device lama_hip_blob_copy calls ... */
     uint64_t peer_copy_bytes;           /* ... and the bytes they moved INTO this context: bytes / ms = the achieved xGMI rate               */
-} lama_hip_counters;
+} lama_hip_counters;      /* (the group count of the grouped step schedule: lama_hip_pf_step_groups, not a member here) */
 int32_t lama_hip_get_counters(lama_hip_ctx* ctx, lama_hip_counters* out);
 /* The same for a caller compiled against another version of this header: at most `bytes` bytes are written (the struct
  * grows at its END only, a consumer built against an older header passes its own sizeof and is never written past). */

@@ -158,6 +158,34 @@ struct PinVec {
     const T& operator[](size_t i) const { return p[i]; }
 };
 
+// One particle group of the grouped step schedule (lama_hip_pf_match_and_map): a contiguous block of the pool with a stream of its
+// own and its own copy of everything that is a pool-wide scalar or list of an update.  Arrays indexed by particle stay the context's.
+// Three groups by default: the context's three streams of the routed / early lanes, idle in small pools.  With the runtime's default
+// of four hardware queues per process they get a queue each; a fourth stream shares one with the third, and the two groups' brushfire
+// kernels then run one after the other (measured: a 30-particle step takes 2.65 ms with four groups, 1.39 ms with three, 1.47 ms with
+// one; profiles/r07_step_groups.md).  Four can be asked for (LAMA_HIP_STEP_GROUPS) where the process has more queues.
+constexpr uint32_t MAX_STEP_GROUPS = 4;
+constexpr uint32_t DEFAULT_STEP_GROUPS = 3;
+struct StepGroup {
+    hipStream_t s = nullptr;          // one of the context's streams (not owned)
+    uint32_t first = 0, count = 0;
+    DevBuf<uint32_t> d_words;         // [0]: error word, [2..9]: hand-over counts (DevParams::slow_n)
+    DevBuf<uint32_t> d_slow_list;     // [4][P] hand-over lists (DevParams::slow_list)
+    DevBuf<double> d_pts;             // the group's own copy of the scan, uploaded on its stream
+    DevBuf<uint8_t> d_pack; PinVec<uint8_t> h_pack;      // k_pack_group's block and its page-locked destination
+    Event ev_match;                   // the block has arrived
+    Event tev[6];                     // cfg.profile: brackets of scan match, ray-cast, brushfire
+    uint32_t timed = 0;               // ... which of them have been recorded and not read yet (bit per bracket)
+    bool maps_queued = false;         // a map update whose status has not been collected yet
+    // what that update was asked to do (a clean abort repeats it after the arenas grew): poses, mount, scan slot, beams, reach
+    std::vector<double> upd_poses; Affine upd_mtf; uint32_t upd_slot = 0, upd_n = 0; double upd_reach = 0.0;
+};
+// byte offsets inside a group's block for `n` particles (k_pack_group writes it)
+struct GroupPack {
+    size_t poses, loglik, stats, guard, counts, iters, words, bytes;
+    explicit GroupPack(size_t n) : poses(0), loglik(32 * n), stats(40 * n), guard(72 * n), counts(76 * n), iters(84 * n), words(88 * n), bytes(88 * n + 64) {}
+};
+
 struct lama_hip_ctx {
     lama_hip_cfg cfg;
     std::string error;
@@ -258,6 +286,17 @@ struct lama_hip_ctx {
     // host-side effects of a map update that a repeated pass (recover_update) must not apply twice
     uint32_t saved_visit_bound = 0; lama_hip_counters saved_ctr;
     bool pending_maps = false;        // lama_hip_pf_update_maps_begin queued work whose status has not been collected yet
+    // grouped step schedule (lama_hip_pf_match_and_map): pools below route_min_count are split into step_groups contiguous blocks
+    StepGroup grp[MAX_STEP_GROUPS];
+    Stream stream4;
+    uint32_t step_groups = 1;         // 1: the single-stream schedule (LAMA_HIP_STEP_GROUPS overrides, read at creation)
+    uint32_t groups_ran = 0;          // how many groups the last lama_hip_pf_match_and_map really ran (lama_hip_pf_step_groups)
+    std::vector<int32_t> deferred_idx; bool resample_deferred = false;      // lama_hip_pf_resample while the groups were busy: made by the next call
+    bool groups_busy = false;         // group streams may hold work: whoever touches shared state on the main stream waits for them first
+    PinVec<double> h_pts2; uint32_t scan_slot = 0;       // second scan staging buffer: a step's scan outlives the step (repeat after a clean abort)
+    std::vector<uint64_t> h_chain;    // per-particle brushfire cell counts of the map update whose status is being collected
+    bool chain_dirty = false;
+    double step_ms[3] = {0, 0, 0}; bool step_ms_any[3] = {false, false, false};     // longest group bracket of the update being collected
     PinVec<double> h_poses;           // host mirror of the particle poses (source of truth between calls)
     PinVec<int32_t> h_counts;         // host mirror of counts of the current set (refreshed after map updates)
     lama_hip_counters ctr;
@@ -267,6 +306,7 @@ struct lama_hip_ctx {
     {
         (void)hipSetDevice(cfg.device);
         if (stream) (void)hipStreamSynchronize(stream);
+        for (StepGroup& g : grp) if (g.s) (void)hipStreamSynchronize(g.s);
     }
 };
 
@@ -278,6 +318,7 @@ int32_t hip_fail(lama_hip_ctx* ctx, hipError_t e, const char* what)
 {
     ctx->error = std::string(what) + ": " + hipGetErrorString(e);
     (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->groups_busy) for (StepGroup& g : ctx->grp) if (g.s) (void)hipStreamSynchronize(g.s);
     return LAMA_HIP_E_HIP;
 }
 #define HIPCHK(ctx, call)                                                                              \
@@ -347,6 +388,25 @@ DevParams make_params(const lama_hip_ctx* c)
     return p;
 }
 
+// the kernels of one particle group: the context's parameters with the group's own error word and hand-over lists
+DevParams group_params(const lama_hip_ctx* c, const StepGroup& g)
+{
+    DevParams p = make_params(c);
+    p.err = reinterpret_cast<int32_t*>(g.d_words.p); p.slow_n = g.d_words.p + 2; p.slow_list = g.d_slow_list;
+    return p;
+}
+
+// Nothing runs on the group streams any more when this returns.  Whoever touches, on the main stream, state that all particles
+// share -- the window directories, the particle table and the regions behind it, the pools -- calls it first (the grouped step
+// schedule's rare paths are drained, not made clever).
+int32_t wait_for_groups(lama_hip_ctx* c)
+{
+    if (!c->groups_busy) return LAMA_HIP_OK;
+    for (StepGroup& g : c->grp)
+        if (g.count) { const hipError_t e = hipStreamSynchronize(g.s); if (e != hipSuccess) { c->error = std::string("hipStreamSynchronize(group stream): ") + hipGetErrorString(e); return LAMA_HIP_E_HIP; } }
+    return LAMA_HIP_OK;
+}
+
 int32_t upload_scan(lama_hip_ctx* c, const double* pts, uint32_t n)
 {
     if (!pts) {      // reuse the scan uploaded by the previous call (same scan for scan_match and update_maps)
@@ -382,10 +442,40 @@ void resolve_timers(lama_hip_ctx* c);
 
 // End of an API call: one stream synchronisation that brings back the device error word and, when asked, the
 // per-particle patch counts and statistics (a single host round trip per call).
-int32_t grow_arenas(lama_hip_ctx* c, uint32_t need_dm, uint32_t need_occ);
+int32_t grow_arenas(lama_hip_ctx* c, uint32_t first, uint32_t count);
 int32_t recover_update(lama_hip_ctx* c, int32_t e);
-int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count);
+int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count, StepGroup* g = nullptr);
 int32_t permute_particles(lama_hip_ctx* c, const int32_t* idx);
+
+// A failed allocation keeps counting (dir_alloc_one: the counts then say what a particle WANTED, which the clean-abort path
+// uses).  When the error is final, the counts go back into the regions: every later copy (resample, export, a region move)
+// is sized from them and must not run into a neighbour's region.
+int32_t clamp_counts(lama_hip_ctx* c, bool fetch)
+{
+    if (fetch) HIPCHK(c, hipMemcpyAsync(c->h_counts.data(), c->ms.counts, sizeof(int32_t) * 2 * c->P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool clamped = false;
+    for (uint32_t p = 0; p < c->P; ++p) {
+        const HostPart& hp = c->h_part[p];
+        if ((uint32_t)c->h_counts[2 * p] > hp.dm_cap) { c->h_counts[2 * p] = (int32_t)hp.dm_cap; clamped = true; }
+        if ((uint32_t)c->h_counts[2 * p + 1] > hp.occ_cap) { c->h_counts[2 * p + 1] = (int32_t)hp.occ_cap; clamped = true; }
+    }
+    if (clamped) {
+        HIPCHK(c, hipMemcpyAsync(c->ms.counts, c->h_counts.data(), sizeof(int32_t) * 2 * c->P, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return LAMA_HIP_OK;
+}
+
+// what a non-zero device error word means to the caller
+int32_t device_error_result(lama_hip_ctx* c, int32_t e)
+{
+    if (e & ERR_WINDOW) return fail(c, LAMA_HIP_E_WINDOW, "a map cell fell outside the device window (the mapped area is wider than 1016 patches)");
+    if (e & ERR_DM_CAP) return fail(c, LAMA_HIP_E_CAPACITY, "a particle's distance map exceeds 32767 patches (or the device is out of memory)");
+    if (e & ERR_OCC_CAP) return fail(c, LAMA_HIP_E_CAPACITY, "a particle's occupancy map exceeds 32767 patches (or the device is out of memory)");
+    if (e & ERR_QUEUE) return fail(c, LAMA_HIP_E_CAPACITY, "brushfire queue full (raise cfg.queue_capacity)");
+    return fail(c, LAMA_HIP_E_NUMERIC, "unit complex number is (near) zero (SophusException in the reference)");
+}
 
 int32_t check_device_errors(lama_hip_ctx* c, bool maps = false, bool match = false, bool err_in_results = false)
 {
@@ -427,41 +517,23 @@ int32_t check_device_errors(lama_hip_ctx* c, bool maps = false, bool match = fal
             const int32_t rr = recover_update(c, e);
             if (rr != LAMA_HIP_E_CAPACITY) return rr;      // done (or another error); E_CAPACITY: the arenas are at their limit
         }
-        if (e & (ERR_DM_CAP | ERR_OCC_CAP)) {
-            // A failed allocation keeps counting (dir_alloc_one: the counts then say what a particle WANTED, which the clean-abort path
-            // uses).  When the error is final, the counts go back into the regions: every later copy (resample, export, a region move)
-            // is sized from them and must not run into a neighbour's region.
-            if (!stats) HIPCHK(c, hipMemcpyAsync(c->h_counts.data(), c->ms.counts, sizeof(int32_t) * 2 * c->P, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            bool clamped = false;
-            for (uint32_t p = 0; p < c->P; ++p) {
-                const HostPart& hp = c->h_part[p];
-                if ((uint32_t)c->h_counts[2 * p] > hp.dm_cap) { c->h_counts[2 * p] = (int32_t)hp.dm_cap; clamped = true; }
-                if ((uint32_t)c->h_counts[2 * p + 1] > hp.occ_cap) { c->h_counts[2 * p + 1] = (int32_t)hp.occ_cap; clamped = true; }
-            }
-            if (clamped) {
-                HIPCHK(c, hipMemcpyAsync(c->ms.counts, c->h_counts.data(), sizeof(int32_t) * 2 * c->P, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-            }
-        }
-        if (e & ERR_WINDOW) return fail(c, LAMA_HIP_E_WINDOW, "a map cell fell outside the device window (the mapped area is wider than 1016 patches)");
-        if (e & ERR_DM_CAP) return fail(c, LAMA_HIP_E_CAPACITY, "a particle's distance map exceeds 32767 patches (or the device is out of memory)");
-        if (e & ERR_OCC_CAP) return fail(c, LAMA_HIP_E_CAPACITY, "a particle's occupancy map exceeds 32767 patches (or the device is out of memory)");
-        if (e & ERR_QUEUE) return fail(c, LAMA_HIP_E_CAPACITY, "brushfire queue full (raise cfg.queue_capacity)");
-        return fail(c, LAMA_HIP_E_NUMERIC, "unit complex number is (near) zero (SophusException in the reference)");
+        if (e & (ERR_DM_CAP | ERR_OCC_CAP)) { const int32_t rcl = clamp_counts(c, !stats); if (rcl) return rcl; }
+        return device_error_result(c, e);
     }
     if (stats) {
         const PinVec<uint64_t>& st = c->h_stats;
         uint64_t dm = 0, oc = 0;
+        // (a map update's statistics: of the particles it ran for -- a block's update leaves the others' words alone)
+        const uint32_t m0 = c->last_first, m1 = c->last_first + c->last_count;
         for (uint32_t p = 0; p < c->P; ++p) {
             if (match) { c->ctr.gn_iterations += st[4 * p]; c->ctr.gn_evals += st[4 * p + 1]; }
-            if (maps) { c->ctr.ray_cells += st[4 * p + 2]; c->ctr.bf_cells += st[4 * p + 3]; }
+            if (maps && p >= m0 && p < m1) { c->ctr.ray_cells += st[4 * p + 2]; c->ctr.bf_cells += st[4 * p + 3]; }
             dm += c->h_counts[2 * p]; oc += c->h_counts[2 * p + 1];
         }
         c->ctr.dm_patches = dm; c->ctr.occ_patches = oc;
         if (maps) {                                                  // the update lasted as long as its longest chain
             uint64_t mx = 0, sum = 0; uint32_t arg = 0;
-            for (uint32_t p = 0; p < c->P; ++p) { sum += st[4 * p + 3]; if (st[4 * p + 3] > mx) { mx = st[4 * p + 3]; arg = p; } }
+            for (uint32_t p = m0; p < m1; ++p) { sum += st[4 * p + 3]; if (st[4 * p + 3] > mx) { mx = st[4 * p + 3]; arg = p; } }
             c->ctr.bf_longest_chain_sum += mx; c->ctr.bf_longest_chain_last = mx;
             if (c->debug_tail) {
                 // (how well would the scan match's log-likelihood have predicted the longest chain? its rank among the pool, 0 = lowest)
@@ -475,7 +547,7 @@ int32_t check_device_errors(lama_hip_ctx* c, bool maps = false, bool match = fal
                 std::fprintf(stderr, "brushfire pops: mean %.0f max %llu (particle %u) handovers %u brushfire %.3f ms; log-lik of that particle %.1f (pool mean %.1f), rank %u of %u\n", (double)sum / c->P, (unsigned long long)mx, arg, c->h_slow_n[0], c->ctr.ms_brushfire, ll, mean_ll, rank, c->P);
             }
         }
-        if (maps) return grow_arenas(c, 0, 0);
+        if (maps) return grow_arenas(c, 0, c->P);
     }
     return LAMA_HIP_OK;
 }
@@ -615,6 +687,7 @@ int32_t set_capacities(lama_hip_ctx* c, const std::vector<CapRequest>& reqs)
     // front: the lists must not be re-allocated while a transfer is pending) and of nothing else -- the device-side lists are read by
     // a group's kernels before the next group's upload overwrites them, in stream order.
     constexpr size_t GROUP = 64;
+    { const int32_t rw = wait_for_groups(c); if (rw) return rw; }      // regions move, the particle table is rewritten: on an idle device only
     struct Old { bool dm; uint32_t chunk, off, cap; };
     bool any = false;
     int32_t err = LAMA_HIP_OK;                                     // a failed allocation: what was planned so far is still carried out (the table,
@@ -670,14 +743,15 @@ int32_t set_capacities(lama_hip_ctx* c, const std::vector<CapRequest>& reqs)
 }
 
 // after a map update (counts on the host, stream idle): every particle keeps head room for the next one
-int32_t grow_arenas(lama_hip_ctx* c, uint32_t /*need_dm*/, uint32_t /*need_occ*/)
+int32_t grow_arenas(lama_hip_ctx* c, uint32_t first, uint32_t count)
 {
     std::vector<CapRequest> reqs;
     // the guard's bound of the last update says what the next one will ask for (open space: many occupancy patches without a
     // distance-map patch nearby)
-    for (uint32_t p = 0; p < c->P; ++p) {
+    for (uint32_t p = first; p < first + count; ++p) {
         const HostPart& pr = c->h_part[p];
         const uint32_t dmc = (uint32_t)c->h_counts[2 * p], occ = (uint32_t)c->h_counts[2 * p + 1];
+        if (dmc > pr.dm_cap || occ > pr.occ_cap) continue;      // a cleanly aborted update of another particle group: its own repeat grows it
         const uint32_t gh = p < c->h_guard.size() ? c->h_guard[p] : 0u;
         uint32_t nd = pr.dm_cap, no = pr.occ_cap;
         if (dmc + std::max<uint32_t>(std::max<uint32_t>(16u, dmc / 16u), gh) > pr.dm_cap) nd = want_capacity(c->floor_dm, dmc, gh + gh / 4u);
@@ -715,7 +789,7 @@ int32_t recover_update(lama_hip_ctx* c, int32_t e)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<CapRequest> reqs;
     bool at_limit = false, fixed_counts = false;
-    for (uint32_t p = 0; p < c->P; ++p) {
+    for (uint32_t p = c->last_first; p < c->last_first + c->last_count; ++p) {      // (the particles of the aborted update)
         HostPart& pr = c->h_part[p];
         uint32_t wdm = (uint32_t)c->h_counts[2 * p], wocc = (uint32_t)c->h_counts[2 * p + 1];
         uint32_t nd = pr.dm_cap, no = pr.occ_cap;
@@ -746,14 +820,25 @@ int32_t recover_update(lama_hip_ctx* c, int32_t e)
 
 // Collects the status of a map update queued by lama_hip_pf_update_maps_begin (one synchronisation); called at the start of
 // every other entry point, so a deferred error surfaces in the next call on the context.
+int32_t drain_groups(lama_hip_ctx* c);
+int32_t apply_resample(lama_hip_ctx* c, const int32_t* idx);
 int32_t finish_pending(lama_hip_ctx* c)
 {
-    if (!c->pending_maps) return LAMA_HIP_OK;
-    c->pending_maps = false;
-    (void)hipSetDevice(c->cfg.device);
-    const int32_t rc = check_device_errors(c, true, false);
-    if (rc) c->error = "deferred from lama_hip_pf_update_maps_begin: " + c->error;
-    return rc;
+    if (c->groups_busy) { (void)hipSetDevice(c->cfg.device); const int32_t rg = drain_groups(c); if (rg) { c->resample_deferred = false; return rg; } }
+    if (c->pending_maps) {
+        c->pending_maps = false;
+        (void)hipSetDevice(c->cfg.device);
+        const int32_t rc = check_device_errors(c, true, false);
+        if (rc) { c->error = "deferred from lama_hip_pf_update_maps_begin: " + c->error; c->resample_deferred = false; return rc; }
+    }
+    if (c->resample_deferred) {                                     // (lama_hip_pf_resample while the groups were still running)
+        c->resample_deferred = false;
+        (void)hipSetDevice(c->cfg.device);
+        const int32_t rc = apply_resample(c, c->deferred_idx.data());
+        if (rc) c->error = "deferred from lama_hip_pf_resample: " + c->error;
+        return rc;
+    }
+    return LAMA_HIP_OK;
 }
 #define ENTER(c) do { if ((c)->poisoned) return fail((c), LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue"); const int32_t rc_enter_ = finish_pending(c); if (rc_enter_) return rc_enter_; } while (0)
 
@@ -761,6 +846,15 @@ int32_t finish_pending(lama_hip_ctx* c)
 // stream synchronisation, so profiling adds no host round trips.
 struct Timer {
     lama_hip_ctx* c; double* acc; uint64_t* launches; hipEvent_t a = nullptr, b = nullptr;
+    StepGroup* g = nullptr; int kind = 0;
+    // a particle group's bracket (kind 0: scan match, 1: ray-cast, 2: brushfire): the group's own events on its own stream; read by
+    // take_group_timers once the group's next block has arrived
+    Timer(lama_hip_ctx* c_, StepGroup* g_, int kind_) : c(c_), acc(nullptr), launches(nullptr), g(g_), kind(kind_)
+    {
+        if (!c->cfg.profile) return;
+        a = g->tev[2 * kind]; b = g->tev[2 * kind + 1];
+        (void)hipEventRecord(a, g->s);
+    }
     Timer(lama_hip_ctx* c_, double* acc_, uint64_t* l_) : c(c_), acc(acc_), launches(l_)
     {
         if (!c->cfg.profile) return;
@@ -772,10 +866,43 @@ struct Timer {
     void stop()
     {
         if (!c->cfg.profile) return;
+        if (g) { (void)hipEventRecord(b, g->s); g->timed |= 1u << kind; return; }
         (void)hipEventRecord(b, c->stream);
         c->pending.push_back({a, b, acc, launches});
     }
 };
+
+// the brackets of a group whose stream has passed them: the step's figure is the LONGEST group's (flush_step_timers adds it)
+void take_group_timers(lama_hip_ctx* c, StepGroup& g)
+{
+    for (int k = 0; k < 3; ++k) {
+        if (!(g.timed & (1u << k))) continue;
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, g.tev[2 * k], g.tev[2 * k + 1]) == hipSuccess) { c->step_ms[k] = std::max(c->step_ms[k], (double)ms); c->step_ms_any[k] = true; }
+    }
+    g.timed = 0;
+}
+
+// end of a grouped step (or of a drain): ms_* accumulate the longest group's bracket, launches_* count updates; the longest chain of the
+// update whose statuses have just been collected keeps its pool-wide meaning
+void flush_step_figures(lama_hip_ctx* c)
+{
+    double* acc[3] = {&c->ctr.ms_scan_match, &c->ctr.ms_raycast, &c->ctr.ms_brushfire};
+    uint64_t* cnt[3] = {&c->ctr.launches_scan_match, &c->ctr.launches_raycast, &c->ctr.launches_brushfire};
+    for (int k = 0; k < 3; ++k) {
+        if (c->step_ms_any[k]) { *acc[k] += c->step_ms[k]; *cnt[k] += 1; }
+        c->step_ms[k] = 0; c->step_ms_any[k] = false;
+    }
+    c->ctr.ms_update_maps = c->ctr.ms_raycast + c->ctr.ms_brushfire;
+    c->ctr.launches_update_maps = c->ctr.launches_raycast;
+    if (c->chain_dirty) {
+        uint64_t mx = 0;
+        for (uint64_t v : c->h_chain) mx = std::max(mx, v);
+        c->ctr.bf_longest_chain_sum += mx; c->ctr.bf_longest_chain_last = mx;
+        std::fill(c->h_chain.begin(), c->h_chain.end(), 0);
+        c->chain_dirty = false;
+    }
+}
 
 void resolve_timers(lama_hip_ctx* c)      // call after the stream has been synchronised
 {
@@ -807,6 +934,7 @@ int32_t regrid_window(lama_hip_ctx* c, uint32_t newW, int64_t nox, int64_t noy)
     const int dx = (int)(nox - ox), dy = (int)(noy - oy);
     const size_t WW = (size_t)c->W * c->W, nWW = (size_t)newW * newW, P = c->P;
     if (!c->initialised && newW == c->W) { c->wx0 = (uint32_t)(nox * 32); c->wy0 = (uint32_t)(noy * 32); return LAMA_HIP_OK; }   // nothing mapped yet
+    { const int32_t rw = wait_for_groups(c); if (rw) return rw; }      // the directories are every particle's
     // both directories of every home are re-tiled into fresh arrays (same side: a permutation; larger side: the window grew), then the
     // old arrays are released.  A failed allocation leaves the window as it was (nothing leaks).
     {
@@ -905,12 +1033,14 @@ int32_t fit_window(lama_hip_ctx* c, const Affine& mtf, uint32_t first, uint32_t 
 // particle dimension up (the kernels skip particles >= P).
 static unsigned xcd_grid(const lama_hip_ctx* c, uint32_t first, uint32_t count)
 {
-    return (first == 0 && count == c->P) ? (count + 7u) / 8u * 8u : count;
+    // (the last block of a pool may round up like the whole pool; the blocks in front of it cannot -- the next particle is another
+    // group's -- and are multiples of 8 wherever the split allows, see lama_hip_ctx_create)
+    return first + count == c->P ? (count + 7u) / 8u * 8u : count;
 }
 
 // allocation phase of a map update (ray records, hit cells' patches, the patches the rays cross, the bound on the distance-map patches
 // still to come): afterwards either every patch the update needs exists or an error bit is set and no map cell has been modified
-int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only)
+int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only, hipStream_t s, const double* d_pts)
 {
     const size_t need = (size_t)c->P * n;
     if (need > c->d_rrec.n) {                                       // all three are freed before any is allocated
@@ -920,14 +1050,14 @@ int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t 
         if (e == hipSuccess) e = c->d_rchunk.alloc((size_t)c->P * ((n + 63) / 64));     // per 64 beams of a particle
         if (e != hipSuccess) { c->d_rrec.reset(); return hip_fail(c, e, "ray buffers"); }
     }
-    hipLaunchKernelGGL(k_ray_hits, dim3(xcd_grid(c, first, count), (n + 255) / 256), dim3(256), 0, c->stream, prm, c->d_pts, (int)n, c->d_tfs, (int)first,
+    hipLaunchKernelGGL(k_ray_hits, dim3(xcd_grid(c, first, count), (n + 255) / 256), dim3(256), 0, s, prm, d_pts, (int)n, c->d_tfs, (int)first,
                        c->d_rrec, c->d_rbbox, alloc_only, c->d_rchunk);
     const int rw_seg = count <= 64 ? 4 : 1;
-    hipLaunchKernelGGL(k_ray_alloc_walk, dim3(xcd_grid(c, first, count), (n * rw_seg + 255) / 256), dim3(256), 0, c->stream, prm, (const lama_dev::RayRec*)c->d_rrec, (int)n, (int)first, rw_seg);
+    hipLaunchKernelGGL(k_ray_alloc_walk, dim3(xcd_grid(c, first, count), (n * rw_seg + 255) / 256), dim3(256), 0, s, prm, (const lama_dev::RayRec*)c->d_rrec, (int)n, (int)first, rw_seg);
     double far = c->scan_reach;                                   // no cell further than truncated_range from the sensor is touched
     if (c->cfg.truncated_range > 0.0) far = std::min(far, c->cfg.truncated_range);
     const int reach_cells = (int)std::ceil(far * c->scale) + 2;
-    hipLaunchKernelGGL(k_occ_reverse_dir, dim3(count), dim3(256), 0, c->stream, prm, (int)first, (const double*)c->d_tfs, reach_cells,
+    hipLaunchKernelGGL(k_occ_reverse_dir, dim3(count), dim3(256), 0, s, prm, (int)first, (const double*)c->d_tfs, reach_cells,
                        c->unguarded_retry ? 1 : 0);
     return LAMA_HIP_OK;
 }
@@ -941,31 +1071,40 @@ static uint32_t route_places(const lama_hip_ctx* c, uint32_t count)
     return std::min<uint32_t>(c->route_cap, std::max<uint32_t>(8u, (slots - count) / 7u));
 }
 
-int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count)
+int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count, StepGroup* g)
 {
-    {
+    // g: the update of one particle group of the grouped step schedule -- its stream, its scan buffer, its error word and hand-over
+    // lists; the caller has fitted the window and ruled out every path below that needs more than the plain parallel update
+    hipStream_t s = g ? g->s : (hipStream_t)c->stream;
+    const double* d_pts = g ? (const double*)g->d_pts : (const double*)c->d_pts;
+    if (!g) {
         const int32_t rcw = fit_window(c, mtf, first, count);
         if (rcw) return rcw;
+        c->last_mtf = mtf; c->last_first = first; c->last_count = count;
+        if (c->recover_depth == 0) { c->saved_visit_bound = c->visit_bound; c->saved_ctr = c->ctr; }
     }
-    c->last_mtf = mtf; c->last_first = first; c->last_count = count;
-    if (c->recover_depth == 0) { c->saved_visit_bound = c->visit_bound; c->saved_ctr = c->ctr; }
     PinVec<double>& tfs = c->h_tfs;
     tfs.resize((size_t)c->P * 12);
-    for (uint32_t p = 0; p < c->P; ++p) host_scan_tf(&c->h_poses[4 * p], mtf, &tfs[12 * (size_t)p]);
-    HIPCHK(c, hipMemcpyAsync(c->d_tfs, tfs.data(), sizeof(double) * tfs.size(), hipMemcpyHostToDevice, c->stream));
-    DevParams prm = make_params(c);
+    for (uint32_t p = first; p < first + count; ++p) host_scan_tf(&c->h_poses[4 * p], mtf, &tfs[12 * (size_t)p]);
+    HIPCHK(c, hipMemcpyAsync(c->d_tfs + 12 * (size_t)first, &tfs[12 * (size_t)first], sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
+    DevParams prm = g ? group_params(c, *g) : make_params(c);
     bool early_lane = false;
     {
-        Timer t(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
+        Timer t = g ? Timer(c, g, 1) : Timer(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
         // both ray-casts are bit-exact; the parallel one wins while the chip is not yet full of particles
-        (void)hipMemsetAsync(c->d_slow_n, 0, 32 + sizeof(uint64_t) * 4 * c->P, c->stream);      // hand-over counts and statistics: adjacent (ctx_create)
+        if (first == 0 && count == c->P && !g) {
+            (void)hipMemsetAsync(c->d_slow_n, 0, 32 + sizeof(uint64_t) * 4 * c->P, c->stream);      // hand-over counts and statistics: adjacent (ctx_create)
+        } else {                                                  // a block: the other particles' statistics may not have been collected yet
+            (void)hipMemsetAsync(prm.slow_n, 0, 32, s);
+            (void)hipMemsetAsync(c->d_stats + 4 * (size_t)first, 0, sizeof(uint64_t) * 4 * count, s);
+        }
         bool sequential = c->cfg.sequential_raycast == 1 || c->cfg.occupancy_policy == 1 ||
                           c->cfg.ray_rule == 1;      // the parallel kernels implement the frequency counters and the PF ray rule only
         // every hit is an order-sensitive visit (the list holds active_capacity of them) and the visit key carries the beam index
         // in 13 bits (act_key) and k_ray_patches keeps one 64-beam chunk per lane: scans with more than 4096 points go beam by beam
         if (!sequential && (n > 4096u || (uint64_t)n + 4096u > c->cfg.active_capacity)) sequential = true;
         // a uint16 `visited` counter that wraps INSIDE a scan makes the order of the visits matter (k_occ_max_visited)
-        if (!sequential && (uint64_t)c->visit_bound + n >= 65536u) {
+        if (!g && !sequential && (uint64_t)c->visit_bound + n >= 65536u) {      // (a group's update: step_can_group has looked, with the bound as it was before this scan)
             uint32_t m = 0;
             if (c->initialised) {
                 (void)hipMemsetAsync(c->d_scalar, 0, sizeof(uint32_t), c->stream);
@@ -976,13 +1115,15 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
             c->visit_bound = m;
             if ((uint64_t)m + n >= 65536u) { sequential = true; c->ctr.wrap_guard_scans += 1; }
         }
-        c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + n, 65535u);
-        if (sequential) c->ctr.sequential_raycast_scans += 1; else c->ctr.parallel_raycast_scans += 1;
+        if (!g) {                                                 // (a grouped step counts the scan once, for the pool)
+            c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + n, 65535u);
+            if (sequential) c->ctr.sequential_raycast_scans += 1; else c->ctr.parallel_raycast_scans += 1;
+        }
         // The patches an update needs are allocated BEFORE any cell is modified, so that running out of patches is recoverable
         // (grow + run again, recover_update).  The allocation walk uses the PF ray rule; LidarOdometry's rule / log-odds cells
         // (one-particle contexts) get a conservative pre-grown arena instead: every patch a scan of this reach can touch.
-        c->last_guarded = c->cfg.ray_rule == 0;
-        if (!c->last_guarded) {
+        if (!g) c->last_guarded = c->cfg.ray_rule == 0;
+        if (!g && !c->last_guarded) {
             const double side = 32.0 * c->cfg.resolution;
             const double rp = c->scan_reach / side + 2.5;
             const uint32_t bound = (uint32_t)std::min(32767.0, std::ceil(3.1416 * rp * rp));
@@ -999,7 +1140,7 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
             }
         }
         if (sequential) {
-            if (c->last_guarded) { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 1); if (ra) return ra; }
+            if (c->last_guarded) { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 1, c->stream, c->d_pts); if (ra) return ra; }
             hipLaunchKernelGGL(k_raycast, dim3(count), dim3(UM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, c->d_tfs, (int)first);
         } else {
             // patch-centric visits: a workgroup owns one occupancy patch of one particle, no global atomics on the counters
@@ -1028,7 +1169,7 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
             if (early_lane)
                 hipLaunchKernelGGL(k_early_list, dim3(1), dim3(256), 0, c->stream, prev_ok ? (const uint8_t*)c->d_heavy : (const uint8_t*)nullptr,
                                    (const uint32_t*)c->d_hlist, host_n, c->d_early, c->d_elist, c->d_slow_n + 4, (int)c->P, route_places(c, count));
-            { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 0); if (ra) return ra; }
+            { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 0, s, d_pts); if (ra) return ra; }
             // workgroups per particle = patches of a particle in flight at once.  A chip full of particles needs no more parallelism
             // inside one: 8 instead of 32 workgroups per particle (each then walks ~8 of its ~65 patches behind ONE prologue) took the
             // ray-cast of the 3000-particle pool from 1.31 to 1.24 ms (round 6); 4 and 16 are within noise of it, 64 is slower
@@ -1059,23 +1200,23 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_go, 0));
                 prm.early = c->d_early;                          // everybody else: the main lane skips them
             }
-            hipLaunchKernelGGL(k_ray_patches, dim3(xcd_grid(c, first, count), gy), dim3(256), 0, c->stream, prm, (const lama_dev::RayRec*)c->d_rrec,
+            hipLaunchKernelGGL(k_ray_patches, dim3(xcd_grid(c, first, count), gy), dim3(256), 0, s, prm, (const lama_dev::RayRec*)c->d_rrec,
                                (const uint64_t*)c->d_rbbox, (const lama_dev::RayChunk*)c->d_rchunk, (int)n, (int)first);
             const unsigned resume_grid = std::min<unsigned>(count, 256u);       // walks the (usually empty) hand-over list
             if (count <= 512) {
-                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(count), dim3(RP_BLOCK_LARGE), 0, c->stream, prm, (int)first);
-                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(resume_grid), dim3(RP_BLOCK_LARGE), 0, c->stream, prm, (int)first);
+                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(count), dim3(RP_BLOCK_LARGE), 0, s, prm, (int)first);
+                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(resume_grid), dim3(RP_BLOCK_LARGE), 0, s, prm, (int)first);
             } else {
-                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_SMALL>), dim3(count), dim3(RP_BLOCK_SMALL), 0, c->stream, prm, (int)first);
-                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_SMALL>), dim3(resume_grid), dim3(RP_BLOCK_SMALL), 0, c->stream, prm, (int)first);
+                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_SMALL>), dim3(count), dim3(RP_BLOCK_SMALL), 0, s, prm, (int)first);
+                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_SMALL>), dim3(resume_grid), dim3(RP_BLOCK_SMALL), 0, s, prm, (int)first);
             }
         }
         t.stop();
     }
     HIPCHK(c, hipGetLastError());
     {
-        Timer t(c, &c->ctr.ms_brushfire, &c->ctr.launches_brushfire);
-        if (c->cfg.brushfire_mode == 1)     // opt-in parallel variant; whatever it leaves (qsizes != 0) falls through to the exact stages
+        Timer t = g ? Timer(c, g, 2) : Timer(c, &c->ctr.ms_brushfire, &c->ctr.launches_brushfire);
+        if (c->cfg.brushfire_mode == 1 && !g)     // opt-in parallel variant; whatever it leaves (qsizes != 0) falls through to the exact stages
             hipLaunchKernelGGL(k_brushfire_canon, dim3(count), dim3(CN_BLOCK), 0, c->stream, prm, (int)first);
         // stage 1: small LDS window, every particle; stage 2: big window, resumes particles whose queue outgrew stage 1
         // (e.g. the first scan); stage 3: generic HBM-queue kernel for anything larger still
@@ -1104,16 +1245,16 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
                 HIPCHK(c, hipEventRecord(c->ev_heavy, c->stream2));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_heavy, 0));
             } else {
-                hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(count), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)first, 0);
+                hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(count), dim3(2 * UM_BLOCK), 0, s, prm, (int)first, 0);
             }
-            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(resume_grid), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)first, 0);
+            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(resume_grid), dim3(2 * UM_BLOCK), 0, s, prm, (int)first, 0);
         } else {
-            hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, false>), dim3(count), dim3(UM_BLOCK), 0, c->stream, prm, (int)first, 0);
-            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, false>), dim3(resume_grid), dim3(UM_BLOCK), 0, c->stream, prm, (int)first, 0);
+            hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, false>), dim3(count), dim3(UM_BLOCK), 0, s, prm, (int)first, 0);
+            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, false>), dim3(resume_grid), dim3(UM_BLOCK), 0, s, prm, (int)first, 0);
         }
         if (early_lane) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_early, 0));
-        hipLaunchKernelGGL(k_brushfire_slow, dim3(count), dim3(UM_BLOCK), 0, c->stream, prm, (int)first);
-        c->early_ok = route && first == 0 && count == c->P;      // d_heavy now holds this update's routed particles (early lane included)
+        hipLaunchKernelGGL(k_brushfire_slow, dim3(count), dim3(UM_BLOCK), 0, s, prm, (int)first);
+        if (!g) c->early_ok = route && first == 0 && count == c->P;      // d_heavy now holds this update's routed particles (early lane included)
         t.stop();
     }
     HIPCHK(c, hipGetLastError());
@@ -1212,6 +1353,202 @@ int32_t permute_particles(lama_hip_ctx* c, const int32_t* idx)
     resolve_timers(c);
     c->ctr.resample_clones += clones.size();
     c->ctr.resample_bytes += c->clone_bytes;
+    return LAMA_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grouped step schedule (lama_hip_pf_match_and_map).  A particle's map update is a function of its own pose, its own maps and the
+// scan, and its scan match reads its own distance map only: nothing but the host's resample decision couples the particles of a step.
+// So every group runs scan match -> (host: window, transforms) -> ray-cast -> brushfire on its own stream, nobody waits for a map
+// update, and the status of a group's update travels with the results of its NEXT scan match (k_pack_group: one copy per group).
+// All ordering is stream order, events and host decisions; no kernel waits for anything.
+// ------------------------------------------------------------------------------------------------
+int32_t apply_resample(lama_hip_ctx* c, const int32_t* idx)
+{
+    c->early_ok = false;                                            // particle indices change meaning
+    if (c->ll_valid) { std::vector<double> nl(c->P); for (uint32_t i = 0; i < c->P; ++i) nl[i] = c->h_ll[idx[i]]; c->h_ll.swap(nl); }
+    return permute_particles(c, idx);
+}
+
+bool step_can_group(const lama_hip_ctx* c, uint32_t n)
+{
+    // (the plain parallel update only: everything else -- beam-sequential ray-cast, the wrap-guard probe, LidarOdometry's ray rule, the
+    // opt-in parallel brushfire, routing -- runs as it always did, on the main stream, after the groups have drained)
+    return c->step_groups > 1 && c->P < c->route_min_count && c->cfg.brushfire_mode == 0 && c->cfg.sequential_raycast != 1 &&
+           c->cfg.occupancy_policy != 1 && c->cfg.ray_rule == 0 && n <= 4096u && (uint64_t)n + 4096u <= c->cfg.active_capacity &&
+           (uint64_t)c->visit_bound + n < 65536u;
+}
+
+// scan match of the group's block from the poses in c->h_poses, then its block (results + status of its previous map update) on the
+// way to g.h_pack; g.ev_match says when it has arrived.  status_only: no scan match (drain_groups)
+int32_t queue_group_match(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affine& mtf, bool status_only)
+{
+    const DevParams prm = group_params(c, g);
+    // (launch arguments are plain values: the owners are not copied)
+    hipStream_t s = g.s;
+    const double* const d_pts = g.d_pts;
+    const uint32_t* const d_words = g.d_words;
+    uint8_t* const d_pack = g.d_pack;
+    const int first = (int)g.first, count = (int)g.count;
+    if (!status_only) {
+        HIPCHK(c, hipMemcpyAsync(c->d_poses + 4 * (size_t)g.first, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count, hipMemcpyHostToDevice, s));
+        Timer t(c, &g, 0);
+        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_scan_match<true>, dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first);
+        else hipLaunchKernelGGL(k_scan_match<false>, dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first);
+        t.stop();
+    }
+    hipLaunchKernelGGL(k_pack_group, dim3(1), dim3(64), 0, s, prm, (const double*)c->d_loglik, (const int32_t*)c->d_iters, d_words, first, count, d_pack);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(g.h_pack.data(), d_pack, GroupPack(g.count).bytes, hipMemcpyDeviceToHost, g.s));
+    HIPCHK(c, hipEventRecord(g.ev_match, g.s));
+    return LAMA_HIP_OK;
+}
+
+// A cleanly aborted map update of one group (its allocation phase ran out of patches before any cell was modified): today's code on
+// the main stream, on an idle device, for the group's block -- grow, then the same update again from the poses and the scan it had.
+int32_t recover_group(lama_hip_ctx* c, StepGroup& g, int32_t e)
+{
+    int32_t rc = wait_for_groups(c);
+    if (rc) return rc;
+    const size_t o = 4 * (size_t)g.first, m = 4 * (size_t)g.count;
+    const std::vector<double> now(c->h_poses.data() + o, c->h_poses.data() + o + m);
+    std::memcpy(c->h_poses.data() + o, g.upd_poses.data(), sizeof(double) * m);
+    const PinVec<double>& scan = g.upd_slot ? c->h_pts2 : c->h_pts;
+    HIPCHK(c, c->d_pts.grow((size_t)3 * g.upd_n, (size_t)3 * 2048));
+    HIPCHK(c, hipMemcpyAsync(c->d_pts, scan.data(), sizeof(double) * 3 * g.upd_n, hipMemcpyHostToDevice, c->stream));
+    const double reach_now = c->scan_reach;
+    c->scan_reach = g.upd_reach; c->last_n = g.upd_n;
+    c->last_mtf = g.upd_mtf; c->last_first = g.first; c->last_count = g.count; c->last_guarded = true;
+    // what the repeat does on the host a second time (the scan's visits, launch counts and brackets, the longest chain) is taken back
+    const uint32_t vb = c->visit_bound;
+    const lama_hip_counters before = c->ctr;
+    c->saved_visit_bound = vb; c->saved_ctr = c->ctr;               // (recover_update rolls back to these: nothing to roll back here)
+    rc = recover_update(c, e);
+    c->visit_bound = vb;
+    c->ctr.parallel_raycast_scans = before.parallel_raycast_scans; c->ctr.sequential_raycast_scans = before.sequential_raycast_scans;
+    c->ctr.ms_raycast = before.ms_raycast; c->ctr.launches_raycast = before.launches_raycast;
+    c->ctr.ms_brushfire = before.ms_brushfire; c->ctr.launches_brushfire = before.launches_brushfire;
+    c->ctr.bf_longest_chain_sum = before.bf_longest_chain_sum; c->ctr.bf_longest_chain_last = before.bf_longest_chain_last;
+    if (rc == LAMA_HIP_OK) { for (uint32_t p = g.first; p < g.first + g.count; ++p) c->h_chain[p] = c->h_stats[4 * (size_t)p + 3]; c->chain_dirty = true; }
+    c->scan_reach = reach_now; c->last_n = 0;                       // (the main stream's scan buffer holds no scan a later call may reuse)
+    std::memcpy(c->h_poses.data() + o, now.data(), sizeof(double) * m);
+    return rc;
+}
+
+// The block of group g has arrived: the status of its previous map update (if one was queued) goes into the host mirrors and the
+// counters.  Returns the group's error word through `e`.
+void collect_group_status(lama_hip_ctx* c, StepGroup& g, int32_t& e)
+{
+    const GroupPack L(g.count);
+    const uint8_t* b = g.h_pack.data();
+    uint32_t w[16];
+    std::memcpy(w, b + L.words, sizeof(w));
+    e = (int32_t)w[0];
+    take_group_timers(c, g);
+    if (!g.maps_queued) return;
+    const uint32_t* sn = w + 2;
+    c->ctr.brushfire_handovers += sn[0]; c->ctr.replay_handovers += sn[1] + sn[3]; c->ctr.brushfire_routed += sn[2] + sn[4]; c->ctr.brushfire_early += sn[4];
+    c->h_guard.resize(c->P);
+    std::memcpy(&c->h_guard[g.first], b + L.guard, sizeof(uint32_t) * g.count);
+    std::memcpy(&c->h_counts[2 * (size_t)g.first], b + L.counts, sizeof(int32_t) * 2 * g.count);
+    if (e != 0) return;
+    const uint64_t* st = reinterpret_cast<const uint64_t*>(b + L.stats);
+    for (uint32_t i = 0; i < g.count; ++i) { c->ctr.ray_cells += st[4 * i + 2]; c->ctr.bf_cells += st[4 * i + 3]; c->h_chain[g.first + i] = st[4 * i + 3]; }
+    c->chain_dirty = true;
+}
+
+// a non-zero error word of group g (of its previous map update when one was queued, else of its scan match): what
+// check_device_errors does, for the group
+int32_t handle_group_error(lama_hip_ctx* c, StepGroup& g, int32_t e, bool of_maps)
+{
+    HIPCHK(c, hipMemsetAsync(g.d_words, 0, sizeof(int32_t), g.s));
+    if (of_maps && (e & ERR_CLEAN_ABORT) && (e & (ERR_DM_CAP | ERR_OCC_CAP)) && !(e & ERR_WINDOW)) {
+        const int32_t rr = recover_group(c, g, e);
+        if (rr != LAMA_HIP_E_CAPACITY) return rr;                   // done (or another error); E_CAPACITY: the arenas are at their limit
+    }
+    int32_t rc = wait_for_groups(c);
+    if (rc) return rc;
+    if (e & (ERR_DM_CAP | ERR_OCC_CAP)) { rc = clamp_counts(c, true); if (rc) return rc; }
+    return device_error_result(c, e);
+}
+
+void refresh_patch_totals(lama_hip_ctx* c)
+{
+    uint64_t dm = 0, oc = 0;
+    for (uint32_t p = 0; p < c->P; ++p) { dm += c->h_counts[2 * p]; oc += c->h_counts[2 * p + 1]; }
+    c->ctr.dm_patches = dm; c->ctr.occ_patches = oc;
+}
+
+// Collects the status of every group's queued map update (one more block per group, one wait per stream) and leaves the device idle:
+// called, through ENTER, at the start of every entry point but lama_hip_pf_match_and_map -- a deferred error surfaces there.
+int32_t drain_groups(lama_hip_ctx* c)
+{
+    if (!c->groups_busy) return LAMA_HIP_OK;
+    int32_t rc = LAMA_HIP_OK;
+    for (uint32_t k = 0; k < c->step_groups && rc == LAMA_HIP_OK; ++k)
+        if (c->grp[k].count && c->grp[k].maps_queued) rc = queue_group_match(c, c->grp[k], 0, Affine(), true);
+    const int32_t rw = wait_for_groups(c);
+    if (rc == LAMA_HIP_OK) rc = rw;
+    c->groups_busy = false;
+    if (rc) { for (StepGroup& g : c->grp) g.maps_queued = false; return rc; }
+    std::string first_msg;
+    for (uint32_t k = 0; k < c->step_groups; ++k) {
+        StepGroup& g = c->grp[k];
+        if (!g.count || !g.maps_queued) continue;
+        int32_t e = 0;
+        collect_group_status(c, g, e);
+        g.maps_queued = false;
+        if (e == 0) continue;
+        const int32_t re = handle_group_error(c, g, e, true);
+        if (re && rc == LAMA_HIP_OK) { rc = re; first_msg = c->error; }
+    }
+    for (uint32_t k = 0; k < c->step_groups; ++k) if (c->grp[k].count) (void)hipStreamSynchronize(c->grp[k].s);     // (error words cleared)
+    flush_step_figures(c);
+    refresh_patch_totals(c);
+    if (rc) { c->error = "deferred from the previous map update: " + first_msg; return rc; }
+    return grow_arenas(c, 0, c->P);
+}
+
+// one group of a grouped step, its block has arrived: status, results, window, map update
+int32_t finish_group_step(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affine& mtf, double* poses_out, double* loglik_out, int32_t* iters_out)
+{
+    const size_t o = 4 * (size_t)g.first, m = 4 * (size_t)g.count;
+    int32_t e = 0;
+    const bool had_maps = g.maps_queued;
+    collect_group_status(c, g, e);
+    g.maps_queued = false;
+    if (e != 0) {
+        int32_t rc = handle_group_error(c, g, e, had_maps);
+        if (rc) { if (had_maps) c->error = "deferred from the previous map update: " + c->error; return rc; }
+        // the update has been repeated: this step's scan match ran on the map as it was before -- once more, on the updated one
+        // (h_poses still holds the block's predicted poses)
+        rc = queue_group_match(c, g, n, mtf, false);
+        if (rc) return rc;
+        HIPCHK(c, hipStreamSynchronize(g.s));
+        collect_group_status(c, g, e);
+        if (e != 0) { HIPCHK(c, hipMemsetAsync(g.d_words, 0, sizeof(int32_t), g.s)); return device_error_result(c, e); }
+    } else if (had_maps) {
+        const int32_t rc = grow_arenas(c, g.first, g.count);         // head room for the next update (waits for the groups only when a region moves)
+        if (rc) return rc;
+    }
+    const GroupPack L(g.count);
+    const uint8_t* b = g.h_pack.data();
+    std::memcpy(c->h_poses.data() + o, b + L.poses, sizeof(double) * m);
+    std::memcpy(&c->h_ll[g.first], b + L.loglik, sizeof(double) * g.count);
+    if (poses_out) std::memcpy(poses_out + o, b + L.poses, sizeof(double) * m);
+    if (loglik_out) std::memcpy(loglik_out + g.first, b + L.loglik, sizeof(double) * g.count);
+    if (iters_out) std::memcpy(iters_out + g.first, b + L.iters, sizeof(int32_t) * g.count);
+    if (c->cfg.profile) {
+        const uint64_t* st = reinterpret_cast<const uint64_t*>(b + L.stats);
+        for (uint32_t i = 0; i < g.count; ++i) { c->ctr.gn_iterations += st[4 * i]; c->ctr.gn_evals += st[4 * i + 1]; }
+    }
+    int32_t rc = fit_window(c, mtf, g.first, g.count);              // (a move or a re-tiling waits for the groups first)
+    if (rc) return rc;
+    g.upd_poses.assign(c->h_poses.data() + o, c->h_poses.data() + o + m);
+    g.upd_mtf = mtf; g.upd_slot = c->scan_slot; g.upd_n = n; g.upd_reach = c->scan_reach;
+    rc = run_update_maps(c, n, mtf, g.first, g.count, &g);
+    if (rc) return rc;
+    g.maps_queued = true;
     return LAMA_HIP_OK;
 }
 
@@ -1357,6 +1694,46 @@ int32_t lama_hip_ctx_create(const lama_hip_cfg* cfg_in, lama_hip_ctx** out)
     if (c->d_elist.alloc(256) || hipMemset(c->d_elist, 0, 256 * 4)) return LAMA_HIP_E_HIP;
     if (c->d_hlist.alloc(256) || hipMemset(c->d_hlist, 0, 256 * 4)) return LAMA_HIP_E_HIP;
     if (hipStreamCreate(&c->stream2.h) || hipStreamCreate(&c->stream3.h)) return LAMA_HIP_E_HIP;
+    {
+        // Grouped step schedule (lama_hip_pf_match_and_map): a pool too small for routing and the early lane -- whose streams are
+        // therefore idle -- is split into contiguous blocks, each with a stream of its own, so that a block whose brushfire chains are
+        // short this step goes on with the next scan match while another block's longest chain still runs.
+        // THE RULE of these streams: nothing that one group's stream wrote, by kernel or by copy, is read on another group's stream.
+        // What all groups read and the host rewrites per step (the scan) is uploaded once per group, into the group's own buffer, on
+        // the group's stream; per-update scalars and lists (error word, hand-over counts and lists) exist once per group; arrays
+        // indexed by particle are touched by the owning group only.  Everything else (window, particle table, regions, resample,
+        // export / import, downloads) runs on the main stream after wait_for_groups / drain_groups, i.e. on an idle device.
+        uint32_t G = c->P < c->route_min_count ? DEFAULT_STEP_GROUPS : 1u;
+        if (const char* sg = std::getenv("LAMA_HIP_STEP_GROUPS")) {      // tests, measurements: 1 = the single-stream schedule
+            unsigned v = 0;
+            if (std::sscanf(sg, "%u", &v) == 1 && v >= 1) G = std::min<uint32_t>(v, MAX_STEP_GROUPS);
+        }
+        if (c->P >= c->route_min_count) G = 1;
+        c->step_groups = G;
+        if (G > 1) {
+            if (G > 3 && hipStreamCreate(&c->stream4.h)) return LAMA_HIP_E_HIP;      // (only an override asks for a fourth group)
+            const hipStream_t ss[MAX_STEP_GROUPS] = {c->stream, c->stream2, c->stream3, c->stream4};
+            // contiguous blocks of ceil(P / G) particles -- of the next multiple of 8 where that still makes G blocks (30 particles in
+            // 4 groups: 8, 8, 8, 6), so that a block's two-dimensional launches keep a particle on the XCD its one-dimensional ones
+            // put it on (xcd_grid)
+            uint32_t per = (uint32_t)((P + G - 1) / G);
+            const uint32_t per8 = (per + 7u) / 8u * 8u;
+            if ((P + per8 - 1) / per8 == G) per = per8;
+            for (uint32_t k = 0; k < G; ++k) {
+                StepGroup& g = c->grp[k];
+                g.s = ss[k];
+                g.first = (uint32_t)std::min<size_t>(P, (size_t)k * per); g.count = (uint32_t)std::min<size_t>(P, (size_t)(k + 1) * per) - g.first;
+                if (g.count == 0) continue;
+                const GroupPack L(g.count);
+                if (g.d_words.alloc(16) || hipMemset(g.d_words, 0, 64) || g.d_slow_list.alloc(4 * P) || hipMemset(g.d_slow_list, 0, 4 * P * 4) ||
+                    g.d_pack.alloc(L.bytes) || hipEventCreateWithFlags(&g.ev_match.h, hipEventDisableTiming))
+                    return LAMA_HIP_E_HIP;
+                g.h_pack.resize(L.bytes);
+                if (cfg.profile) for (Event& e : g.tev) if (hipEventCreate(&e.h)) return LAMA_HIP_E_HIP;
+            }
+            c->h_chain.assign(P, 0);
+        }
+    }
     if (hipEventCreateWithFlags(&c->ev_alloc.h, hipEventDisableTiming) || hipEventCreateWithFlags(&c->ev_early.h, hipEventDisableTiming) ||
         hipEventCreateWithFlags(&c->ev_go.h, hipEventDisableTiming) ||
         hipEventCreateWithFlags(&c->ev_route.h, hipEventDisableTiming) || hipEventCreateWithFlags(&c->ev_heavy.h, hipEventDisableTiming))
@@ -1438,8 +1815,8 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
     DevParams prm = make_params(c);
     {
         Timer t(c, &c->ctr.ms_scan_match, &c->ctr.launches_scan_match);
-        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_scan_match<true>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters);
-        else hipLaunchKernelGGL(k_scan_match<false>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters);
+        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_scan_match<true>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0);
+        else hipLaunchKernelGGL(k_scan_match<false>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0);
         t.stop();
     }
     HIPCHK(c, hipGetLastError());
@@ -1460,14 +1837,21 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
 int32_t lama_hip_pf_resample(lama_hip_ctx* c, const int32_t* sample_idx)
 {
     if (!c || !sample_idx) return LAMA_HIP_E_INVALID;
-    ENTER(c);
+    if (c->poisoned) return fail(c, LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue");
     if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_pf_resample before lama_hip_pf_init");
     for (uint32_t i = 0; i < c->P; ++i)
         if (sample_idx[i] < 0 || (uint32_t)sample_idx[i] >= c->P) return fail(c, LAMA_HIP_E_INVALID, "sample_idx out of range");
+    // The groups of a grouped step are still updating their maps: the copy waits for all of them, so it is made by the NEXT call on the
+    // context, whatever that is (finish_pending) -- until then the host is free, and a filter's prediction of the next step runs
+    // beside the map kernels as it does when no resample is due.  An error of the copy is then that call's ("deferred from ...").
+    if (c->groups_busy && !c->resample_deferred) {
+        c->deferred_idx.assign(sample_idx, sample_idx + c->P);
+        c->resample_deferred = true;
+        return LAMA_HIP_OK;
+    }
+    ENTER(c);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    c->early_ok = false;                                            // particle indices change meaning
-    if (c->ll_valid) { std::vector<double> nl(c->P); for (uint32_t i = 0; i < c->P; ++i) nl[i] = c->h_ll[sample_idx[i]]; c->h_ll.swap(nl); }
-    return permute_particles(c, sample_idx);
+    return apply_resample(c, sample_idx);
 }
 
 int32_t lama_hip_pf_update_maps_begin(lama_hip_ctx* c, const double* pts, uint32_t n, const double* origin3, const double* quat)
@@ -1499,6 +1883,109 @@ int32_t lama_hip_pf_update_maps(lama_hip_ctx* c, const double* pts, uint32_t n, 
     const int32_t rc = lama_hip_pf_update_maps_begin(c, pts, n, origin3, quat);
     if (rc) return rc;
     return lama_hip_sync(c);
+}
+
+int32_t lama_hip_pf_match_and_map(lama_hip_ctx* c, const double* pts, uint32_t n, const double* origin3, const double* quat,
+                                  const double* poses_in, double* poses_out, double* loglik_out, int32_t* iters_out)
+{
+    if (!c || !pts || !poses_in || n == 0) return LAMA_HIP_E_INVALID;
+    if (c->poisoned) return fail(c, LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue");
+    if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_pf_match_and_map before lama_hip_pf_init");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // A step that could not be grouped (below) has left its map update queued on the main stream: its status is collected here, and the
+    // schedule is chosen for THIS step alone -- one ungroupable scan (the wrap-guard probe is due every 65536 / n scans) must not
+    // keep the context on one stream.
+    if (c->pending_maps || c->resample_deferred) { const int32_t rp = finish_pending(c); if (rp) return rp; }
+    if (!step_can_group(c, n)) {
+        // the single-stream schedule (each of the three calls drains whatever the groups still hold)
+        int32_t rc = lama_hip_pf_set_poses(c, poses_in);
+        if (rc == LAMA_HIP_OK) rc = lama_hip_pf_scan_match(c, pts, n, origin3, quat, poses_out, loglik_out, iters_out);
+        if (rc == LAMA_HIP_OK) rc = lama_hip_pf_update_maps_begin(c, nullptr, n, origin3, quat);
+        if (rc == LAMA_HIP_OK) c->groups_ran = 1;
+        return rc;
+    }
+    // the scan: page-locked staging (two buffers by turns: the previous step's scan may be needed once more, recover_group), reach
+    c->scan_slot ^= 1u;
+    PinVec<double>& hp = c->scan_slot ? c->h_pts2 : c->h_pts;
+    hp.resize((size_t)3 * n);
+    std::memcpy(hp.data(), pts, sizeof(double) * 3 * n);
+    double r2 = 0.0;
+    for (uint32_t i = 0; i < n; ++i) r2 = std::max(r2, pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2]);
+    if (!std::isfinite(r2)) { c->scan_slot ^= 1u; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
+    c->scan_reach = std::sqrt(r2);
+    c->last_n = 0;                                                  // (the main stream's scan buffer is not this scan)
+    const Affine mtf = moving_tf(origin3, quat);
+    std::memcpy(c->h_poses.data(), poses_in, sizeof(double) * 4 * c->P);
+    c->h_ll.resize(c->P);
+    c->groups_busy = true;
+    c->early_ok = false;
+    uint32_t left = 0;
+    for (uint32_t k = 0; k < c->step_groups; ++k) {
+        StepGroup& g = c->grp[k];
+        if (!g.count) continue;
+        HIPCHK(c, g.d_pts.grow((size_t)3 * n, (size_t)3 * 2048));
+        HIPCHK(c, hipMemcpyAsync(g.d_pts, hp.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, g.s));
+        const int32_t rc = queue_group_match(c, g, n, mtf, false);
+        if (rc) return rc;
+        left |= 1u << k;
+    }
+    // the scan's visits count once for the pool (the wrap guard's bound), whichever group ray-casts first
+    c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + n, 65535u);
+    c->ctr.parallel_raycast_scans += 1;
+    c->last_guarded = true;
+    // the groups are taken as their blocks arrive, not in a fixed order: the one whose chains were short goes on first
+    while (left) {
+        for (uint32_t k = 0; k < c->step_groups; ++k) {
+            if (!(left & (1u << k))) continue;
+            StepGroup& g = c->grp[k];
+#ifndef LAMA_WAVE_SIM
+            const hipError_t q = hipEventQuery(g.ev_match);
+            if (q == hipErrorNotReady) continue;
+            if (q != hipSuccess) return hip_fail(c, q, "hipEventQuery");
+#endif
+            left &= ~(1u << k);
+            const int32_t rc = finish_group_step(c, g, n, mtf, poses_out, loglik_out, iters_out);
+            if (rc) {
+                // The step fails as a whole, once: the groups not taken yet hand in the status of the same update (their scan match
+                // results are dropped), so that the next call starts clean -- as it does after the single-stream schedule's one error.
+                const std::string msg = c->error;
+                (void)wait_for_groups(c);
+                for (uint32_t j = 0; j < c->step_groups; ++j) {
+                    if (!(left & (1u << j))) continue;
+                    StepGroup& o = c->grp[j];
+                    int32_t e = 0;
+                    const bool had_maps = o.maps_queued;
+                    collect_group_status(c, o, e);
+                    o.maps_queued = false;
+                    if (e != 0) (void)handle_group_error(c, o, e, had_maps);
+                }
+                flush_step_figures(c);
+                c->error = msg;
+                return rc;
+            }
+        }
+    }
+    c->ll_valid = true;
+    flush_step_figures(c);
+    refresh_patch_totals(c);
+    c->ctr.brushfire_mode = c->cfg.brushfire_mode;
+    c->groups_ran = 0;
+    for (uint32_t k = 0; k < c->step_groups; ++k) c->groups_ran += c->grp[k].count ? 1u : 0u;      // (more groups than particles: the empty ones did not run)
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_pf_step_groups(lama_hip_ctx* c, uint32_t* ran, uint32_t* configured)
+{
+    if (!c || (!ran && !configured)) return LAMA_HIP_E_INVALID;
+    if (configured) {                                               // (fixed at creation: no need to wait for anything)
+        uint32_t n = 0;
+        for (uint32_t k = 0; k < c->step_groups; ++k) n += c->grp[k].count ? 1u : 0u;
+        *configured = c->step_groups > 1 ? n : 0u;
+    }
+    if (!ran) return LAMA_HIP_OK;
+    ENTER(c);
+    *ran = c->groups_ran;
+    return LAMA_HIP_OK;
 }
 
 int32_t lama_hip_pf_map_patches(lama_hip_ctx* c, uint32_t particle, int32_t kind, uint32_t* num)
@@ -2293,6 +2780,7 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
     hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(1), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)particle, 0);
     hipLaunchKernelGGL(k_brushfire_slow, dim3(1), dim3(UM_BLOCK), 0, c->stream, prm, (int)particle);
     HIPCHK(c, hipGetLastError());
+    c->last_first = 0; c->last_count = c->P;                        // (whose statistics check_device_errors reads)
     return check_device_errors(c, true, false);
 }
 

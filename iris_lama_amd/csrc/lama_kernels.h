@@ -404,10 +404,10 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
 // +50 % at 3000 particles -- for 2 us at 30.)
 template <bool BIGSQ>
 __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) void k_scan_match(DevParams prm, const double* __restrict__ pts, int n, Affine mtf,
-                                                          double* __restrict__ loglik_out, int32_t* __restrict__ iters_out)
+                                                          double* __restrict__ loglik_out, int32_t* __restrict__ iters_out, int first_particle)
 {
     __shared__ SMShared sh;
-    const int p = blockIdx.x;
+    const int p = first_particle + blockIdx.x;
     const PV pv_ = pview_w(prm, p);
     const int16_t* dir = pv_.dm_dir;
     const sv_t* sv = pv_.dm_sv;
@@ -443,6 +443,31 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
         prm.stats[4 * p + 0] = iter;
         prm.stats[4 * p + 1] = evals;
     }
+}
+
+// k_pack_group: what the host wants back from the particles [first, first + count) after their scan match -- matched poses,
+// log-likelihoods, iteration counts -- together with the status their previous map update left behind (statistics, guard bounds,
+// patch counts, the group's error word and hand-over counts: `words`), gathered into ONE block so that a particle group of the
+// grouped step schedule (lama_hip_pf_match_and_map) costs a single device-to-host copy.  Layout: GroupPack in lama_hip.hip.
+__global__ __launch_bounds__(64) void k_pack_group(DevParams prm, const double* __restrict__ loglik, const int32_t* __restrict__ iters,
+                                                    const uint32_t* __restrict__ words, int first_particle, int count, uint8_t* __restrict__ out)
+{
+    double* o_pose = reinterpret_cast<double*>(out);
+    double* o_ll = o_pose + 4 * (size_t)count;
+    uint64_t* o_st = reinterpret_cast<uint64_t*>(o_ll + count);
+    uint32_t* o_guard = reinterpret_cast<uint32_t*>(o_st + 4 * (size_t)count);
+    int32_t* o_cnt = reinterpret_cast<int32_t*>(o_guard + count);
+    int32_t* o_it = o_cnt + 2 * (size_t)count;
+    uint32_t* o_w = reinterpret_cast<uint32_t*>(o_it + count);
+    for (int i = threadIdx.x; i < count; i += 64) {
+        const int p = first_particle + i;
+        for (int k = 0; k < 4; ++k) { o_pose[4 * i + k] = prm.poses[4 * p + k]; o_st[4 * i + k] = prm.stats[4 * p + k]; }
+        o_ll[i] = loglik[p];
+        o_guard[i] = prm.guard[p];
+        o_cnt[2 * i] = prm.counts[2 * p]; o_cnt[2 * i + 1] = prm.counts[2 * p + 1];
+        o_it[i] = iters[p];
+    }
+    if (threadIdx.x < 16) o_w[threadIdx.x] = words[threadIdx.x];
 }
 
 // MatchSurface2D::eval (src/match_surface_2d.cpp:42-90) as the reference's Problem interface exposes it: the UNWEIGHTED

@@ -82,6 +82,7 @@ def _hip_signatures():
         {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
         {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
         {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
+        {"lama_hip_pf_match_and_map": [vp, vp, u32, vp, vp, vp, vp, vp, vp], "lama_hip_pf_step_groups": [vp, vp, vp]},   # whole device step
         {"lama_hip_pgo_create": [i32, u32, vp, vp, vp, vp, u32, vp], "lama_hip_pgo_destroy": [vp], "lama_hip_pgo_last_error": [vp],
          "lama_hip_pgo_linearize": [vp, vp, vp, vp, vp, vp, vp, vp], "lama_hip_pgo_pattern": [vp, vp, vp, vp], "lama_hip_pgo_set_poses": [vp, vp],
          "lama_hip_pgo_get_poses": [vp, vp], "lama_hip_pgo_linearize_system": [vp, vp, vp, vp, vp, vp], "lama_hip_pgo_try_step": [vp, vp, vp, vp],
@@ -324,6 +325,30 @@ class HipContext(_Handle):
         pts, origin, quat = self._scan(pts, origin, quat)
         self._chk(self.L.lama_hip_pf_update_maps(self.h, _p(pts), len(pts), _p(origin), _p(quat)))
 
+    def match_and_map(self, pts, poses, origin=None, quat=None):
+        """One whole device step: scan match from `poses`, then the map update of the matched poses, queued (its status is collected
+        by the next call on the context).  Pools below 64 particles run it as particle groups on streams of their own."""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        poses = np.ascontiguousarray(poses, dtype=np.float64)
+        assert poses.shape == (self.P, 4)
+        out = np.zeros((self.P, 4))
+        ll = np.zeros(self.P)
+        it = np.zeros(self.P, dtype=np.int32)
+        self._chk(self.L.lama_hip_pf_match_and_map(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(poses), _p(out), _p(ll), _p(it)))
+        return out, ll, it
+
+    def step_groups(self):
+        """Particle groups the last match_and_map ran (1: the single-stream schedule; 0: none yet).  Waits for the device."""
+        n = C.c_uint32(0)
+        self._chk(self.L.lama_hip_pf_step_groups(self.h, C.byref(n), None))
+        return int(n.value)
+
+    def configured_step_groups(self):
+        """Groups a step of this context is split into when it can be (0: never, the single-stream schedule).  Waits for nothing."""
+        n = C.c_uint32(0)
+        self._chk(self.L.lama_hip_pf_step_groups(self.h, None, C.byref(n)))
+        return int(n.value)
+
     def download_map(self, particle, kind):
         """{reference patch id: (cells[1024] in the reference record format, mask[16])}"""
         n = C.c_uint32(0)
@@ -558,7 +583,10 @@ class HipContext(_Handle):
     def counters(self):
         c = HipCounters()
         self._chk(self.L.lama_hip_get_counters(self.h, C.byref(c)))
-        return c.as_dict()
+        d = c.as_dict()
+        if hasattr(self.L, "lama_hip_pf_step_groups"):        # (its own getter: the struct's tail is pinned by a consumer check)
+            d["step_groups"] = self.step_groups()
+        return d
 
     def reset_counters(self):
         self._chk(self.L.lama_hip_reset_counters(self.h))

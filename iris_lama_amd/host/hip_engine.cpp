@@ -99,6 +99,8 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     e->map_occupied_cells = reinterpret_cast<decltype(e->map_occupied_cells)>(dlsym(dl, "lama_hip_map_occupied_cells"));
     e->match_solve_batch = reinterpret_cast<decltype(e->match_solve_batch)>(dlsym(dl, "lama_hip_match_solve_batch"));
     e->match_search_lattice = reinterpret_cast<decltype(e->match_search_lattice)>(dlsym(dl, "lama_hip_match_search_lattice"));
+    e->pf_match_and_map = reinterpret_cast<decltype(e->pf_match_and_map)>(dlsym(dl, "lama_hip_pf_match_and_map"));
+    e->pf_step_groups = reinterpret_cast<decltype(e->pf_step_groups)>(dlsym(dl, "lama_hip_pf_step_groups"));
     return e;
 }
 

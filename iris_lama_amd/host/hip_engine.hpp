@@ -57,6 +57,10 @@ struct HipEngine {
     decltype(&lama_hip_match_solve_batch) match_solve_batch = nullptr;
     // pose-lattice search (lama::CorrelativeSearch2D, Loc2D::relocalize); optional in the same way
     decltype(&lama_hip_match_search_lattice) match_search_lattice = nullptr;
+    // a whole device step with the map update in front of the resample (PFSlam2D::update on one shard); optional: without it the
+    // step runs scan match -> resample -> map update through the calls above
+    decltype(&lama_hip_pf_match_and_map) pf_match_and_map = nullptr;
+    decltype(&lama_hip_pf_step_groups) pf_step_groups = nullptr;
     ~HipEngine();
 };
 

@@ -445,6 +445,11 @@ void PFSlam2D::uploadLocalPoses()
 
 PFSlam2D::Phase PFSlam2D::updateBegin(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, double timestamp)
 {
+    return beginStep(surface, odometry, timestamp, false);
+}
+
+PFSlam2D::Phase PFSlam2D::beginStep(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, double timestamp, bool whole_step)
+{
     if (group_) throw std::runtime_error("lama::PFSlam2D: the step-wise API belongs to single shards; an object with Options::gpus > 1 runs the whole step in update()");
     if (!surface || surface->points.empty()) throw std::runtime_error("lama::PFSlam2D::update: empty scan");
     t_begin_ = now_s();
@@ -492,10 +497,18 @@ PFSlam2D::Phase PFSlam2D::updateBegin(const PointCloudXYZ::Ptr& surface, const P
 
     // 2. scan matching of the local shard on the device                    :252-266, :416-437
     const double t0 = now_s();
-    uploadLocalPoses();
     std::vector<double> poses((size_t)(hi_ - lo_) * 4);
-    dev_.check(dev_->pf_scan_match(dev_.get(), pts_.data(), n, origin_, quat_, poses.data(), local_loglik_.data(), nullptr), "lama_hip_pf_scan_match");
-    scan_resident_ = true;
+    if (whole_step) {
+        // scan match AND the map update of the matched poses, queued (region 2 in front of the resample: see update())
+        std::vector<double> predicted(poses.size());
+        for (uint32_t i = lo_; i < hi_; ++i) particles_[i].pose.state.toArray(&predicted[4 * (size_t)(i - lo_)]);
+        dev_.check(dev_->pf_match_and_map(dev_.get(), pts_.data(), n, origin_, quat_, predicted.data(), poses.data(), local_loglik_.data(), nullptr),
+                   "lama_hip_pf_match_and_map");
+    } else {
+        uploadLocalPoses();
+        dev_.check(dev_->pf_scan_match(dev_.get(), pts_.data(), n, origin_, quat_, poses.data(), local_loglik_.data(), nullptr), "lama_hip_pf_scan_match");
+        scan_resident_ = true;
+    }
     for (uint32_t i = lo_; i < hi_; ++i) {
         particles_[i].pose.state = SE2d::fromArray(&poses[4 * (size_t)(i - lo_)]);
         if (options_.shard_world == 1) particles_[i].poses.push_back(particles_[i].pose);
@@ -571,12 +584,29 @@ bool PFSlam2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry,
     if (group_) return updateGroup(surface, odometry, timestamp);
     if (options_.shard_world != 1)
         throw std::runtime_error("lama::PFSlam2D::update: with shard_world > 1 drive the step-wise API (all-gather needed)");
-    const Phase ph = updateBegin(surface, odometry, timestamp);
+    // One shard, no Summary, an engine with the whole-step entry point: predict -> device step (scan match, then the map update of
+    // the matched poses, queued) -> resample if due.  The reference resamples BEFORE the map update (src/pf_slam2d.cpp:280-302); the
+    // swap is exact: a resample makes new particle i a copy of old particle idx[i] -- pose and both maps -- and touches nothing
+    // else, and a particle's map update is a function of its own pose, its own maps and the scan, so "copy, then update every copy"
+    // and "update, then copy the updated maps" leave the same poses and the same maps bit for bit; weights, Neff and the resample's
+    // random draw are host bookkeeping that does not see the maps.  What it buys: the device needs no pool-wide decision between a
+    // particle's scan match and its map update, so particle groups run ahead of each other (include/lama_hip.h).
+    // The Summary's buckets time the reference's order, the step-wise API is the caller's order: both keep it.
+    // ... and so does every pool that the device does not split (64 particles and more): there the swap would buy nothing and cost a
+    // resampling step the overlap of the map update with the copy and the next predict.
+    if (whole_step_ < 0) {
+        uint32_t groups = 0;
+        const auto& e = dev_.engine();
+        if (e->pf_match_and_map && e->pf_step_groups) dev_.check(e->pf_step_groups(dev_.get(), nullptr, &groups), "lama_hip_pf_step_groups");
+        whole_step_ = groups > 0 ? 1 : 0;
+    }
+    const bool whole_step = !summary && whole_step_ == 1;
+    const Phase ph = beginStep(surface, odometry, timestamp, whole_step);
     if (ph == kNoUpdate) return false;
     if (ph == kFirstScan) return true;
     std::vector<int32_t> idx;
     if (planResample(local_loglik_.data(), idx)) applyResample(idx);
-    updateMaps();
+    if (!whole_step) updateMaps();
     return true;
 }
 
