@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstddef>
+#include <type_traits>
 
 // Two instantiations of the library (iris_lama_amd/Makefile): the default one, and -- compiled with -DLAMA_WIDE_DM into
 // liblama_hip_wide.so -- the one for a distance map whose l2_max lies beyond 127 cells, up to the 255 cells that the reference's own
@@ -143,6 +144,16 @@ struct DevParams {
     uint32_t strategy;     // 0 = GaussNewton, 1 = LevenbergMarquard (cfg.solver_strategy; Slam2D / Loc2D "lm")
     double lo_miss, lo_hit, lo_min, lo_max;   // ProbabilisticOccupancyMap parameters (float-rounded, as the reference stores them)
 };
+
+// A block of at most ARG_BLOCK particles (a group of the grouped step schedule) brings the small tables the host rewrites before every
+// launch -- its predicted poses, its scan transforms -- along as launch arguments, entry b = workgroup b of the block's launch,
+// instead of copying them into d_poses / d_tfs first: one operation less on the stream per table, and a kernel argument cannot be
+// stale in any cache.
+constexpr int ARG_BLOCK = 16;
+struct PoseTable { double v[4 * ARG_BLOCK]; };               // [b]: c, s, tx, ty
+struct TfTable { double v[12 * ARG_BLOCK]; };                // [b]: R row-major | t (host_scan_tf)
+// every other launch of those kernels reads d_poses / d_tfs and carries this instead: no argument bytes, the code it ran before
+struct NoTable {};
 
 // Particle p's view of the maps: its directories, its regions of the pooled planes (slot-relative addressing inside), capacities.
 struct PV {

@@ -1040,8 +1040,11 @@ static unsigned xcd_grid(const lama_hip_ctx* c, uint32_t first, uint32_t count)
 
 // allocation phase of a map update (ray records, hit cells' patches, the patches the rays cross, the bound on the distance-map patches
 // still to come): afterwards either every patch the update needs exists or an error bit is set and no map cell has been modified
-int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only, hipStream_t s, const double* d_pts)
+int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only, hipStream_t s, const double* d_pts,
+                                const lama_dev::TfTable* tab = nullptr)
 {
+    // tab: the block's scan transforms travel with the launches (at most ARG_BLOCK particles), d_tfs is not read
+    const double* const d_tfs = tab ? nullptr : (const double*)c->d_tfs;
     const size_t need = (size_t)c->P * n;
     if (need > c->d_rrec.n) {                                       // all three are freed before any is allocated
         c->d_rrec.reset(); c->d_rbbox.reset(); c->d_rchunk.reset();
@@ -1050,15 +1053,27 @@ int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t 
         if (e == hipSuccess) e = c->d_rchunk.alloc((size_t)c->P * ((n + 63) / 64));     // per 64 beams of a particle
         if (e != hipSuccess) { c->d_rrec.reset(); return hip_fail(c, e, "ray buffers"); }
     }
-    hipLaunchKernelGGL(k_ray_hits, dim3(xcd_grid(c, first, count), (n + 255) / 256), dim3(256), 0, s, prm, d_pts, (int)n, c->d_tfs, (int)first,
-                       c->d_rrec, c->d_rbbox, alloc_only, c->d_rchunk);
+    const dim3 hits_grid(xcd_grid(c, first, count), (n + 255) / 256);
+    if (tab) hipLaunchKernelGGL(k_ray_hits<lama_dev::TfTable>, hits_grid, dim3(256), 0, s, prm, d_pts, (int)n, d_tfs, (int)first,
+                                (lama_dev::RayRec*)c->d_rrec, (uint64_t*)c->d_rbbox, alloc_only, (lama_dev::RayChunk*)c->d_rchunk, *tab);
+    else hipLaunchKernelGGL(k_ray_hits<lama_dev::NoTable>, hits_grid, dim3(256), 0, s, prm, d_pts, (int)n, d_tfs, (int)first,
+                            (lama_dev::RayRec*)c->d_rrec, (uint64_t*)c->d_rbbox, alloc_only, (lama_dev::RayChunk*)c->d_rchunk, lama_dev::NoTable());
     const int rw_seg = count <= 64 ? 4 : 1;
     hipLaunchKernelGGL(k_ray_alloc_walk, dim3(xcd_grid(c, first, count), (n * rw_seg + 255) / 256), dim3(256), 0, s, prm, (const lama_dev::RayRec*)c->d_rrec, (int)n, (int)first, rw_seg);
     double far = c->scan_reach;                                   // no cell further than truncated_range from the sensor is touched
     if (c->cfg.truncated_range > 0.0) far = std::min(far, c->cfg.truncated_range);
     const int reach_cells = (int)std::ceil(far * c->scale) + 2;
-    hipLaunchKernelGGL(k_occ_reverse_dir, dim3(count), dim3(256), 0, s, prm, (int)first, (const double*)c->d_tfs, reach_cells,
-                       c->unguarded_retry ? 1 : 0);
+    // the directory rows that can hold a patch at all: the mapped box (ensure_window; what permute_particles copies)
+    uint32_t row0 = 0, row1 = c->W - 1;
+    if (c->mb_valid) {
+        const int64_t oy = c->wy0 >> 5, W = c->W;
+        const int64_t lo = std::min(std::max(c->mby0 - oy, (int64_t)0), W - 1), hi = std::min(std::max(c->mby1 - oy, (int64_t)0), W - 1);
+        if (hi >= lo) { row0 = (uint32_t)lo; row1 = (uint32_t)hi; }
+    }
+    if (tab) hipLaunchKernelGGL(k_occ_reverse_dir<lama_dev::TfTable>, dim3(count), dim3(256), 0, s, prm, (int)first, d_tfs, reach_cells,
+                                c->unguarded_retry ? 1 : 0, row0, row1, *tab);
+    else hipLaunchKernelGGL(k_occ_reverse_dir<lama_dev::NoTable>, dim3(count), dim3(256), 0, s, prm, (int)first, d_tfs, reach_cells,
+                            c->unguarded_retry ? 1 : 0, row0, row1, lama_dev::NoTable());
     return LAMA_HIP_OK;
 }
 
@@ -1086,15 +1101,21 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
     PinVec<double>& tfs = c->h_tfs;
     tfs.resize((size_t)c->P * 12);
     for (uint32_t p = first; p < first + count; ++p) host_scan_tf(&c->h_poses[4 * p], mtf, &tfs[12 * (size_t)p]);
-    HIPCHK(c, hipMemcpyAsync(c->d_tfs + 12 * (size_t)first, &tfs[12 * (size_t)first], sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
+    // a group's block of at most ARG_BLOCK particles: the transforms are launch arguments of the two kernels that read them
+    const bool tf_by_value = g && count <= (uint32_t)lama_dev::ARG_BLOCK;
+    lama_dev::TfTable tf_tab = lama_dev::TfTable();
+    if (tf_by_value) std::memcpy(tf_tab.v, &tfs[12 * (size_t)first], sizeof(double) * 12 * count);
+    else HIPCHK(c, hipMemcpyAsync(c->d_tfs + 12 * (size_t)first, &tfs[12 * (size_t)first], sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
     DevParams prm = g ? group_params(c, *g) : make_params(c);
     bool early_lane = false;
     {
         Timer t = g ? Timer(c, g, 1) : Timer(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
         // both ray-casts are bit-exact; the parallel one wins while the chip is not yet full of particles
+        // (hand-over counts and statistics: a group's update follows the k_pack_group of its step -- finish_group_step is the only caller
+        // with a group --, which has cleared both behind what it packed)
         if (first == 0 && count == c->P && !g) {
             (void)hipMemsetAsync(c->d_slow_n, 0, 32 + sizeof(uint64_t) * 4 * c->P, c->stream);      // hand-over counts and statistics: adjacent (ctx_create)
-        } else {                                                  // a block: the other particles' statistics may not have been collected yet
+        } else if (!g) {                                          // a block: the other particles' statistics may not have been collected yet
             (void)hipMemsetAsync(prm.slow_n, 0, 32, s);
             (void)hipMemsetAsync(c->d_stats + 4 * (size_t)first, 0, sizeof(uint64_t) * 4 * count, s);
         }
@@ -1169,7 +1190,7 @@ int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t
             if (early_lane)
                 hipLaunchKernelGGL(k_early_list, dim3(1), dim3(256), 0, c->stream, prev_ok ? (const uint8_t*)c->d_heavy : (const uint8_t*)nullptr,
                                    (const uint32_t*)c->d_hlist, host_n, c->d_early, c->d_elist, c->d_slow_n + 4, (int)c->P, route_places(c, count));
-            { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 0, s, d_pts); if (ra) return ra; }
+            { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 0, s, d_pts, tf_by_value ? &tf_tab : nullptr); if (ra) return ra; }
             // workgroups per particle = patches of a particle in flight at once.  A chip full of particles needs no more parallelism
             // inside one: 8 instead of 32 workgroups per particle (each then walks ~8 of its ~65 patches behind ONE prologue) took the
             // ray-cast of the 3000-particle pool from 1.31 to 1.24 ms (round 6); 4 and 16 are within noise of it, 64 is slower
@@ -1387,17 +1408,29 @@ int32_t queue_group_match(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affin
     // (launch arguments are plain values: the owners are not copied)
     hipStream_t s = g.s;
     const double* const d_pts = g.d_pts;
-    const uint32_t* const d_words = g.d_words;
+    uint32_t* const d_words = g.d_words;
     uint8_t* const d_pack = g.d_pack;
     const int first = (int)g.first, count = (int)g.count;
+    // The step path: the predicted poses of a block of at most ARG_BLOCK particles are launch arguments -- no upload of the poses --, and
+    // k_pack_group clears what it has packed -- no fills in front of the ray-cast (run_update_maps).
     if (!status_only) {
-        HIPCHK(c, hipMemcpyAsync(c->d_poses + 4 * (size_t)g.first, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count, hipMemcpyHostToDevice, s));
+        const bool by_value = g.count <= (uint32_t)lama_dev::ARG_BLOCK;
+        lama_dev::PoseTable ptab = lama_dev::PoseTable();
+        if (by_value) std::memcpy(ptab.v, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count);
+        else HIPCHK(c, hipMemcpyAsync(c->d_poses + 4 * (size_t)g.first, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count, hipMemcpyHostToDevice, s));
+        const bool big = c->max_sqdist > (uint32_t)SM_LUT;
+        const lama_dev::NoTable none;
         Timer t(c, &g, 0);
-        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_scan_match<true>, dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first);
-        else hipLaunchKernelGGL(k_scan_match<false>, dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first);
+        if (by_value) {
+            if (big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, ptab);
+            else hipLaunchKernelGGL((k_scan_match<false, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, ptab);
+        } else {
+            if (big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, none);
+            else hipLaunchKernelGGL((k_scan_match<false, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, none);
+        }
         t.stop();
     }
-    hipLaunchKernelGGL(k_pack_group, dim3(1), dim3(64), 0, s, prm, (const double*)c->d_loglik, (const int32_t*)c->d_iters, d_words, first, count, d_pack);
+    hipLaunchKernelGGL(k_pack_group, dim3(1), dim3(64), 0, s, prm, (const double*)c->d_loglik, (const int32_t*)c->d_iters, d_words, first, count, d_pack, status_only ? 0 : 1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(g.h_pack.data(), d_pack, GroupPack(g.count).bytes, hipMemcpyDeviceToHost, g.s));
     HIPCHK(c, hipEventRecord(g.ev_match, g.s));
@@ -1813,10 +1846,11 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
     if (rc) return rc;
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
+    const lama_dev::NoTable none;                                   // (the poses are in d_poses)
     {
         Timer t(c, &c->ctr.ms_scan_match, &c->ctr.launches_scan_match);
-        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL(k_scan_match<true>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0);
-        else hipLaunchKernelGGL(k_scan_match<false>, dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0);
+        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL((k_scan_match<true, lama_dev::NoTable>), dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0, none);
+        else hipLaunchKernelGGL((k_scan_match<false, lama_dev::NoTable>), dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0, none);
         t.stop();
     }
     HIPCHK(c, hipGetLastError());

@@ -402,9 +402,11 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
 // ------------------------------------------------------------------------------------------------
 // (128 VGPRs: four waves per SIMD.  Left alone the allocator takes 136 since the single-lane step calls sincos -- three waves per SIMD,
 // +50 % at 3000 particles -- for 2 us at 30.)
-template <bool BIGSQ>
+// PT = PoseTable: the predicted poses of a block of at most ARG_BLOCK particles came with the launch; NoTable: they are in prm.poses
+template <bool BIGSQ, class PT>
 __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) void k_scan_match(DevParams prm, const double* __restrict__ pts, int n, Affine mtf,
-                                                          double* __restrict__ loglik_out, int32_t* __restrict__ iters_out, int first_particle)
+                                                          double* __restrict__ loglik_out, int32_t* __restrict__ iters_out, int first_particle,
+                                                          PT ptab)
 {
     __shared__ SMShared sh;
     const int p = first_particle + blockIdx.x;
@@ -412,7 +414,10 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
     const int16_t* dir = pv_.dm_dir;
     const sv_t* sv = pv_.dm_sv;
     if (threadIdx.x == 0) {
-        sh.state = load_pose(prm.poses + 4 * p);
+        if constexpr (std::is_same<PT, PoseTable>::value) {
+            const int b = (int)blockIdx.x & (ARG_BLOCK - 1);
+            sh.state = SE2{ptab.v[4 * b], ptab.v[4 * b + 1], ptab.v[4 * b + 2], ptab.v[4 * b + 3]};
+        } else sh.state = load_pose(prm.poses + 4 * p);
         sh.tf = scan_tf(sh.state, mtf);
         sh.ctl[0] = 0; sh.ctl[1] = 0;
     }
@@ -450,7 +455,7 @@ __global__ __launch_bounds__(SM_BLOCK) __attribute__((amdgpu_num_vgpr(128))) voi
 // patch counts, the group's error word and hand-over counts: `words`), gathered into ONE block so that a particle group of the
 // grouped step schedule (lama_hip_pf_match_and_map) costs a single device-to-host copy.  Layout: GroupPack in lama_hip.hip.
 __global__ __launch_bounds__(64) void k_pack_group(DevParams prm, const double* __restrict__ loglik, const int32_t* __restrict__ iters,
-                                                    const uint32_t* __restrict__ words, int first_particle, int count, uint8_t* __restrict__ out)
+                                                    uint32_t* __restrict__ words, int first_particle, int count, uint8_t* __restrict__ out, int clear)
 {
     double* o_pose = reinterpret_cast<double*>(out);
     double* o_ll = o_pose + 4 * (size_t)count;
@@ -466,8 +471,13 @@ __global__ __launch_bounds__(64) void k_pack_group(DevParams prm, const double* 
         o_guard[i] = prm.guard[p];
         o_cnt[2 * i] = prm.counts[2 * p]; o_cnt[2 * i + 1] = prm.counts[2 * p + 1];
         o_it[i] = iters[p];
+        if (clear) for (int k = 0; k < 4; ++k) prm.stats[4 * p + k] = 0;
     }
     if (threadIdx.x < 16) o_w[threadIdx.x] = words[threadIdx.x];
+    // clear (the step path of a group): what has just been packed -- the statistics above,
+    // the hand-over counts here, each by the lane that read it -- is cleared for the update that follows on this stream, instead of
+    // by two fills in front of its ray-cast; stream order keeps the update's readers in front of this kernel and its writers behind
+    if (clear && threadIdx.x >= 2 && threadIdx.x < 10) words[threadIdx.x] = 0;
 }
 
 // MatchSurface2D::eval (src/match_surface_2d.cpp:42-90) as the reference's Problem interface exposes it: the UNWEIGHTED

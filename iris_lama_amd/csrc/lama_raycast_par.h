@@ -181,10 +181,12 @@ __device__ inline void ray_chunk_record(const DevParams& prm, const BeamGeom& g,
 
 // alloc_only: the beam-sequential ray-cast (k_raycast) follows -- only the allocation phase is wanted here (ray records for the
 // allocation walk, the hit cells' patches); no hit bits, no active-visit list.
+// TAB = TfTable: the scan transforms of a block of at most ARG_BLOCK particles came with the launch; NoTable: they are in `tfs`
+template <class TAB>
 __global__ __launch_bounds__(256) void k_ray_hits(DevParams prm, const double* __restrict__ pts, int n,
                                                    const double* __restrict__ tfs, int first_particle,
                                                    RayRec* __restrict__ rec_out = nullptr, uint64_t* __restrict__ bbox_out = nullptr, int alloc_only = 0,
-                                                   RayChunk* __restrict__ chunk_out = nullptr)
+                                                   RayChunk* __restrict__ chunk_out = nullptr, TAB tab = TAB())
 {
     const int p = first_particle + blockIdx.x;
     if (p >= (int)prm.P) return;                    // (the particle dimension of the grid is rounded up to a multiple of 8: xcd_grid)
@@ -193,7 +195,11 @@ __global__ __launch_bounds__(256) void k_ray_hits(DevParams prm, const double* _
     const bool live = i < n;
     const int ic = live ? i : n - 1;
     double T[12];
-    uload_f64_w<12>(tfs + 12 * (size_t)p, T);                 // (rewritten by the host before every update: coherent uniform loads, lama_dev.h)
+    if constexpr (std::is_same<TAB, TfTable>::value) {
+        const int b = (int)blockIdx.x & (ARG_BLOCK - 1);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T[k] = tab.v[12 * b + k];
+    } else uload_f64_w<12>(tfs + 12 * (size_t)p, T);          // (rewritten by the host before every update: coherent uniform loads, lama_dev.h)
     const BeamGeom g = beam_geometry(prm, T, pts[3 * ic], pts[3 * ic + 1], pts[3 * ic + 2]);
     uint64_t bb = RAY_BBOX_EMPTY;
     if (rec_out && live) bb = ray_hits_record(prm, g, p, i, n, rec_out, bbox_out);

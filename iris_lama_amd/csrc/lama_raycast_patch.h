@@ -198,19 +198,25 @@ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 constexpr int RD_MARK_SIDE = 256;                            // the marked region (scan box grown by guard_r) is at most this many patches wide
 constexpr int RD_MARK_WORDS = RD_MARK_SIDE * RD_MARK_SIDE / 32;
 
+template <class TAB>
 __global__ __launch_bounds__(256) void k_occ_reverse_dir(DevParams prm, int first_particle,
-                                                          const double* __restrict__ tfs /*[P][12]*/, int reach_cells, int guard_off)
+                                                          const double* __restrict__ tfs /*[P][12]*/, int reach_cells, int guard_off,
+                                                          uint32_t row0, uint32_t row1, TAB tab)
 {
     __shared__ uint32_t mark[RD_MARK_WORDS];                  // positions of the region within guard_r patches of an occupancy patch in reach
     __shared__ uint32_t need_s;
     const int p = first_particle + blockIdx.x;
-    const uint32_t W = prm.W, WW = W * W;
+    const uint32_t W = prm.W;
     const int tid = threadIdx.x, r = (int)prm.guard_r;
     const PV pv = pview_w(prm, p);
     const int16_t* occ_dir = pv.occ_dir;
     const int16_t* dm_dir = pv.dm_dir;
     // the patches the scan can touch: sensor origin (tf.translation(), src/pf_slam2d.cpp:452) +- reach, window-relative patch units
-    const int scx = (int)(w2m(prm, uload_f64(tfs + 12 * (size_t)p + 9)) - prm.wx0), scy = (int)(w2m(prm, uload_f64(tfs + 12 * (size_t)p + 10)) - prm.wy0);
+    // (TAB = TfTable: a block of at most ARG_BLOCK particles, its transforms came with the launch)
+    double stx, sty;
+    if constexpr (std::is_same<TAB, TfTable>::value) { const int tb = (int)blockIdx.x & (ARG_BLOCK - 1); stx = tab.v[12 * tb + 9]; sty = tab.v[12 * tb + 10]; }
+    else { stx = uload_f64(tfs + 12 * (size_t)p + 9); sty = uload_f64(tfs + 12 * (size_t)p + 10); }
+    const int scx = (int)(w2m(prm, stx) - prm.wx0), scy = (int)(w2m(prm, sty) - prm.wy0);
     const int bx0 = imax((scx - reach_cells) >> 5, 0), bx1 = imin((scx + reach_cells) >> 5, (int)W - 1);
     const int by0 = imax((scy - reach_cells) >> 5, 0), by1 = imin((scy + reach_cells) >> 5, (int)W - 1);
     // the marked region: that box grown by guard_r, clipped to the window; too large for the bitmap -> counted in tiles below
@@ -220,8 +226,10 @@ __global__ __launch_bounds__(256) void k_occ_reverse_dir(DevParams prm, int firs
     for (uint32_t i = tid; i < (nbits + 31u) / 32u; i += 256u) mark[i] = 0;
     if (tid == 0) need_s = 0;
     __syncthreads();
-    // eight directory entries per thread and round (W is a multiple of 8: a run never leaves its row, 16-byte aligned)
-    for (uint32_t w0 = (uint32_t)tid * 8u; w0 < WW; w0 += 256u * 8u) {
+    // eight directory entries per thread and round (W is a multiple of 8: a run never leaves its row, 16-byte aligned), over the
+    // rows [row0, row1] that can hold a patch at all: the host's mapped box, which every patch of every particle lies in
+    const uint32_t w_end = (row1 < W ? row1 + 1u : W) * W;
+    for (uint32_t w0 = row0 * W + (uint32_t)tid * 8u; w0 < w_end; w0 += 256u * 8u) {
         const uint4 q = *reinterpret_cast<const uint4*>(occ_dir + w0);
         if ((q.x & q.y & q.z & q.w) == 0xFFFFFFFFu) continue;                 // eight absent patches (-1): the common case
         const uint32_t ww[4] = {q.x, q.y, q.z, q.w};
@@ -240,15 +248,13 @@ __global__ __launch_bounds__(256) void k_occ_reverse_dir(DevParams prm, int firs
         }
     }
     __syncthreads();
+    // a position per thread and round, not a word of 32: the directory reads of a round are independent of each other, where the
+    // bits of a word made one thread wait for up to 32 of them in turn (a few hundred positions: the kernel was mostly this wait)
     uint32_t need = 0;
-    for (uint32_t i = tid; i < (nbits + 31u) / 32u; i += 256u) {
-        uint32_t m = mark[i];
-        while (m) {
-            const uint32_t n = i * 32u + (uint32_t)(__ffs((int)m) - 1);
-            const uint32_t wx = (uint32_t)mx0 + n % (uint32_t)mw, wy = (uint32_t)my0 + n / (uint32_t)mw;
-            if (dm_dir[wy * W + wx] < 0) ++need;
-            m &= m - 1u;
-        }
+    for (uint32_t n = (uint32_t)tid; n < nbits; n += 256u) {
+        if (!((mark[n >> 5] >> (n & 31u)) & 1u)) continue;
+        const uint32_t wx = (uint32_t)mx0 + n % (uint32_t)mw, wy = (uint32_t)my0 + n / (uint32_t)mw;
+        if (dm_dir[wy * W + wx] < 0) ++need;
     }
     if (need) atomicAdd(&need_s, need);
     __syncthreads();
