@@ -364,6 +364,9 @@ void host_scan_tf(const double* pose4, const Affine& m, double* out12)
     }
 }
 
+// how many patches beyond an obstacle's own the brushfire can reach (and allocate): ceil(l2_max / resolution) + 1 cells
+uint32_t guard_radius(const lama_hip_ctx* c) { return ((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u; }
+
 DevParams make_params(const lama_hip_ctx* c)
 {
     DevParams p;
@@ -377,7 +380,7 @@ DevParams make_params(const lama_hip_ctx* c)
     const MapStore& s = c->ms;
     p.dm_dir = s.dm_dir; p.occ_dir = s.occ_dir; p.counts = s.counts;
     p.guard = c->d_guard;
-    p.guard_r = ((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u;
+    p.guard_r = guard_radius(c);
     p.poses = c->d_poses; p.q_lower = c->d_qlower; p.q_raise = c->d_qraise; p.stats = c->d_stats; p.qsizes = c->d_qsizes; p.err = c->d_err; p.dbg = c->d_dbg; p.slow = c->d_slow; p.slow_list = c->d_slow_list; p.slow_n = c->d_slow_n; p.heavy = nullptr; p.elist = nullptr; p.elist_n = nullptr; p.early = nullptr; p.lane = 0;
     p.act = c->d_act; p.act_count = c->d_act_count; p.act_cap = c->cfg.active_capacity;
     p.occ_policy = c->cfg.occupancy_policy; p.ray_rule = c->cfg.ray_rule; p.strategy = c->cfg.solver_strategy;
@@ -407,6 +410,15 @@ int32_t wait_for_groups(lama_hip_ctx* c)
     return LAMA_HIP_OK;
 }
 
+// The largest squared point distance of a scan.  False when a coordinate is infinite: no cell (the reference's w2m casts it to an integer:
+// undefined behaviour, include/lama/sdm/map.h:125-128); strict: or a NaN (std::max drops it, the sum of products with zero keeps it)
+bool scan_reach2(const double* pts, size_t n, bool strict, double& r2)
+{
+    double nan_acc = r2 = 0.0;
+    for (size_t i = 0; i < n; ++i) { const double d2 = pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2]; r2 = std::max(r2, d2); nan_acc += d2 * 0.0; }
+    return std::isfinite(r2) && (!strict || nan_acc == 0.0);
+}
+
 int32_t upload_scan(lama_hip_ctx* c, const double* pts, uint32_t n)
 {
     if (!pts) {      // reuse the scan uploaded by the previous call (same scan for scan_match and update_maps)
@@ -418,9 +430,7 @@ int32_t upload_scan(lama_hip_ctx* c, const double* pts, uint32_t n)
     c->h_pts.resize((size_t)3 * n);                       // the caller's buffer is only borrowed for the call
     std::memcpy(c->h_pts.data(), pts, sizeof(double) * 3 * n);
     double r2 = 0.0;
-    for (uint32_t i = 0; i < n; ++i) r2 = std::max(r2, pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2]);
-    // a non-finite coordinate has no cell (the reference's w2m casts it to an integer: undefined behaviour, include/lama/sdm/map.h:125-128)
-    if (!std::isfinite(r2)) { c->last_n = 0; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
+    if (!scan_reach2(pts, n, false, r2)) { c->last_n = 0; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
     c->scan_reach = std::sqrt(r2);
     HIPCHK(c, hipMemcpyAsync(c->d_pts, c->h_pts.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
     return LAMA_HIP_OK;
@@ -439,12 +449,9 @@ int32_t ensure_batch(lama_hip_ctx* c, size_t entries, size_t floor = 0)
 }
 
 void resolve_timers(lama_hip_ctx* c);
-
-// End of an API call: one stream synchronisation that brings back the device error word and, when asked, the
-// per-particle patch counts and statistics (a single host round trip per call).
 int32_t grow_arenas(lama_hip_ctx* c, uint32_t first, uint32_t count);
 int32_t recover_update(lama_hip_ctx* c, int32_t e);
-int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count, StepGroup* g = nullptr);
+int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count);
 int32_t permute_particles(lama_hip_ctx* c, const int32_t* idx);
 
 // A failed allocation keeps counting (dir_alloc_one: the counts then say what a particle WANTED, which the clean-abort path
@@ -477,37 +484,61 @@ int32_t device_error_result(lama_hip_ctx* c, int32_t e)
     return fail(c, LAMA_HIP_E_NUMERIC, "unit complex number is (near) zero (SophusException in the reference)");
 }
 
+// A map update's status in the fetched bytes of the pool's packed block or of a group's k_pack_group block (read with memcpy): error word,
+// 5 hand-over counts, and for the particles base .. base + n their [n][4] statistics words, [n] guard bounds and [n][2] patch counts.
+struct StatusView {
+    const uint8_t *err, *slow_n, *stats, *guard, *counts; uint32_t base, n;
+    int32_t error() const { int32_t e; std::memcpy(&e, err, sizeof(e)); return e; }
+};
+
+// an update's status goes into the counters and host mirrors; of one that succeeded (particles [first, first + count)) also the cell statistics and, if given, the chains
+void apply_update_status(lama_hip_ctx* c, const StatusView& v, uint32_t first, uint32_t count, uint64_t* chain)
+{
+    uint32_t sn[5]; std::memcpy(sn, v.slow_n, sizeof(sn));
+    c->ctr.brushfire_handovers += sn[0]; c->ctr.replay_handovers += sn[1] + sn[3]; c->ctr.brushfire_routed += sn[2] + sn[4]; c->ctr.brushfire_early += sn[4];
+    c->early_candidates = sn[2] + sn[4];
+    c->h_guard.resize(c->P);
+    std::memcpy(&c->h_guard[v.base], v.guard, sizeof(uint32_t) * v.n);
+    std::memcpy(&c->h_counts[2 * (size_t)v.base], v.counts, sizeof(int32_t) * 2 * v.n);
+    if (v.error() != 0) return;
+    for (uint32_t p = first; p < first + count; ++p) {
+        uint64_t st[4]; std::memcpy(st, v.stats + sizeof(st) * (p - v.base), sizeof(st));
+        c->ctr.ray_cells += st[2]; c->ctr.bf_cells += st[3]; if (chain) chain[p] = st[3];
+    }
+}
+
+void refresh_patch_totals(lama_hip_ctx* c)
+{
+    c->ctr.dm_patches = c->ctr.occ_patches = 0;
+    for (uint32_t p = 0; p < c->P; ++p) { c->ctr.dm_patches += c->h_counts[2 * p]; c->ctr.occ_patches += c->h_counts[2 * p + 1]; }
+}
+
+// End of an API call: one stream synchronisation that brings back the device error word and, when asked, a map update's packed
+// status (maps) or a scan match's statistics (match; err_in_results: its error word has come with its results): one round trip.
 int32_t check_device_errors(lama_hip_ctx* c, bool maps = false, bool match = false, bool err_in_results = false)
 {
     c->h_err.resize(1);
-    int32_t& e = c->h_err[0];
-    e = 0;
-    const bool stats = maps || match;
-    const bool packed = maps && !err_in_results;      // a map update: error word, hand-over counts, statistics, guard and patch counts in ONE copy
-    if (stats) c->h_stats.resize((size_t)c->P * 4);
-    if (packed) {
-        c->h_status.resize(c->status_bytes); c->h_guard.resize(c->P); c->h_slow_n.resize(5);
+    int32_t& e = c->h_err[0] = 0;
+    if (maps || match) c->h_stats.resize((size_t)c->P * 4);
+    if (maps) {
+        c->h_status.resize(c->status_bytes); c->h_slow_n.resize(5);
         HIPCHK(c, hipMemcpyAsync(c->h_status.data(), c->d_results + c->status_off, c->status_bytes, hipMemcpyDeviceToHost, c->stream));
     } else {
-        if (stats) {
+        if (match) {
             HIPCHK(c, hipMemcpyAsync(c->h_counts.data(), c->ms.counts, sizeof(int32_t) * 2 * c->P, hipMemcpyDeviceToHost, c->stream));
-            if (maps) { c->h_guard.resize(c->P); HIPCHK(c, hipMemcpyAsync(c->h_guard.data(), c->d_guard, sizeof(uint32_t) * c->P, hipMemcpyDeviceToHost, c->stream)); }
             HIPCHK(c, hipMemcpyAsync(c->h_stats.data(), c->d_stats, sizeof(uint64_t) * c->h_stats.size(), hipMemcpyDeviceToHost, c->stream));
         }
         if (!err_in_results) HIPCHK(c, hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-        if (maps) { c->h_slow_n.resize(5); HIPCHK(c, hipMemcpyAsync(c->h_slow_n.data(), c->d_slow_n, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream)); }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (packed) {
-        const uint8_t* b = c->h_status.data();
-        const size_t o_slow = (const uint8_t*)c->d_slow_n - (c->d_results + c->status_off);
-        std::memcpy(&e, b, sizeof(e));
-        std::memcpy(c->h_slow_n.data(), b + o_slow, 5 * sizeof(uint32_t));
-        std::memcpy(c->h_stats.data(), b + o_slow + 32, sizeof(uint64_t) * 4 * c->P);
-        std::memcpy(c->h_guard.data(), b + o_slow + 32 + sizeof(uint64_t) * 4 * c->P, sizeof(uint32_t) * c->P);
-        std::memcpy(c->h_counts.data(), b + o_slow + 32 + sizeof(uint64_t) * 4 * c->P + sizeof(uint32_t) * 2 * c->P, sizeof(int32_t) * 2 * c->P);
+    if (maps) {
+        const uint8_t* const b = c->h_status.data(), * const sn = b + ((const uint8_t*)c->d_slow_n - (c->d_results + c->status_off));
+        const StatusView v{b, sn, sn + 32, sn + 32 + 32 * (size_t)c->P, sn + 32 + 40 * (size_t)c->P, 0u, c->P};
+        e = v.error();
+        std::memcpy(c->h_slow_n.data(), v.slow_n, 5 * sizeof(uint32_t));                 // (mirrors: the longest chain below, recover_group)
+        std::memcpy(c->h_stats.data(), v.stats, sizeof(uint64_t) * 4 * c->P);
+        apply_update_status(c, v, c->last_first, c->last_count, nullptr);      // (a block's update leaves the others' statistics alone)
     }
-    if (maps) { c->ctr.brushfire_handovers += c->h_slow_n[0]; c->ctr.replay_handovers += c->h_slow_n[1] + c->h_slow_n[3]; c->ctr.brushfire_routed += c->h_slow_n[2] + c->h_slow_n[4]; c->ctr.brushfire_early += c->h_slow_n[4]; c->early_candidates = c->h_slow_n[2] + c->h_slow_n[4]; }
     if (err_in_results) std::memcpy(&e, c->h_results.data() + ((const uint8_t*)c->d_err - c->d_results), sizeof(e));
     resolve_timers(c);
     if (e != 0) {
@@ -517,39 +548,27 @@ int32_t check_device_errors(lama_hip_ctx* c, bool maps = false, bool match = fal
             const int32_t rr = recover_update(c, e);
             if (rr != LAMA_HIP_E_CAPACITY) return rr;      // done (or another error); E_CAPACITY: the arenas are at their limit
         }
-        if (e & (ERR_DM_CAP | ERR_OCC_CAP)) { const int32_t rcl = clamp_counts(c, !stats); if (rcl) return rcl; }
+        if (e & (ERR_DM_CAP | ERR_OCC_CAP)) { const int32_t rcl = clamp_counts(c, !(maps || match)); if (rcl) return rcl; }
         return device_error_result(c, e);
     }
-    if (stats) {
-        const PinVec<uint64_t>& st = c->h_stats;
-        uint64_t dm = 0, oc = 0;
-        // (a map update's statistics: of the particles it ran for -- a block's update leaves the others' words alone)
-        const uint32_t m0 = c->last_first, m1 = c->last_first + c->last_count;
-        for (uint32_t p = 0; p < c->P; ++p) {
-            if (match) { c->ctr.gn_iterations += st[4 * p]; c->ctr.gn_evals += st[4 * p + 1]; }
-            if (maps && p >= m0 && p < m1) { c->ctr.ray_cells += st[4 * p + 2]; c->ctr.bf_cells += st[4 * p + 3]; }
-            dm += c->h_counts[2 * p]; oc += c->h_counts[2 * p + 1];
+    if (match) for (uint32_t p = 0; p < c->P; ++p) { c->ctr.gn_iterations += c->h_stats[4 * p]; c->ctr.gn_evals += c->h_stats[4 * p + 1]; }
+    if (maps || match) refresh_patch_totals(c);
+    if (!maps) return LAMA_HIP_OK;
+    uint64_t mx = 0, sum = 0; uint32_t arg = 0;                     // the update lasted as long as its longest chain
+    for (uint32_t p = c->last_first; p < c->last_first + c->last_count; ++p) { const uint64_t v = c->h_stats[4 * p + 3]; sum += v; if (v > mx) { mx = v; arg = p; } }
+    c->ctr.bf_longest_chain_sum += mx; c->ctr.bf_longest_chain_last = mx;
+    if (c->debug_tail) {
+        // (how well would the scan match's log-likelihood have predicted the longest chain? its rank among the pool, 0 = lowest)
+        uint32_t rank = 0; double ll = 0, mean_ll = 0;
+        if (c->h_results.size() >= c->results_bytes && c->P > 1) {
+            const double* L = reinterpret_cast<const double*>(c->h_results.data() + sizeof(double) * 4 * c->P);
+            ll = L[arg];
+            for (uint32_t p = 0; p < c->P; ++p) { rank += L[p] < ll ? 1u : 0u; mean_ll += L[p]; }
+            mean_ll /= c->P;
         }
-        c->ctr.dm_patches = dm; c->ctr.occ_patches = oc;
-        if (maps) {                                                  // the update lasted as long as its longest chain
-            uint64_t mx = 0, sum = 0; uint32_t arg = 0;
-            for (uint32_t p = m0; p < m1; ++p) { sum += st[4 * p + 3]; if (st[4 * p + 3] > mx) { mx = st[4 * p + 3]; arg = p; } }
-            c->ctr.bf_longest_chain_sum += mx; c->ctr.bf_longest_chain_last = mx;
-            if (c->debug_tail) {
-                // (how well would the scan match's log-likelihood have predicted the longest chain? its rank among the pool, 0 = lowest)
-                uint32_t rank = 0; double ll = 0, mean_ll = 0;
-                if (c->h_results.size() >= c->results_bytes && c->P > 1) {
-                    const double* L = reinterpret_cast<const double*>(c->h_results.data() + sizeof(double) * 4 * c->P);
-                    ll = L[arg];
-                    for (uint32_t p = 0; p < c->P; ++p) { rank += L[p] < ll ? 1u : 0u; mean_ll += L[p]; }
-                    mean_ll /= c->P;
-                }
-                std::fprintf(stderr, "brushfire pops: mean %.0f max %llu (particle %u) handovers %u brushfire %.3f ms; log-lik of that particle %.1f (pool mean %.1f), rank %u of %u\n", (double)sum / c->P, (unsigned long long)mx, arg, c->h_slow_n[0], c->ctr.ms_brushfire, ll, mean_ll, rank, c->P);
-            }
-        }
-        if (maps) return grow_arenas(c, 0, c->P);
+        std::fprintf(stderr, "brushfire pops: mean %.0f max %llu (particle %u) handovers %u brushfire %.3f ms; log-lik of that particle %.1f (pool mean %.1f), rank %u of %u\n", (double)sum / c->P, (unsigned long long)mx, arg, c->h_slow_n[0], c->ctr.ms_brushfire, ll, mean_ll, rank, c->P);
     }
-    return LAMA_HIP_OK;
+    return grow_arenas(c, 0, c->P);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -818,10 +837,10 @@ int32_t recover_update(lama_hip_ctx* c, int32_t e)
     return rc;
 }
 
-// Collects the status of a map update queued by lama_hip_pf_update_maps_begin (one synchronisation); called at the start of
-// every other entry point, so a deferred error surfaces in the next call on the context.
 int32_t drain_groups(lama_hip_ctx* c);
 int32_t apply_resample(lama_hip_ctx* c, const int32_t* idx);
+// Collects the status of a map update queued by lama_hip_pf_update_maps_begin (one synchronisation); called at the start of
+// every other entry point, so a deferred error surfaces in the next call on the context.
 int32_t finish_pending(lama_hip_ctx* c)
 {
     if (c->groups_busy) { (void)hipSetDevice(c->cfg.device); const int32_t rg = drain_groups(c); if (rg) { c->resample_deferred = false; return rg; } }
@@ -840,7 +859,8 @@ int32_t finish_pending(lama_hip_ctx* c)
     }
     return LAMA_HIP_OK;
 }
-#define ENTER(c) do { if ((c)->poisoned) return fail((c), LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue"); const int32_t rc_enter_ = finish_pending(c); if (rc_enter_) return rc_enter_; } while (0)
+int32_t refuse_poisoned(lama_hip_ctx* c) { return fail(c, LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue"); }
+#define ENTER(c) do { if ((c)->poisoned) return refuse_poisoned(c); const int32_t rc_enter_ = finish_pending(c); if (rc_enter_) return rc_enter_; } while (0)
 
 // hipEvent bracket around a kernel group; resolved (elapsed time read) by resolve_timers() after the API call's final
 // stream synchronisation, so profiling adds no host round trips.
@@ -863,6 +883,8 @@ struct Timer {
         a = c->ev_pool[c->ev_used++]; b = c->ev_pool[c->ev_used++];
         (void)hipEventRecord(a, c->stream);
     }
+    // the ray-cast (ray: kind 1) or brushfire (kind 2) bracket of a map update: its group's, else the context's
+    static Timer of_update(lama_hip_ctx* c, StepGroup* g, int kind) { return g ? Timer(c, g, kind) : kind == 1 ? Timer(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast) : Timer(c, &c->ctr.ms_brushfire, &c->ctr.launches_brushfire); }
     void stop()
     {
         if (!c->cfg.profile) return;
@@ -1014,7 +1036,7 @@ int32_t fit_window(lama_hip_ctx* c, const Affine& mtf, uint32_t first, uint32_t 
     // padding: the brushfire allocates distance-map patches up to guard_r patches beyond a hit (make_params: ceil(l2_max / resolution)
     // + 1 cells), plus one patch for the rounding of the box.  permute_particles copies only the directory rows inside this box, so a
     // patch outside it would be lost by a clone (a fixed 2 patches were too few for l2_max above 64 cells).
-    const uint32_t guard_r = ((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u;
+    const uint32_t guard_r = guard_radius(c);
     const double reach = far + std::sqrt(mtf.t[0] * mtf.t[0] + mtf.t[1] * mtf.t[1]) + (double)(guard_r + 1u) * 32.0 * c->cfg.resolution;
     double xlo = 1e300, xhi = -1e300, ylo = 1e300, yhi = -1e300;
     for (uint32_t p = first; p < first + count; ++p) {
@@ -1026,25 +1048,137 @@ int32_t fit_window(lama_hip_ctx* c, const Affine& mtf, uint32_t first, uint32_t 
     return ensure_window(c, patch(xlo), patch(xhi), patch(ylo), patch(yhi));
 }
 
-// The dispatcher hands workgroup number b of a launch to XCD b mod 8, and every XCD has its own L2.  A one-dimensional launch with a
-// workgroup per particle therefore keeps particle p on XCD p mod 8 in every kernel of an update; a two-dimensional one (particle,
-// something) does so only when its particle dimension is a multiple of 8 -- else the workgroups of one particle are spread over all
-// XCDs and the brushfire finds none of its cells in the L2 its ray-cast wrote them through.  Launches over the whole pool round the
-// particle dimension up (the kernels skip particles >= P).
+// how many particles may go to the big-queue stage beside the first one: an 84 KB workgroup takes the LDS of seven first-stage
+// workgroups, and a first stage that no longer fits the chip in one round (12 per CU) costs far more than the routing saves
+static uint32_t route_places(const lama_hip_ctx* c, uint32_t count)
+{
+    const uint32_t slots = c->num_cus * 12u;
+    if (c->route_forced || count >= slots) return c->route_cap;                 // (several rounds anyway)
+    return std::min<uint32_t>(c->route_cap, std::max<uint32_t>(8u, (slots - count) / 7u));
+}
+
+// A map update is decided (plan_update), noted (note_update_begin) and launched (launch_update).  The plan's defaults are the plain parallel update: all a particle group ever runs (step_can_group); the rest is decided for the main stream only.
+struct UpdatePlan {
+    hipStream_t s = nullptr; const double* d_pts = nullptr; uint32_t n = 0, first = 0, count = 0;      // the main lane's stream, the scan as uploaded on it
+    DevParams prm;                                                    // (error word and hand-over lists: the context's or a group's)
+    lama_dev::TfTable tab = lama_dev::TfTable(); bool tf_by_value = false;     // the scan transforms travel with the launches, d_tfs is not read
+    StepGroup* timers = nullptr;                                      // whose brackets time the update: the group's own, else the context's
+    bool sequential = false, guarded = true, canon = false, two_waves = false, route = false, early_lane = false;
+    bool prev_routed = false; uint32_t host_n = 0;                    // early lane: d_heavy holds the previous update's routed particles; entries of h_hlist
+    uint32_t route_places = 0; unsigned gy = 0, resume_grid = 0; bool replay_large = true;
+};
+
+// the parallel kernels implement the frequency counters and the PF ray rule only; every hit is an order-sensitive visit (the list holds
+// active_capacity of them), the visit key carries the beam index in 13 bits (act_key) and k_ray_patches keeps one 64-beam chunk per lane
+static bool parallel_raycast_ruled_out(const lama_hip_ctx* c, uint32_t n)
+{
+    return c->cfg.sequential_raycast == 1 || c->cfg.occupancy_policy == 1 || c->cfg.ray_rule == 1 || n > 4096u || (uint64_t)n + 4096u > c->cfg.active_capacity;
+}
+
+// every decision of the map update of particles [first, first + count); g: of that particle group, on its stream; wrap_sequential: wrap_guard_probe's answer
+UpdatePlan plan_update(lama_hip_ctx* c, uint32_t n, uint32_t first, uint32_t count, bool wrap_sequential, StepGroup* g = nullptr)
+{
+    UpdatePlan u;
+    u.n = n; u.first = first; u.count = count; u.timers = g; u.tf_by_value = g && count <= (uint32_t)lama_dev::ARG_BLOCK;
+    u.s = g ? g->s : (hipStream_t)c->stream; u.d_pts = g ? (const double*)g->d_pts : (const double*)c->d_pts; u.prm = g ? group_params(c, *g) : make_params(c);
+    u.two_waves = c->cfg.brushfire_waves == 2 || (c->cfg.brushfire_waves == 0 && count <= BF_TW_MAX_PARTICLES);
+    u.gy = count <= 64 ? 128u : (count >= 1024 ? 8u : 32u);      // workgroups per particle; a full chip needs fewer
+#ifdef LAMA_WAVE_SIM
+    u.gy = 4u;                                   // (tests/sim runs every thread as a fiber: 128 mostly idle workgroups per particle cost it minutes)
+#endif
+    u.replay_large = count <= 512; u.resume_grid = std::min<unsigned>(count, 256u);      // (workgroups that walk the usually empty hand-over lists)
+    if (g) return u;
+    u.sequential = parallel_raycast_ruled_out(c, n) || wrap_sequential;      // both ray-casts are bit-exact; the parallel one wins while the chip is not full
+    u.guarded = c->cfg.ray_rule == 0;            // the allocation walk uses the PF ray rule (else: pregrow_unguarded)
+    u.canon = c->cfg.brushfire_mode == 1;        // opt-in parallel variant; whatever it leaves (qsizes != 0) falls through to the exact stages
+    u.route = u.two_waves && count >= c->route_min_count && c->route_cap > 0; u.route_places = route_places(c, count);
+    // early lane: the particles the previous update routed (long chains, usually long again) ...
+    if (u.sequential || !(c->early_on && u.two_waves && !u.canon && first == 0 && count == c->P &&
+                          count >= std::max<uint32_t>(c->route_min_count, c->early_min_count) && c->route_cap > 0)) return u;
+    if (c->ll_valid) {
+        // ... and those whose scan match of this step fitted far worse than the pool's (log-likelihood below 2.5 times the mean, both negative)
+        double mean = 0; for (uint32_t p = 0; p < c->P; ++p) mean += c->h_ll[p]; mean /= c->P;
+        const double lim = 2.5 * std::min(mean, 0.0) - 5.0;
+        std::vector<std::pair<double, uint32_t>> cand;
+        for (uint32_t p = 0; p < c->P; ++p) if (c->h_ll[p] < lim) cand.emplace_back(c->h_ll[p], p);
+        if (cand.size() > u.route_places) { std::partial_sort(cand.begin(), cand.begin() + u.route_places, cand.end()); cand.resize(u.route_places); }
+        c->h_hlist.resize(256);
+        for (auto& e : cand) c->h_hlist[u.host_n++] = e.second;
+    }
+    u.prev_routed = c->early_ok && c->early_candidates > 0; u.early_lane = u.host_n > 0 || u.prev_routed;
+    return u;
+}
+
+// A uint16 `visited` counter that wraps INSIDE a scan makes the order of the visits matter (k_occ_max_visited): where the host's bound
+// cannot rule that out, the device is asked for the largest counter (`bound`, else left at -1).  note_update_begin takes the answer.
+int32_t wrap_guard_probe(lama_hip_ctx* c, uint32_t n, int64_t& bound)
+{
+    if (parallel_raycast_ruled_out(c, n) || (uint64_t)c->visit_bound + n < 65536u) return LAMA_HIP_OK;
+    uint32_t m = 0;
+    if (c->initialised) {
+        const DevParams prm = make_params(c);
+        (void)hipMemsetAsync(c->d_scalar, 0, sizeof(uint32_t), c->stream);
+        hipLaunchKernelGGL(k_occ_max_visited, dim3(c->P), dim3(256), 0, c->stream, prm, c->d_scalar);
+        HIPCHK(c, hipMemcpyAsync(&m, c->d_scalar, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    bound = m;
+    return LAMA_HIP_OK;
+}
+
+// the allocation phase walks by the PF ray rule: under LidarOdometry's rule the particles get every patch a scan of this reach can touch beforehand
+int32_t pregrow_unguarded(lama_hip_ctx* c, uint32_t first, uint32_t count)
+{
+    if (c->cfg.ray_rule == 0) return LAMA_HIP_OK;
+    const double rp = c->scan_reach / (32.0 * c->cfg.resolution) + 2.5;
+    const uint32_t bound = (uint32_t)std::min(32767.0, std::ceil(3.1416 * rp * rp));
+    std::vector<CapRequest> reqs;
+    for (uint32_t p = first; p < first + count; ++p) {
+        const HostPart& pr = c->h_part[p];
+        const uint32_t nd = std::min<uint32_t>(MAX_PATCHES, round_up32((uint32_t)c->h_counts[2 * p] + bound)), no = std::min<uint32_t>(MAX_PATCHES, round_up32((uint32_t)c->h_counts[2 * p + 1] + bound));
+        if (nd > pr.dm_cap || no > pr.occ_cap) reqs.push_back(CapRequest{p, std::max(nd, pr.dm_cap), std::max(no, pr.occ_cap)});
+    }
+    return reqs.empty() ? LAMA_HIP_OK : set_capacities(c, reqs);
+}
+
+// the host-side effects of beginning an update (a grouped step: once, for the pool); saved_*: what a repeat must not apply twice
+void note_update_begin(lama_hip_ctx* c, const Affine& mtf, const UpdatePlan& u, int64_t probed)
+{
+    c->last_mtf = mtf; c->last_first = u.first; c->last_count = u.count; c->last_guarded = u.guarded;
+    if (c->recover_depth == 0) { c->saved_visit_bound = c->visit_bound; c->saved_ctr = c->ctr; }
+    if (probed >= 0) { c->visit_bound = (uint32_t)probed; if (u.sequential) c->ctr.wrap_guard_scans += 1; }
+    c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + u.n, 65535u);
+    if (u.sequential) c->ctr.sequential_raycast_scans += 1; else c->ctr.parallel_raycast_scans += 1;
+    c->early_ok = u.route && u.first == 0 && u.count == c->P;      // (early lane included; a resample takes it back)
+}
+
+// the scan transforms of particles [first, first + count): into `tab` (launch arguments) or to d_tfs on stream s
+int32_t stage_scan_tfs(lama_hip_ctx* c, const Affine& mtf, uint32_t first, uint32_t count, hipStream_t s, lama_dev::TfTable* tab)
+{
+    PinVec<double>& tfs = c->h_tfs; tfs.resize((size_t)c->P * 12);
+    for (uint32_t p = first; p < first + count; ++p) host_scan_tf(&c->h_poses[4 * p], mtf, &tfs[12 * (size_t)p]);
+    if (tab) std::memcpy(tab->v, &tfs[12 * (size_t)first], sizeof(double) * 12 * count);
+    else HIPCHK(c, hipMemcpyAsync(c->d_tfs + 12 * (size_t)first, &tfs[12 * (size_t)first], sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
+    return LAMA_HIP_OK;
+}
+
+// Workgroup b of a launch goes to XCD b mod 8, each with its own L2: a two-dimensional launch (particle, something) keeps a particle's
+// workgroups on the XCD of its one-dimensional launches only when its particle dimension is a multiple of 8 (else the brushfire finds
+// none of its cells in the L2 its ray-cast wrote them through).  The whole pool, or its last block, rounds up (the kernels skip
+// particles >= P); the blocks in front cannot -- the next particle is another group's -- and are multiples of 8 where the split allows.
 static unsigned xcd_grid(const lama_hip_ctx* c, uint32_t first, uint32_t count)
 {
-    // (the last block of a pool may round up like the whole pool; the blocks in front of it cannot -- the next particle is another
-    // group's -- and are multiples of 8 wherever the split allows, see lama_hip_ctx_create)
     return first + count == c->P ? (count + 7u) / 8u * 8u : count;
 }
 
 // allocation phase of a map update (ray records, hit cells' patches, the patches the rays cross, the bound on the distance-map patches
 // still to come): afterwards either every patch the update needs exists or an error bit is set and no map cell has been modified
-int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t n, uint32_t first, uint32_t count, int alloc_only, hipStream_t s, const double* d_pts,
-                                const lama_dev::TfTable* tab = nullptr)
+// (tab: k_ray_hits and k_occ_reverse_dir take the scan transforms as a launch argument, the plan's TfTable, or read d_tfs: NoTable)
+template <class Tab>
+int32_t launch_allocation_phase(lama_hip_ctx* c, const UpdatePlan& u, int alloc_only, const Tab& tab)
 {
-    // tab: the block's scan transforms travel with the launches (at most ARG_BLOCK particles), d_tfs is not read
-    const double* const d_tfs = tab ? nullptr : (const double*)c->d_tfs;
+    const uint32_t n = u.n, first = u.first, count = u.count;
+    const double* const d_tfs = u.tf_by_value ? nullptr : (const double*)c->d_tfs;
     const size_t need = (size_t)c->P * n;
     if (need > c->d_rrec.n) {                                       // all three are freed before any is allocated
         c->d_rrec.reset(); c->d_rbbox.reset(); c->d_rchunk.reset();
@@ -1054,12 +1188,10 @@ int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t 
         if (e != hipSuccess) { c->d_rrec.reset(); return hip_fail(c, e, "ray buffers"); }
     }
     const dim3 hits_grid(xcd_grid(c, first, count), (n + 255) / 256);
-    if (tab) hipLaunchKernelGGL(k_ray_hits<lama_dev::TfTable>, hits_grid, dim3(256), 0, s, prm, d_pts, (int)n, d_tfs, (int)first,
-                                (lama_dev::RayRec*)c->d_rrec, (uint64_t*)c->d_rbbox, alloc_only, (lama_dev::RayChunk*)c->d_rchunk, *tab);
-    else hipLaunchKernelGGL(k_ray_hits<lama_dev::NoTable>, hits_grid, dim3(256), 0, s, prm, d_pts, (int)n, d_tfs, (int)first,
-                            (lama_dev::RayRec*)c->d_rrec, (uint64_t*)c->d_rbbox, alloc_only, (lama_dev::RayChunk*)c->d_rchunk, lama_dev::NoTable());
+    hipLaunchKernelGGL(k_ray_hits<Tab>, hits_grid, dim3(256), 0, u.s, u.prm, u.d_pts, (int)n, d_tfs, (int)first,
+                       (lama_dev::RayRec*)c->d_rrec, (uint64_t*)c->d_rbbox, alloc_only, (lama_dev::RayChunk*)c->d_rchunk, tab);
     const int rw_seg = count <= 64 ? 4 : 1;
-    hipLaunchKernelGGL(k_ray_alloc_walk, dim3(xcd_grid(c, first, count), (n * rw_seg + 255) / 256), dim3(256), 0, s, prm, (const lama_dev::RayRec*)c->d_rrec, (int)n, (int)first, rw_seg);
+    hipLaunchKernelGGL(k_ray_alloc_walk, dim3(xcd_grid(c, first, count), (n * rw_seg + 255) / 256), dim3(256), 0, u.s, u.prm, (const lama_dev::RayRec*)c->d_rrec, (int)n, (int)first, rw_seg);
     double far = c->scan_reach;                                   // no cell further than truncated_range from the sensor is touched
     if (c->cfg.truncated_range > 0.0) far = std::min(far, c->cfg.truncated_range);
     const int reach_cells = (int)std::ceil(far * c->scale) + 2;
@@ -1070,216 +1202,111 @@ int32_t launch_allocation_phase(lama_hip_ctx* c, const DevParams& prm, uint32_t 
         const int64_t lo = std::min(std::max(c->mby0 - oy, (int64_t)0), W - 1), hi = std::min(std::max(c->mby1 - oy, (int64_t)0), W - 1);
         if (hi >= lo) { row0 = (uint32_t)lo; row1 = (uint32_t)hi; }
     }
-    if (tab) hipLaunchKernelGGL(k_occ_reverse_dir<lama_dev::TfTable>, dim3(count), dim3(256), 0, s, prm, (int)first, d_tfs, reach_cells,
-                                c->unguarded_retry ? 1 : 0, row0, row1, *tab);
-    else hipLaunchKernelGGL(k_occ_reverse_dir<lama_dev::NoTable>, dim3(count), dim3(256), 0, s, prm, (int)first, d_tfs, reach_cells,
-                            c->unguarded_retry ? 1 : 0, row0, row1, lama_dev::NoTable());
+    hipLaunchKernelGGL(k_occ_reverse_dir<Tab>, dim3(count), dim3(256), 0, u.s, u.prm, (int)first, d_tfs, reach_cells, c->unguarded_retry ? 1 : 0, row0, row1, tab);
+    return LAMA_HIP_OK;
+}
+int32_t launch_allocation_phase(lama_hip_ctx* c, const UpdatePlan& u, int alloc_only) { return u.tf_by_value ? launch_allocation_phase(c, u, alloc_only, u.tab) : launch_allocation_phase(c, u, alloc_only, lama_dev::NoTable()); }
+
+// The early lane's ray-cast kernels run HERE, on an idle chip, its brushfire on a stream of its own; the main lane waits for an event
+// recorded directly in front of that brushfire, so that its big-queue workgroups are placed first (order of dispatch: DESIGN.md section 4)
+int32_t launch_early_lane(lama_hip_ctx* c, const UpdatePlan& u)
+{
+    DevParams pe = u.prm; pe.elist = c->d_elist; pe.elist_n = c->d_slow_n + 4; pe.lane = 1;
+    hipLaunchKernelGGL(k_ray_patches, dim3(u.route_places, 128u), dim3(256), 0, c->stream, pe, (const lama_dev::RayRec*)c->d_rrec,
+                       (const uint64_t*)c->d_rbbox, (const lama_dev::RayChunk*)c->d_rchunk, (int)u.n, 0);
+    hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(u.route_places), dim3(RP_BLOCK_LARGE), 0, c->stream, pe, 0);
+    hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(u.route_places), dim3(RP_BLOCK_LARGE), 0, c->stream, pe, 0);
+    HIPCHK(c, hipEventRecord(c->ev_alloc, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_alloc, 0));
+    hipLaunchKernelGGL(k_mark_early, dim3(1), dim3(64), 0, c->stream3, pe);
+    HIPCHK(c, hipEventRecord(c->ev_go, c->stream3));
+    hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(u.route_places), dim3(2 * UM_BLOCK), c->big_stage_pad, c->stream3, pe, 0, 2);
+    HIPCHK(c, hipEventRecord(c->ev_early, c->stream3));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_go, 0));
     return LAMA_HIP_OK;
 }
 
-// how many particles may go to the big-queue stage beside the first one: an 84 KB workgroup takes the LDS of seven first-stage
-// workgroups, and a first stage that no longer fits the chip in one round (12 per CU) costs far more than the routing saves
-static uint32_t route_places(const lama_hip_ctx* c, uint32_t count)
+// patch-centric visits: a workgroup owns one occupancy patch of one particle, no global atomics on the counters
+int32_t launch_parallel_raycast(lama_hip_ctx* c, const UpdatePlan& u)
 {
-    const uint32_t slots = c->num_cus * 12u;
-    if (c->route_forced || count >= slots) return c->route_cap;                 // (several rounds anyway)
-    return std::min<uint32_t>(c->route_cap, std::max<uint32_t>(8u, (slots - count) / 7u));
+    const int first = (int)u.first; const uint32_t host_n = u.host_n;
+    if (u.early_lane) {                                             // the early list, before anything is queued
+        if (host_n) HIPCHK(c, hipMemcpyAsync(c->d_hlist, c->h_hlist.data(), sizeof(uint32_t) * host_n, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_early_list, dim3(1), dim3(256), 0, c->stream, u.prev_routed ? (const uint8_t*)c->d_heavy : (const uint8_t*)nullptr,
+                           (const uint32_t*)c->d_hlist, host_n, c->d_early, c->d_elist, c->d_slow_n + 4, (int)c->P, u.route_places);
+    }
+    { const int32_t ra = launch_allocation_phase(c, u, 0); if (ra) return ra; }
+    DevParams prm = u.prm;
+    if (u.early_lane) { const int32_t re = launch_early_lane(c, u); if (re) return re; prm.early = c->d_early; }     // everybody else: the main lane skips them
+    hipLaunchKernelGGL(k_ray_patches, dim3(xcd_grid(c, u.first, u.count), u.gy), dim3(256), 0, u.s, prm, (const lama_dev::RayRec*)c->d_rrec,
+                       (const uint64_t*)c->d_rbbox, (const lama_dev::RayChunk*)c->d_rchunk, (int)u.n, first);
+    if (u.replay_large) {
+        hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(u.count), dim3(RP_BLOCK_LARGE), 0, u.s, prm, first);
+        hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(u.resume_grid), dim3(RP_BLOCK_LARGE), 0, u.s, prm, first);
+    } else {
+        hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_SMALL>), dim3(u.count), dim3(RP_BLOCK_SMALL), 0, u.s, prm, first);
+        hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_SMALL>), dim3(u.resume_grid), dim3(RP_BLOCK_SMALL), 0, u.s, prm, first);
+    }
+    return LAMA_HIP_OK;
 }
 
-int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count, StepGroup* g)
+// stage 1: small LDS window, every particle; 2: big window, resumes particles whose queue outgrew stage 1; 3: HBM queue for anything larger
+int32_t launch_brushfire(lama_hip_ctx* c, const UpdatePlan& u)
 {
-    // g: the update of one particle group of the grouped step schedule -- its stream, its scan buffer, its error word and hand-over
-    // lists; the caller has fitted the window and ruled out every path below that needs more than the plain parallel update
-    hipStream_t s = g ? g->s : (hipStream_t)c->stream;
-    const double* d_pts = g ? (const double*)g->d_pts : (const double*)c->d_pts;
-    if (!g) {
-        const int32_t rcw = fit_window(c, mtf, first, count);
-        if (rcw) return rcw;
-        c->last_mtf = mtf; c->last_first = first; c->last_count = count;
-        if (c->recover_depth == 0) { c->saved_visit_bound = c->visit_bound; c->saved_ctr = c->ctr; }
-    }
-    PinVec<double>& tfs = c->h_tfs;
-    tfs.resize((size_t)c->P * 12);
-    for (uint32_t p = first; p < first + count; ++p) host_scan_tf(&c->h_poses[4 * p], mtf, &tfs[12 * (size_t)p]);
-    // a group's block of at most ARG_BLOCK particles: the transforms are launch arguments of the two kernels that read them
-    const bool tf_by_value = g && count <= (uint32_t)lama_dev::ARG_BLOCK;
-    lama_dev::TfTable tf_tab = lama_dev::TfTable();
-    if (tf_by_value) std::memcpy(tf_tab.v, &tfs[12 * (size_t)first], sizeof(double) * 12 * count);
-    else HIPCHK(c, hipMemcpyAsync(c->d_tfs + 12 * (size_t)first, &tfs[12 * (size_t)first], sizeof(double) * 12 * count, hipMemcpyHostToDevice, s));
-    DevParams prm = g ? group_params(c, *g) : make_params(c);
-    bool early_lane = false;
-    {
-        Timer t = g ? Timer(c, g, 1) : Timer(c, &c->ctr.ms_raycast, &c->ctr.launches_raycast);
-        // both ray-casts are bit-exact; the parallel one wins while the chip is not yet full of particles
-        // (hand-over counts and statistics: a group's update follows the k_pack_group of its step -- finish_group_step is the only caller
-        // with a group --, which has cleared both behind what it packed)
-        if (first == 0 && count == c->P && !g) {
-            (void)hipMemsetAsync(c->d_slow_n, 0, 32 + sizeof(uint64_t) * 4 * c->P, c->stream);      // hand-over counts and statistics: adjacent (ctx_create)
-        } else if (!g) {                                          // a block: the other particles' statistics may not have been collected yet
-            (void)hipMemsetAsync(prm.slow_n, 0, 32, s);
-            (void)hipMemsetAsync(c->d_stats + 4 * (size_t)first, 0, sizeof(uint64_t) * 4 * count, s);
-        }
-        bool sequential = c->cfg.sequential_raycast == 1 || c->cfg.occupancy_policy == 1 ||
-                          c->cfg.ray_rule == 1;      // the parallel kernels implement the frequency counters and the PF ray rule only
-        // every hit is an order-sensitive visit (the list holds active_capacity of them) and the visit key carries the beam index
-        // in 13 bits (act_key) and k_ray_patches keeps one 64-beam chunk per lane: scans with more than 4096 points go beam by beam
-        if (!sequential && (n > 4096u || (uint64_t)n + 4096u > c->cfg.active_capacity)) sequential = true;
-        // a uint16 `visited` counter that wraps INSIDE a scan makes the order of the visits matter (k_occ_max_visited)
-        if (!g && !sequential && (uint64_t)c->visit_bound + n >= 65536u) {      // (a group's update: step_can_group has looked, with the bound as it was before this scan)
-            uint32_t m = 0;
-            if (c->initialised) {
-                (void)hipMemsetAsync(c->d_scalar, 0, sizeof(uint32_t), c->stream);
-                hipLaunchKernelGGL(k_occ_max_visited, dim3(c->P), dim3(256), 0, c->stream, prm, c->d_scalar);
-                HIPCHK(c, hipMemcpyAsync(&m, c->d_scalar, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-            }
-            c->visit_bound = m;
-            if ((uint64_t)m + n >= 65536u) { sequential = true; c->ctr.wrap_guard_scans += 1; }
-        }
-        if (!g) {                                                 // (a grouped step counts the scan once, for the pool)
-            c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + n, 65535u);
-            if (sequential) c->ctr.sequential_raycast_scans += 1; else c->ctr.parallel_raycast_scans += 1;
-        }
-        // The patches an update needs are allocated BEFORE any cell is modified, so that running out of patches is recoverable
-        // (grow + run again, recover_update).  The allocation walk uses the PF ray rule; LidarOdometry's rule / log-odds cells
-        // (one-particle contexts) get a conservative pre-grown arena instead: every patch a scan of this reach can touch.
-        if (!g) c->last_guarded = c->cfg.ray_rule == 0;
-        if (!g && !c->last_guarded) {
-            const double side = 32.0 * c->cfg.resolution;
-            const double rp = c->scan_reach / side + 2.5;
-            const uint32_t bound = (uint32_t)std::min(32767.0, std::ceil(3.1416 * rp * rp));
-            std::vector<CapRequest> reqs;
-            for (uint32_t p = first; p < first + count; ++p) {
-                const HostPart& pr = c->h_part[p];
-                const uint32_t nd = std::min<uint32_t>(MAX_PATCHES, round_up32((uint32_t)c->h_counts[2 * p] + bound)), no = std::min<uint32_t>(MAX_PATCHES, round_up32((uint32_t)c->h_counts[2 * p + 1] + bound));
-                if (nd > pr.dm_cap || no > pr.occ_cap) reqs.push_back(CapRequest{p, std::max(nd, pr.dm_cap), std::max(no, pr.occ_cap)});
-            }
-            if (!reqs.empty()) {
-                const int32_t rg = set_capacities(c, reqs);
-                if (rg) return rg;
-                prm = make_params(c);
-            }
-        }
-        if (sequential) {
-            if (c->last_guarded) { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 1, c->stream, c->d_pts); if (ra) return ra; }
-            hipLaunchKernelGGL(k_raycast, dim3(count), dim3(UM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, c->d_tfs, (int)first);
-        } else {
-            // patch-centric visits: a workgroup owns one occupancy patch of one particle, no global atomics on the counters
-            // Early lane: the particles the previous update routed (the long brushfire chains; usually long again) get their modifying
-            // ray-cast kernels and their brushfire on a stream of their own right after the allocation phase -- their chain, which is
-            // what the update waits for, no longer starts behind everybody else's ray-cast.
-            const bool two_waves_e = c->cfg.brushfire_waves == 2 || (c->cfg.brushfire_waves == 0 && count <= BF_TW_MAX_PARTICLES);
-            early_lane = c->early_on && two_waves_e && c->cfg.brushfire_mode == 0 && first == 0 && count == c->P &&
-                         count >= std::max<uint32_t>(c->route_min_count, c->early_min_count) && c->route_cap > 0;
-            uint32_t host_n = 0;
-            if (early_lane && c->ll_valid) {
-                // the particles whose scan match of this step fitted far worse than the pool's (log-likelihood below 2.5 times the
-                // mean, both negative): theirs are the long chains of this update -- known before anything is queued
-                const uint32_t places = route_places(c, count);
-                double mean = 0; for (uint32_t p = 0; p < c->P; ++p) mean += c->h_ll[p]; mean /= c->P;
-                const double lim = 2.5 * std::min(mean, 0.0) - 5.0;
-                std::vector<std::pair<double, uint32_t>> cand;
-                for (uint32_t p = 0; p < c->P; ++p) if (c->h_ll[p] < lim) cand.emplace_back(c->h_ll[p], p);
-                if (cand.size() > places) { std::partial_sort(cand.begin(), cand.begin() + places, cand.end()); cand.resize(places); }
-                c->h_hlist.resize(256);
-                for (auto& e : cand) c->h_hlist[host_n++] = e.second;
-                if (host_n) HIPCHK(c, hipMemcpyAsync(c->d_hlist, c->h_hlist.data(), sizeof(uint32_t) * host_n, hipMemcpyHostToDevice, c->stream));
-            }
-            const bool prev_ok = c->early_ok && c->early_candidates > 0;
-            early_lane = early_lane && (host_n > 0 || prev_ok);
-            if (early_lane)
-                hipLaunchKernelGGL(k_early_list, dim3(1), dim3(256), 0, c->stream, prev_ok ? (const uint8_t*)c->d_heavy : (const uint8_t*)nullptr,
-                                   (const uint32_t*)c->d_hlist, host_n, c->d_early, c->d_elist, c->d_slow_n + 4, (int)c->P, route_places(c, count));
-            { const int32_t ra = launch_allocation_phase(c, prm, n, first, count, 0, s, d_pts, tf_by_value ? &tf_tab : nullptr); if (ra) return ra; }
-            // workgroups per particle = patches of a particle in flight at once.  A chip full of particles needs no more parallelism
-            // inside one: 8 instead of 32 workgroups per particle (each then walks ~8 of its ~65 patches behind ONE prologue) took the
-            // ray-cast of the 3000-particle pool from 1.31 to 1.24 ms (round 6); 4 and 16 are within noise of it, 64 is slower
-#ifdef LAMA_WAVE_SIM
-            const unsigned gy = 4u;                              // (tests/sim runs every thread as a fiber: 128 mostly idle workgroups per particle cost it minutes)
-#else
-            const unsigned gy = count <= 64 ? 128u : (count >= 1024 ? 8u : 32u);
-#endif
-            if (early_lane) {
-                // The early lane's own ray-cast kernels run HERE, on an otherwise idle chip (~0.1 ms for a few particles); its
-                // brushfire goes to a stream of its own.  The main lane's 96 k-workgroup launches must not reach the dispatcher before
-                // the early lane's big-queue workgroups (84 KB of LDS each) are placed -- a saturated chip refills every freed slot
-                // with the saturating kernel's next workgroup and starves them until it has drained -- so the main lane waits for an
-                // event that the early stream records directly in front of its brushfire kernel.
-                DevParams pe = prm;
-                pe.elist = c->d_elist; pe.elist_n = c->d_slow_n + 4; pe.lane = 1;
-                const unsigned eg = route_places(c, count);
-                hipLaunchKernelGGL(k_ray_patches, dim3(eg, 128u), dim3(256), 0, c->stream, pe, (const lama_dev::RayRec*)c->d_rrec,
-                                   (const uint64_t*)c->d_rbbox, (const lama_dev::RayChunk*)c->d_rchunk, (int)n, 0);
-                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(eg), dim3(RP_BLOCK_LARGE), 0, c->stream, pe, 0);
-                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(eg), dim3(RP_BLOCK_LARGE), 0, c->stream, pe, 0);
-                HIPCHK(c, hipEventRecord(c->ev_alloc, c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_alloc, 0));
-                hipLaunchKernelGGL(k_mark_early, dim3(1), dim3(64), 0, c->stream3, pe);
-                HIPCHK(c, hipEventRecord(c->ev_go, c->stream3));
-                hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(eg), dim3(2 * UM_BLOCK), c->big_stage_pad, c->stream3, pe, 0, 2);
-                HIPCHK(c, hipEventRecord(c->ev_early, c->stream3));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_go, 0));
-                prm.early = c->d_early;                          // everybody else: the main lane skips them
-            }
-            hipLaunchKernelGGL(k_ray_patches, dim3(xcd_grid(c, first, count), gy), dim3(256), 0, s, prm, (const lama_dev::RayRec*)c->d_rrec,
-                               (const uint64_t*)c->d_rbbox, (const lama_dev::RayChunk*)c->d_rchunk, (int)n, (int)first);
-            const unsigned resume_grid = std::min<unsigned>(count, 256u);       // walks the (usually empty) hand-over list
-            if (count <= 512) {
-                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_LARGE>), dim3(count), dim3(RP_BLOCK_LARGE), 0, s, prm, (int)first);
-                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_LARGE>), dim3(resume_grid), dim3(RP_BLOCK_LARGE), 0, s, prm, (int)first);
-            } else {
-                hipLaunchKernelGGL((k_ray_replay<RP_SORT_SMALL, RP_SORT_SMALL, false, RP_BLOCK_SMALL>), dim3(count), dim3(RP_BLOCK_SMALL), 0, s, prm, (int)first);
-                hipLaunchKernelGGL((k_ray_replay<8192, 8192, true, RP_BLOCK_SMALL>), dim3(resume_grid), dim3(RP_BLOCK_SMALL), 0, s, prm, (int)first);
-            }
-        }
-        t.stop();
-    }
+    const int first = (int)u.first;
+    DevParams prm = u.prm; if (u.early_lane) prm.early = c->d_early;
+    if (u.canon) hipLaunchKernelGGL(k_brushfire_canon, dim3(u.count), dim3(CN_BLOCK), 0, u.s, prm, first);
+    if (u.route) {
+        // the big-queue workgroups (84 KB of LDS) must be placed BEFORE the first stage, which skips them, fills every CU's LDS: it goes to stream2 behind an event
+        prm.heavy = c->d_heavy;
+        hipLaunchKernelGGL(k_bf_route, dim3(1), dim3(256), 0, c->stream, prm, first, (int)u.count, c->route_min_events, c->route_percent, u.route_places);
+        HIPCHK(c, hipEventRecord(c->ev_route, c->stream));
+        hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(u.route_places), dim3(2 * UM_BLOCK), 0, c->stream, prm, first, 1);
+        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_route, 0));
+        hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(u.count), dim3(2 * UM_BLOCK), 0, c->stream2, prm, first, 0);
+        HIPCHK(c, hipEventRecord(c->ev_heavy, c->stream2));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_heavy, 0));
+    } else if (u.two_waves) hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(u.count), dim3(2 * UM_BLOCK), 0, u.s, prm, first, 0);
+    else hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, false>), dim3(u.count), dim3(UM_BLOCK), 0, u.s, prm, first, 0);
+    if (u.two_waves) hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(u.resume_grid), dim3(2 * UM_BLOCK), 0, u.s, prm, first, 0);
+    else hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, false>), dim3(u.resume_grid), dim3(UM_BLOCK), 0, u.s, prm, first, 0);
+    if (u.early_lane) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_early, 0));
+    hipLaunchKernelGGL(k_brushfire_slow, dim3(u.count), dim3(UM_BLOCK), 0, u.s, prm, first);
+    return LAMA_HIP_OK;
+}
+
+// ray_timer: the ray-cast bracket, which the caller has opened (the pool's: in front of its fills)
+int32_t launch_update(lama_hip_ctx* c, const UpdatePlan& u, Timer& ray_timer)
+{
+    int32_t rc = !u.sequential ? launch_parallel_raycast(c, u) : u.guarded ? launch_allocation_phase(c, u, 1) : LAMA_HIP_OK;
+    if (rc) return rc;
+    if (u.sequential) hipLaunchKernelGGL(k_raycast, dim3(u.count), dim3(UM_BLOCK), 0, u.s, u.prm, u.d_pts, (int)u.n, c->d_tfs, (int)u.first);      // beam by beam
+    ray_timer.stop();
     HIPCHK(c, hipGetLastError());
-    {
-        Timer t = g ? Timer(c, g, 2) : Timer(c, &c->ctr.ms_brushfire, &c->ctr.launches_brushfire);
-        if (c->cfg.brushfire_mode == 1 && !g)     // opt-in parallel variant; whatever it leaves (qsizes != 0) falls through to the exact stages
-            hipLaunchKernelGGL(k_brushfire_canon, dim3(count), dim3(CN_BLOCK), 0, c->stream, prm, (int)first);
-        // stage 1: small LDS window, every particle; stage 2: big window, resumes particles whose queue outgrew stage 1
-        // (e.g. the first scan); stage 3: generic HBM-queue kernel for anything larger still
-        // few particles: CUs are idle, spend a helper wave per particle on the heap (see k_brushfire, TW)
-        const bool two_waves = c->cfg.brushfire_waves == 2 || (c->cfg.brushfire_waves == 0 && count <= BF_TW_MAX_PARTICLES);
-        c->ctr.brushfire_mode = c->cfg.brushfire_mode;
-        c->ctr.brushfire_waves = two_waves ? 2u : 1u;
-        const unsigned resume_grid = std::min<unsigned>(count, 256u);      // workgroups that walk the hand-over list (usually empty)
-        // the long chains are known before they start (k_bf_route): they go to the big-queue stage on a second stream, beside the
-        // first stage (which skips them), instead of outgrowing it half-way and waiting for it to end
-        const bool route = two_waves && count >= c->route_min_count && c->route_cap > 0;
-        if (two_waves) {
-            if (route) {
-                // The big-queue workgroups (84 KB of LDS each) must be placed BEFORE the first stage fills every CU's LDS, or they wait
-                // for a third of it to finish: their kernel follows k_bf_route directly in this stream, the first stage goes to the
-                // second stream behind an event -- the cross-queue signal is what makes it the later dispatch.
-                prm.heavy = c->d_heavy;
-                hipLaunchKernelGGL(k_bf_route, dim3(1), dim3(256), 0, c->stream, prm, (int)first, (int)count, c->route_min_events, c->route_percent, route_places(c, count));
-                HIPCHK(c, hipEventRecord(c->ev_route, c->stream));
-                hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(route_places(c, count)), dim3(2 * UM_BLOCK), 0, c->stream, prm, (int)first, 1);
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_route, 0));
-                // (round 6 measured the one-wave straight-line form here for a chip full of particles -- fewer instructions per pop in
-                // total, no barrier: brushfire 4.90 ms against 4.08 ms for the pair at 3000 particles, 3.0 against 1.86 ms at 300.  The
-                // pair stays; the one-wave form is what cfg.brushfire_waves = 1 selects.)
-                hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(count), dim3(2 * UM_BLOCK), 0, c->stream2, prm, (int)first, 0);
-                HIPCHK(c, hipEventRecord(c->ev_heavy, c->stream2));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_heavy, 0));
-            } else {
-                hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, true>), dim3(count), dim3(2 * UM_BLOCK), 0, s, prm, (int)first, 0);
-            }
-            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, true>), dim3(resume_grid), dim3(2 * UM_BLOCK), 0, s, prm, (int)first, 0);
-        } else {
-            hipLaunchKernelGGL((k_brushfire<LQ_SMALL, RQ_SMALL, false, false>), dim3(count), dim3(UM_BLOCK), 0, s, prm, (int)first, 0);
-            hipLaunchKernelGGL((k_brushfire<LQ_BIG, RQ_BIG, true, false>), dim3(resume_grid), dim3(UM_BLOCK), 0, s, prm, (int)first, 0);
-        }
-        if (early_lane) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_early, 0));
-        hipLaunchKernelGGL(k_brushfire_slow, dim3(count), dim3(UM_BLOCK), 0, s, prm, (int)first);
-        if (!g) c->early_ok = route && first == 0 && count == c->P;      // d_heavy now holds this update's routed particles (early lane included)
-        t.stop();
-    }
+    Timer t = Timer::of_update(c, u.timers, 2);
+    c->ctr.brushfire_mode = c->cfg.brushfire_mode; c->ctr.brushfire_waves = u.two_waves ? 2u : 1u;
+    rc = launch_brushfire(c, u);
+    if (rc) return rc;
+    t.stop();
     HIPCHK(c, hipGetLastError());
     return LAMA_HIP_OK;
+}
+
+int32_t run_update_maps(lama_hip_ctx* c, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count)
+{
+    int32_t rc = fit_window(c, mtf, first, count);
+    if (rc == LAMA_HIP_OK) rc = stage_scan_tfs(c, mtf, first, count, c->stream, nullptr);
+    if (rc) return rc;
+    Timer t = Timer::of_update(c, nullptr, 1);
+    const bool whole = first == 0 && count == c->P;      // hand-over counts and statistics are adjacent (ctx_create); a block leaves the others' statistics alone
+    (void)hipMemsetAsync(c->d_slow_n, 0, whole ? 32 + sizeof(uint64_t) * 4 * c->P : 32, c->stream);
+    if (!whole) (void)hipMemsetAsync(c->d_stats + 4 * (size_t)first, 0, sizeof(uint64_t) * 4 * count, c->stream);
+    int64_t probed = -1; rc = wrap_guard_probe(c, n, probed);
+    if (rc == LAMA_HIP_OK) rc = pregrow_unguarded(c, first, count);
+    if (rc) return rc;
+    const UpdatePlan u = plan_update(c, n, first, count, probed >= 0 && (uint64_t)probed + n >= 65536u);
+    note_update_begin(c, mtf, u, probed);
+    return launch_update(c, u, t);
 }
 
 
@@ -1400,6 +1427,16 @@ bool step_can_group(const lama_hip_ctx* c, uint32_t n)
            (uint64_t)c->visit_bound + n < 65536u;
 }
 
+// k_scan_match with the distance look-up that max_sqdist asks for; start poses as a launch argument (ptab, at most ARG_BLOCK) or from d_poses
+void launch_scan_match(lama_hip_ctx* c, const DevParams& prm, hipStream_t s, const double* d_pts, uint32_t n, const Affine& mtf, uint32_t first, uint32_t count, const lama_dev::PoseTable* ptab)
+{
+    const bool big = c->max_sqdist > (uint32_t)SM_LUT; const lama_dev::NoTable none;
+    if (ptab && big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, (int)first, *ptab);
+    else if (ptab) hipLaunchKernelGGL((k_scan_match<false, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, (int)first, *ptab);
+    else if (big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, (int)first, none);
+    else hipLaunchKernelGGL((k_scan_match<false, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, (int)first, none);
+}
+
 // scan match of the group's block from the poses in c->h_poses, then its block (results + status of its previous map update) on the
 // way to g.h_pack; g.ev_match says when it has arrived.  status_only: no scan match (drain_groups)
 int32_t queue_group_match(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affine& mtf, bool status_only)
@@ -1407,27 +1444,17 @@ int32_t queue_group_match(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affin
     const DevParams prm = group_params(c, g);
     // (launch arguments are plain values: the owners are not copied)
     hipStream_t s = g.s;
-    const double* const d_pts = g.d_pts;
-    uint32_t* const d_words = g.d_words;
-    uint8_t* const d_pack = g.d_pack;
+    uint32_t* const d_words = g.d_words; uint8_t* const d_pack = g.d_pack;
     const int first = (int)g.first, count = (int)g.count;
     // The step path: the predicted poses of a block of at most ARG_BLOCK particles are launch arguments -- no upload of the poses --, and
-    // k_pack_group clears what it has packed -- no fills in front of the ray-cast (run_update_maps).
+    // k_pack_group clears what it has packed -- a group's update needs no fills in front of its ray-cast.
     if (!status_only) {
         const bool by_value = g.count <= (uint32_t)lama_dev::ARG_BLOCK;
         lama_dev::PoseTable ptab = lama_dev::PoseTable();
         if (by_value) std::memcpy(ptab.v, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count);
         else HIPCHK(c, hipMemcpyAsync(c->d_poses + 4 * (size_t)g.first, &c->h_poses[4 * (size_t)g.first], sizeof(double) * 4 * g.count, hipMemcpyHostToDevice, s));
-        const bool big = c->max_sqdist > (uint32_t)SM_LUT;
-        const lama_dev::NoTable none;
         Timer t(c, &g, 0);
-        if (by_value) {
-            if (big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, ptab);
-            else hipLaunchKernelGGL((k_scan_match<false, lama_dev::PoseTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, ptab);
-        } else {
-            if (big) hipLaunchKernelGGL((k_scan_match<true, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, none);
-            else hipLaunchKernelGGL((k_scan_match<false, lama_dev::NoTable>), dim3(count), dim3(SM_BLOCK), 0, s, prm, d_pts, (int)n, mtf, c->d_loglik, c->d_iters, first, none);
-        }
+        launch_scan_match(c, prm, s, g.d_pts, n, mtf, g.first, g.count, by_value ? &ptab : nullptr);
         t.stop();
     }
     hipLaunchKernelGGL(k_pack_group, dim3(1), dim3(64), 0, s, prm, (const double*)c->d_loglik, (const int32_t*)c->d_iters, d_words, first, count, d_pack, status_only ? 0 : 1);
@@ -1468,26 +1495,19 @@ int32_t recover_group(lama_hip_ctx* c, StepGroup& g, int32_t e)
     return rc;
 }
 
-// The block of group g has arrived: the status of its previous map update (if one was queued) goes into the host mirrors and the
-// counters.  Returns the group's error word through `e`.
-void collect_group_status(lama_hip_ctx* c, StepGroup& g, int32_t& e)
+// The block of group g has arrived: the status of its previous map update, if one was queued (returned; no longer queued then), goes
+// into the host mirrors and the counters.  The group's error word through `e`.
+bool collect_group_status(lama_hip_ctx* c, StepGroup& g, int32_t& e)
 {
-    const GroupPack L(g.count);
-    const uint8_t* b = g.h_pack.data();
-    uint32_t w[16];
-    std::memcpy(w, b + L.words, sizeof(w));
-    e = (int32_t)w[0];
+    const GroupPack L(g.count); const uint8_t* const b = g.h_pack.data();
+    const StatusView v{b + L.words, b + L.words + 2 * sizeof(uint32_t), b + L.stats, b + L.guard, b + L.counts, g.first, g.count};
+    e = v.error();
     take_group_timers(c, g);
-    if (!g.maps_queued) return;
-    const uint32_t* sn = w + 2;
-    c->ctr.brushfire_handovers += sn[0]; c->ctr.replay_handovers += sn[1] + sn[3]; c->ctr.brushfire_routed += sn[2] + sn[4]; c->ctr.brushfire_early += sn[4];
-    c->h_guard.resize(c->P);
-    std::memcpy(&c->h_guard[g.first], b + L.guard, sizeof(uint32_t) * g.count);
-    std::memcpy(&c->h_counts[2 * (size_t)g.first], b + L.counts, sizeof(int32_t) * 2 * g.count);
-    if (e != 0) return;
-    const uint64_t* st = reinterpret_cast<const uint64_t*>(b + L.stats);
-    for (uint32_t i = 0; i < g.count; ++i) { c->ctr.ray_cells += st[4 * i + 2]; c->ctr.bf_cells += st[4 * i + 3]; c->h_chain[g.first + i] = st[4 * i + 3]; }
-    c->chain_dirty = true;
+    if (!g.maps_queued) return false;
+    apply_update_status(c, v, g.first, g.count, c->h_chain.data());     // (the step's longest chain is pool-wide: flush_step_figures)
+    if (e == 0) c->chain_dirty = true;
+    g.maps_queued = false;
+    return true;
 }
 
 // a non-zero error word of group g (of its previous map update when one was queued, else of its scan match): what
@@ -1503,13 +1523,6 @@ int32_t handle_group_error(lama_hip_ctx* c, StepGroup& g, int32_t e, bool of_map
     if (rc) return rc;
     if (e & (ERR_DM_CAP | ERR_OCC_CAP)) { rc = clamp_counts(c, true); if (rc) return rc; }
     return device_error_result(c, e);
-}
-
-void refresh_patch_totals(lama_hip_ctx* c)
-{
-    uint64_t dm = 0, oc = 0;
-    for (uint32_t p = 0; p < c->P; ++p) { dm += c->h_counts[2 * p]; oc += c->h_counts[2 * p + 1]; }
-    c->ctr.dm_patches = dm; c->ctr.occ_patches = oc;
 }
 
 // Collects the status of every group's queued map update (one more block per group, one wait per stream) and leaves the device idle:
@@ -1529,8 +1542,7 @@ int32_t drain_groups(lama_hip_ctx* c)
         StepGroup& g = c->grp[k];
         if (!g.count || !g.maps_queued) continue;
         int32_t e = 0;
-        collect_group_status(c, g, e);
-        g.maps_queued = false;
+        (void)collect_group_status(c, g, e);
         if (e == 0) continue;
         const int32_t re = handle_group_error(c, g, e, true);
         if (re && rc == LAMA_HIP_OK) { rc = re; first_msg = c->error; }
@@ -1547,9 +1559,7 @@ int32_t finish_group_step(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affin
 {
     const size_t o = 4 * (size_t)g.first, m = 4 * (size_t)g.count;
     int32_t e = 0;
-    const bool had_maps = g.maps_queued;
-    collect_group_status(c, g, e);
-    g.maps_queued = false;
+    const bool had_maps = collect_group_status(c, g, e);
     if (e != 0) {
         int32_t rc = handle_group_error(c, g, e, had_maps);
         if (rc) { if (had_maps) c->error = "deferred from the previous map update: " + c->error; return rc; }
@@ -1558,7 +1568,7 @@ int32_t finish_group_step(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affin
         rc = queue_group_match(c, g, n, mtf, false);
         if (rc) return rc;
         HIPCHK(c, hipStreamSynchronize(g.s));
-        collect_group_status(c, g, e);
+        (void)collect_group_status(c, g, e);
         if (e != 0) { HIPCHK(c, hipMemsetAsync(g.d_words, 0, sizeof(int32_t), g.s)); return device_error_result(c, e); }
     } else if (had_maps) {
         const int32_t rc = grow_arenas(c, g.first, g.count);         // head room for the next update (waits for the groups only when a region moves)
@@ -1579,10 +1589,13 @@ int32_t finish_group_step(lama_hip_ctx* c, StepGroup& g, uint32_t n, const Affin
     if (rc) return rc;
     g.upd_poses.assign(c->h_poses.data() + o, c->h_poses.data() + o + m);
     g.upd_mtf = mtf; g.upd_slot = c->scan_slot; g.upd_n = n; g.upd_reach = c->scan_reach;
-    rc = run_update_maps(c, n, mtf, g.first, g.count, &g);
+    UpdatePlan u = plan_update(c, n, g.first, g.count, false, &g);
+    rc = stage_scan_tfs(c, mtf, g.first, g.count, g.s, u.tf_by_value ? &u.tab : nullptr);
     if (rc) return rc;
-    g.maps_queued = true;
-    return LAMA_HIP_OK;
+    Timer t = Timer::of_update(c, &g, 1);
+    rc = launch_update(c, u, t);
+    g.maps_queued = rc == LAMA_HIP_OK;
+    return rc;
 }
 
 } // namespace
@@ -1846,11 +1859,9 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
     if (rc) return rc;
     const Affine mtf = moving_tf(origin3, quat);
     DevParams prm = make_params(c);
-    const lama_dev::NoTable none;                                   // (the poses are in d_poses)
     {
         Timer t(c, &c->ctr.ms_scan_match, &c->ctr.launches_scan_match);
-        if (c->max_sqdist > (uint32_t)SM_LUT) hipLaunchKernelGGL((k_scan_match<true, lama_dev::NoTable>), dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0, none);
-        else hipLaunchKernelGGL((k_scan_match<false, lama_dev::NoTable>), dim3(c->P), dim3(SM_BLOCK), 0, c->stream, prm, c->d_pts, (int)n, mtf, c->d_loglik, c->d_iters, 0, none);
+        launch_scan_match(c, prm, c->stream, c->d_pts, n, mtf, 0, c->P, nullptr);      // (the poses are in d_poses)
         t.stop();
     }
     HIPCHK(c, hipGetLastError());
@@ -1871,7 +1882,7 @@ int32_t lama_hip_pf_scan_match(lama_hip_ctx* c, const double* pts, uint32_t n, c
 int32_t lama_hip_pf_resample(lama_hip_ctx* c, const int32_t* sample_idx)
 {
     if (!c || !sample_idx) return LAMA_HIP_E_INVALID;
-    if (c->poisoned) return fail(c, LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue");
+    if (c->poisoned) return refuse_poisoned(c);
     if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_pf_resample before lama_hip_pf_init");
     for (uint32_t i = 0; i < c->P; ++i)
         if (sample_idx[i] < 0 || (uint32_t)sample_idx[i] >= c->P) return fail(c, LAMA_HIP_E_INVALID, "sample_idx out of range");
@@ -1923,7 +1934,7 @@ int32_t lama_hip_pf_match_and_map(lama_hip_ctx* c, const double* pts, uint32_t n
                                   const double* poses_in, double* poses_out, double* loglik_out, int32_t* iters_out)
 {
     if (!c || !pts || !poses_in || n == 0) return LAMA_HIP_E_INVALID;
-    if (c->poisoned) return fail(c, LAMA_HIP_E_STATE, "the context ran out of device memory in the middle of a resample and cannot continue");
+    if (c->poisoned) return refuse_poisoned(c);
     if (!c->initialised) return fail(c, LAMA_HIP_E_STATE, "lama_hip_pf_match_and_map before lama_hip_pf_init");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     // A step that could not be grouped (below) has left its map update queued on the main stream: its status is collected here, and the
@@ -1944,8 +1955,7 @@ int32_t lama_hip_pf_match_and_map(lama_hip_ctx* c, const double* pts, uint32_t n
     hp.resize((size_t)3 * n);
     std::memcpy(hp.data(), pts, sizeof(double) * 3 * n);
     double r2 = 0.0;
-    for (uint32_t i = 0; i < n; ++i) r2 = std::max(r2, pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2]);
-    if (!std::isfinite(r2)) { c->scan_slot ^= 1u; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
+    if (!scan_reach2(pts, n, false, r2)) { c->scan_slot ^= 1u; return fail(c, LAMA_HIP_E_INVALID, "the scan holds a non-finite point (filter NaN / inf ranges before the update, as iris_lama_ros does)"); }
     c->scan_reach = std::sqrt(r2);
     c->last_n = 0;                                                  // (the main stream's scan buffer is not this scan)
     const Affine mtf = moving_tf(origin3, quat);
@@ -1963,10 +1973,8 @@ int32_t lama_hip_pf_match_and_map(lama_hip_ctx* c, const double* pts, uint32_t n
         if (rc) return rc;
         left |= 1u << k;
     }
-    // the scan's visits count once for the pool (the wrap guard's bound), whichever group ray-casts first
-    c->visit_bound = (uint32_t)std::min<uint64_t>((uint64_t)c->visit_bound + n, 65535u);
-    c->ctr.parallel_raycast_scans += 1;
-    c->last_guarded = true;
+    UpdatePlan step; step.n = n; step.count = c->P;                // (once for the pool; the plan's defaults are what every group's plan says)
+    note_update_begin(c, mtf, step, -1);
     // the groups are taken as their blocks arrive, not in a fixed order: the one whose chains were short goes on first
     while (left) {
         for (uint32_t k = 0; k < c->step_groups; ++k) {
@@ -1988,9 +1996,7 @@ int32_t lama_hip_pf_match_and_map(lama_hip_ctx* c, const double* pts, uint32_t n
                     if (!(left & (1u << j))) continue;
                     StepGroup& o = c->grp[j];
                     int32_t e = 0;
-                    const bool had_maps = o.maps_queued;
-                    collect_group_status(c, o, e);
-                    o.maps_queued = false;
+                    const bool had_maps = collect_group_status(c, o, e);
                     if (e != 0) (void)handle_group_error(c, o, e, had_maps);
                 }
                 flush_step_figures(c);
@@ -2764,7 +2770,7 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
     ENTER(c);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     {   // the window must hold the listed cells and what the brushfire reaches from them (it is centred / moved / grown for that)
-        const int64_t r = (int64_t)(((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u);
+        const int64_t r = (int64_t)guard_radius(c);
         int64_t x0 = INT64_MAX, x1 = INT64_MIN, y0 = INT64_MAX, y1 = INT64_MIN;
         for (uint32_t i = 0; i < n; ++i) {
             const int64_t px = cells_xy[2 * i] >> 5, py = cells_xy[2 * i + 1] >> 5;
@@ -2775,7 +2781,7 @@ int32_t lama_hip_map_add_obstacles(lama_hip_ctx* c, uint32_t particle, const uin
     }
     { const int32_t rf = start_without_first_scan(c); if (rf) return rf; }
     {   // every distance-map patch this call can allocate lies within guard_r patches of a listed cell's patch: make room first
-        const int r = (int)(((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u);
+        const int r = (int)guard_radius(c);
         std::vector<uint64_t> keys;
         keys.reserve((size_t)n);
         uint64_t last = ~0ull;
@@ -2857,8 +2863,8 @@ int32_t lama_hip_map_integrate_scans(lama_hip_ctx* c, uint32_t particle, uint32_
     HIPCHK(c, hipMemcpyAsync(c->d_mb_pts, pts + 3 * (size_t)offs[0], sizeof(double) * 3 * total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_mb_tfs, c->h_mb_tfs.data(), sizeof(double) * 12 * K, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_mb_offs, c->h_mb_offs.data(), sizeof(uint32_t) * ((size_t)K + 1), hipMemcpyHostToDevice, c->stream));
-    DevParams prm = make_params(c);
-    prm.trunc_ray = 0.0; prm.trunc_range = 0.0;                     // generateOccupancyMap truncates nothing
+    auto untruncated_params = [c]() { DevParams p = make_params(c); p.trunc_ray = 0.0; p.trunc_range = 0.0; return p; };      // generateOccupancyMap truncates nothing
+    DevParams prm = untruncated_params();
     const unsigned ray_blocks = (total + 255u) / 256u;
     MbRay* const d_rays = c->d_mb_rays;
     {
@@ -2890,8 +2896,7 @@ int32_t lama_hip_map_integrate_scans(lama_hip_ctx* c, uint32_t particle, uint32_
     const uint32_t bx0 = bnd.x0 - (c->wx0 >> 5), by0 = bnd.y0 - (c->wy0 >> 5), bw = bnd.x1 - bnd.x0 + 1u, bh = bnd.y1 - bnd.y0 + 1u, nb = bw * bh;
     if (bx0 + bw > c->W || by0 + bh > c->W) { resolve_timers(c); return fail(c, LAMA_HIP_E_WINDOW, "the key scans fell outside the device window"); }
     HIPCHK(c, c->d_mb_table.grow(nb)); HIPCHK(c, c->d_mb_off.grow((size_t)nb + 1)); HIPCHK(c, c->d_mb_list.grow(nb)); HIPCHK(c, c->d_mb_slot.grow(nb));
-    prm = make_params(c);
-    prm.trunc_ray = 0.0; prm.trunc_range = 0.0;
+    prm = untruncated_params();
     uint32_t* const d_table = c->d_mb_table; uint32_t* const d_off = c->d_mb_off; uint32_t* const d_list = c->d_mb_list; int32_t* const d_slot = c->d_mb_slot;
     HIPCHK(c, hipMemsetAsync(d_table, 0, sizeof(uint32_t) * nb, c->stream));
     {
@@ -2910,8 +2915,7 @@ int32_t lama_hip_map_integrate_scans(lama_hip_ctx* c, uint32_t particle, uint32_
     if (want > c->h_part[particle].occ_cap) {
         const int32_t rg = set_capacities(c, {CapRequest{particle, c->h_part[particle].dm_cap, want_capacity(c->floor_occ, (uint32_t)want, 0u)}});
         if (rg) { resolve_timers(c); return rg; }
-        prm = make_params(c);
-        prm.trunc_ray = 0.0; prm.trunc_range = 0.0;
+        prm = untruncated_params();
     }
     HIPCHK(c, c->d_mb_bins.grow(meta.items, (size_t)1 << 16));
     uint32_t* const d_bins = c->d_mb_bins;
@@ -3213,12 +3217,8 @@ int32_t lama_hip_match_search_lattice(lama_hip_ctx* c, uint32_t particle, const 
     for (int k = 0; quat && k < 4; ++k) if (!std::isfinite(quat[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the sensor orientation is not finite");
     if (!std::isfinite(wx0) || !std::isfinite(wy0)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the lattice origin is not finite");
     for (size_t k = 0; k < 2 * (size_t)H; ++k) if (!std::isfinite(headings_cs[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a heading entry is not finite");
-    double r2 = 0.0, nan_acc = 0.0;                               // (std::max drops a NaN: the sum of products with zero keeps it)
-    for (size_t i = 0; i < n; ++i) {
-        const double d2 = pts[3 * i] * pts[3 * i] + pts[3 * i + 1] * pts[3 * i + 1] + pts[3 * i + 2] * pts[3 * i + 2];
-        r2 = std::max(r2, d2); nan_acc += d2 * 0.0;
-    }
-    if (!std::isfinite(r2) || !(nan_acc == 0.0)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)");
+    double r2 = 0.0;
+    if (!scan_reach2(pts, n, true, r2)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)");
     // no cell coordinate of any node may leave [0, 2^32): per heading, the hits lie within |row of R| * reach of the transform's
     // translation, and the far corner adds cell_step * (nx - 1, ny - 1) cells
     const Affine mtf = moving_tf(origin3, quat);

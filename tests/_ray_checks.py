@@ -203,16 +203,22 @@ def check_third_axis_rebuild(F):
     run_rebuild(F, poses, scans, origins, quats, "third axis")
 
 
+LO_DELTAS = [(0, 0, 7), (0, 0, 1), (3, 2, 9), (5, 3, 6), (0, 0, 40), (12, 0, 16), (3, 2, 0), (-4, 7, 0)]
+
+
 def check_third_axis_lidar_odometry(F):
     """One scan through LidarOdometry2D's map update: the last-metre ray rule (ray_rule = 1) and the log-odds cells
     (occupancy_policy = 1), which live in k_raycast only.  The rule starts a beam of a metre or more one metre before its hit, so
     the long beams are (0, 0, 40): straight up, 20 cells; (12, 0, 16): a 3-4-5 beam of exactly a metre in x and z."""
-    deltas = [(0, 0, 7), (0, 0, 1), (3, 2, 9), (5, 3, 6), (0, 0, 40), (12, 0, 16), (3, 2, 0), (-4, 7, 0)]
-    pts = lattice(deltas)
-    assert_deltas(O.se2(0.0, 0.0, 0.0), pts, deltas, "lidar odometry")
+    pts = lattice(LO_DELTAS)
+    assert_deltas(O.se2(0.0, 0.0, 0.0), pts, LO_DELTAS, "lidar odometry")
     o, h = O.LidarOdometry(), F.LidarOdometry2D()
     assert o.update(pts, 0.0) == h.update(pts, 0.0)
-    ctx = h.hip_context()
+    assert_lidar_odometry_maps(F, h.hip_context(), o)
+    h.close()
+
+
+def assert_lidar_odometry_maps(F, ctx, o):
     assert ctx.counters()["sequential_raycast_scans"] == 1
     assert_maps_equal(ctx.download_map(0, F.MAP_DISTANCE), o.dm().dump(), DM_FIELDS, "lidar odometry: dm")
     got, ref = ctx.download_map(0, F.MAP_OCCUPANCY), o.occ().dump()
@@ -220,7 +226,21 @@ def check_third_axis_lidar_odometry(F):
     for pid in ref:
         assert np.array_equal(np.ascontiguousarray(got[pid][0]).view(np.float32).reshape(-1), ref[pid][0]["prob"]), pid
         assert np.array_equal(got[pid][1], ref[pid][1]), pid
-    h.close()
+
+
+def check_third_axis_lidar_odometry_context(F):
+    """The same scan through a one-particle context configured as LidarOdometry2D configures its own, but with regions of 8 patches:
+    the update runs unguarded (no allocation phase under this ray rule), so the regions are grown to everything a scan of this
+    reach can touch before the first launch.  (The host class is not loaded here: the lane simulator can run this form.)"""
+    pts = lattice(LO_DELTAS)
+    o = O.LidarOdometry()
+    assert o.update(pts, 0.0)
+    ctx = F.HipContext(F.default_cfg(particles=1, device=0, l2_max=1.0, occupancy_policy=1, ray_rule=1, dm_patch_capacity=8,
+                                     occ_patch_capacity=8, queue_capacity=1 << 18))
+    ctx.init(pts, O.se2(0.0, 0.0, 0.0))
+    assert ctx.counters()["arena_growths"] >= 1
+    assert_lidar_odometry_maps(F, ctx, o)
+    ctx.close()
 
 
 # ------------------------------------------------------------------------------------------------ 2. truncation

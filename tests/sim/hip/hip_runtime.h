@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <cstdio>
 
 #include "../wave_sim.hpp"
 
@@ -71,10 +72,42 @@ constexpr hipError_t hipSuccess = 0;
 constexpr hipError_t hipErrorOutOfMemory = 2;
 typedef struct wsim_stream* hipStream_t;
 typedef struct wsim_event* hipEvent_t;
-struct wsim_stream { int dummy; };
-struct wsim_event { int dummy; };
+struct wsim_stream { int ord; };       // ord: the trace's name for it (below), -1 until it first appears there
+struct wsim_event { int ord; };
 enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3, hipMemcpyDefault = 4 };
 constexpr unsigned hipHostMallocDefault = 0;
+
+// LAMA_SIM_TRACE=<file>: what the host asks of the runtime, one line per request in program order (appended to the file) -- kernel
+// launches with grid, block, dynamic LDS, argument bytes and stream, event records and waits, fills and copies with byte count, direction and stream,
+// stream synchronisations.  Streams and events are named by the order in which they first appear (s0, s1, ...; the null stream is
+// s-), never by address: two builds of the host code ask for the same schedule exactly when their traces are equal line for line.
+namespace wsim {
+struct Trace {
+    std::FILE* f = nullptr;
+    int streams = 0, events = 0;
+    Trace() { const char* p = std::getenv("LAMA_SIM_TRACE"); if (p && *p) f = std::fopen(p, "a"); if (f) std::setvbuf(f, nullptr, _IOLBF, 0); }
+    ~Trace() { if (f) std::fclose(f); }
+};
+inline Trace& trace() { static Trace t; return t; }
+inline std::string trace_stream(hipStream_t s) { if (!s) return "s-"; if (s->ord < 0) s->ord = trace().streams++; return "s" + std::to_string(s->ord); }
+inline std::string trace_event(hipEvent_t e) { if (!e) return "e-"; if (e->ord < 0) e->ord = trace().events++; return "e" + std::to_string(e->ord); }
+// (args: the bytes of the kernel's parameters -- it tells apart the instantiations of a kernel that a helper launches under one
+// spelling, e.g. with a table of transforms as a parameter or with the empty NoTable)
+template <class... P> constexpr size_t param_bytes(void (*)(P...)) { return (sizeof(P) + ... + (size_t)0); }
+inline void trace_launch(const char* kernel, dim3s g, dim3s b, size_t lds, hipStream_t s, size_t args)
+{
+    if (trace().f) std::fprintf(trace().f, "launch %s grid %u,%u,%u block %u,%u,%u lds %zu args %zu %s\n", kernel, g.x, g.y, g.z, b.x, b.y, b.z, lds, args, trace_stream(s).c_str());
+}
+inline void trace_copy(const char* what, size_t n, int kind_or_value, hipStream_t s, bool async)
+{
+    if (trace().f) std::fprintf(trace().f, "%s %zu %d %s\n", what, n, kind_or_value, async ? trace_stream(s).c_str() : "blocking");
+}
+inline void trace_event_op(const char* what, hipEvent_t e, hipStream_t s)
+{
+    if (trace().f) std::fprintf(trace().f, "%s %s %s\n", what, trace_event(e).c_str(), trace_stream(s).c_str());
+}
+inline void trace_sync(hipStream_t s) { if (trace().f) std::fprintf(trace().f, "sync %s\n", trace_stream(s).c_str()); }
+} // namespace wsim
 
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "simulated HIP error"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -86,13 +119,14 @@ template <class T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)std::
 template <class T> inline hipError_t hipHostMalloc(T** p, size_t n, unsigned = 0) { *p = (T*)std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
-inline hipError_t hipMemset(void* p, int v, size_t n) { std::memset(p, v, n); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t = nullptr) { std::memset(p, v, n); return hipSuccess; }
-inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memmove(d, s, n); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { std::memmove(d, s, n); return hipSuccess; }
-inline hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t = nullptr) { std::memmove(d, s, n); return hipSuccess; }
-inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t = nullptr)
+inline hipError_t hipMemset(void* p, int v, size_t n) { wsim::trace_copy("memset", n, v, nullptr, false); std::memset(p, v, n); return hipSuccess; }
+inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t s = nullptr) { wsim::trace_copy("memset", n, v, s, true); std::memset(p, v, n); return hipSuccess; }
+inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) { wsim::trace_copy("memcpy", n, (int)k, nullptr, false); std::memmove(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) { wsim::trace_copy("memcpy", n, (int)k, st, true); std::memmove(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t st = nullptr) { wsim::trace_copy("memcpy_peer", n, (int)hipMemcpyDeviceToDevice, st, true); std::memmove(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind k, hipStream_t st = nullptr)
 {
+    wsim::trace_copy("memcpy2d", width * height, (int)k, st, true);
     for (size_t r = 0; r < height; ++r) std::memmove((char*)d + r * dpitch, (const char*)s + r * spitch, width);
     return hipSuccess;
 }
@@ -100,22 +134,23 @@ inline hipError_t hipMemGetInfo(size_t* free_b, size_t* total_b) { *free_b = (si
 inline hipError_t hipDeviceCanAccessPeer(int* can, int, int) { *can = 1; return hipSuccess; }
 inline hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
 constexpr hipError_t hipErrorPeerAccessAlreadyEnabled = 704;
-inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new wsim_stream{0}; return hipSuccess; }
+inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new wsim_stream{-1}; return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new wsim_event{0}; return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t s) { wsim::trace_sync(s); return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new wsim_event{-1}; return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t = nullptr) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { wsim::trace_event_op("record", e, s); return hipSuccess; }
 constexpr unsigned hipEventDisableTiming = 2;
 struct hipDeviceProp_t { int multiProcessorCount = 256; };
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { *p = hipDeviceProp_t{}; return hipSuccess; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }   // launches run to completion in program order here
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { wsim::trace_event_op("wait", e, s); return hipSuccess; }   // launches run to completion in program order here
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.0f; return hipSuccess; }
 
 // kernel launch: every argument is copied once (as the device would receive it), every thread calls the kernel with the copies
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    wsim::launch_named(#kernel, wsim::dim3s(grid), wsim::dim3s(block), [=]() { (kernel)(__VA_ARGS__); })
+    (wsim::trace_launch(#kernel, wsim::dim3s(grid), wsim::dim3s(block), (size_t)(shmem), (stream), wsim::param_bytes(kernel)), \
+     wsim::launch_named(#kernel, wsim::dim3s(grid), wsim::dim3s(block), [=]() { (kernel)(__VA_ARGS__); }))
 
 // ---- small vector types / bit casts / scoped atomic loads ----------------------------------------------------------------------
 struct alignas(16) uint4 { unsigned x, y, z, w; };

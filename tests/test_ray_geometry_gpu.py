@@ -34,6 +34,10 @@ def test_third_axis_under_the_lidar_odometry_ray_rule_and_log_odds_cells(F):
     RC.check_third_axis_lidar_odometry(F)
 
 
+def test_third_axis_in_an_unguarded_context_with_the_lidar_odometry_ray_rule(F):
+    RC.check_third_axis_lidar_odometry_context(F)
+
+
 @pytest.mark.parametrize("form", RC.FORMS)
 @pytest.mark.parametrize("name", sorted(RC.TRUNCATIONS))
 def test_truncation_limit_against_the_length_of_a_3_4_5_beam(F, name, form):

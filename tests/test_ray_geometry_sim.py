@@ -28,6 +28,10 @@ def test_third_axis_sets_the_step_count(Fsim, form):
     RC.check_third_axis_through_the_transform_pf(Fsim, form, l2_max=L2_MAX)
 
 
+def test_third_axis_in_an_unguarded_context_with_the_lidar_odometry_ray_rule(Fsim):
+    RC.check_third_axis_lidar_odometry_context(Fsim)
+
+
 @needs_reference
 def test_third_axis_in_the_map_rebuild(Fsim):
     RC.check_third_axis_rebuild(Fsim)
