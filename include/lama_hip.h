@@ -81,7 +81,7 @@ typedef struct lama_hip_cfg {
                                     asked for and the update is run again.  LAMA_HIP_E_CAPACITY remains for the hard limit of 32767
                                     patches per particle and map, and for a device that has no memory left for another pool chunk */
     uint32_t occ_patch_capacity; /* smallest occupancy region a particle gets (default 128)      */
-    uint32_t queue_capacity;     /* brushfire queue entries per particle (default 32768)          */
+    uint32_t queue_capacity;     /* brushfire queue entries per particle (default 32768, at least 8192; brushfire_mode = 1: see there) */
     uint32_t profile;            /* !=0: bracket every kernel with hipEvents (lama_hip_get_counters) */
     uint32_t active_capacity;    /* parallel ray-cast: max. order-sensitive cell visits per particle and scan (default 8192) */
     uint32_t sequential_raycast; /* ray-cast kernels: 0 / 2 = parallel form (default), 1 = beam-sequential form; bit-identical */
@@ -90,7 +90,17 @@ typedef struct lama_hip_cfg {
                                         the measured logs, obstacle offsets of tie cells -- and, once in millions of cells, a
                                         distance -- may differ).  NOT bit-identical: only a caller that sets
                                         this field gets it (no environment variable selects it) and lama_hip_get_counters
-                                        reports the mode that ran.  Other values are rejected. */
+                                        reports the mode that ran.  Other values are rejected.
+                                        Limits of mode 1 (lama_brushfire_canon.h).  A particle's update is left, untouched, to
+                                        the exact kernels -- the result is then the exact one -- when the map's reach is above
+                                        32 cells (max_sqdist > 1024; always in liblama_hip_wide.so) or when one scan removes or
+                                        adds more obstacle cells than queue_capacity / 2.  Its LDS table of 4096 cells does NOT
+                                        limit the cells of a level or of a raise round: larger ones are worked in passes.
+                                        queue_capacity bounds the cells ONE update lowers (the pending list is append-only; for
+                                        the exact kernels it bounds the front at its widest): beyond it, and in the unlikely
+                                        case that one pass's class of 8 x 8 blocks alone holds more than 4096 distinct cells,
+                                        the update ends with LAMA_HIP_E_CAPACITY after cells have been modified, as a full
+                                        queue of the exact kernels does. */
     uint32_t brushfire_waves;    /* exact brushfire: 0 / 2 = a helper wave per particle owns the heap (default), 1 = one wave per
                                     particle; bit-identical */
     uint32_t occupancy_policy;   /* cell policy of the occupancy map: 0 = FrequencyOccupancyMap {uint16 occupied, uint16 visited}

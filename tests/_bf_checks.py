@@ -170,9 +170,11 @@ class EventRun:
                     out.append(("remove", self.rel(*key)))
         return out
 
-    def scan(self, sensor, deltas, expect, what=""):
+    def scan(self, sensor, deltas, expect, what="", exact=True):
         """one scan from the cell `sensor` (relative to the base) with the beams `deltas`; `expect`: the ordered events, one list
-        for all particles or a list per particle -> (oracle stats delta per particle, device counter delta)"""
+        for all particles or a list per particle -> (oracle stats delta per particle, device counter delta).  exact=False
+        (tests/_bf_canon_checks.py: cfg.brushfire_mode = 1) leaves out the two assertions that hold for the exact kernels only:
+        the form of the first stage, and bf_cells == pops (the canonical kernel does not pop a cell's duplicates again)."""
         if not self.uploaded:
             self.upload()
         pose = RC.sensor(self.base[0] + sensor[0], self.base[1] + sensor[1])
@@ -191,9 +193,9 @@ class EventRun:
         st = [stats_delta(self.pf.dm(q).stats(), before[q]) for q in range(self.P)]
         dc = {k: c1[k] - c0[k] for k in ("bf_cells", "brushfire_handovers", "brushfire_routed", "brushfire_early")}
         dc["brushfire_waves"] = c1["brushfire_waves"]
-        assert dc["brushfire_waves"] == self.waves, (self.what, what, dc)
+        assert not exact or dc["brushfire_waves"] == self.waves, (self.what, what, dc)
         self.compare(what)
-        assert dc["bf_cells"] == sum(s["pops"] for s in st), (self.what, what, dc, [s["pops"] for s in st])
+        assert not exact or dc["bf_cells"] == sum(s["pops"] for s in st), (self.what, what, dc, [s["pops"] for s in st])
         return st, dc
 
     def compare(self, what):

@@ -237,6 +237,13 @@ class DM(_MapBase):
     def max_sqdist(self):
         return lib().orc_dm_max_sqdist(self.h)
 
+    def set_canonical(self, on=True):
+        """this map's later update() calls run update_canonical() (NOT the reference's tie order): the checker of cfg.brushfire_mode = 1"""
+        L = lib()
+        L.orc_dm_set_canonical.restype = None
+        L.orc_dm_set_canonical.argtypes = [C.c_void_p, C.c_int]
+        L.orc_dm_set_canonical(self.h, 1 if on else 0)
+
     def distance_cell(self, x, y, z=0):
         return lib().orc_dm_distance_cell(self.h, x, y, z)
 

@@ -43,7 +43,7 @@ inline wsim_tidx wsim_thread_idx() { const wsim::Block* b = wsim::blk(); const u
 #define __builtin_amdgcn_fence(...) ((void)__ballot(true))
 #define __builtin_amdgcn_s_sleep(n) wsim::yield()
 #define __builtin_readcyclecounter() wsim::clock()
-#define __syncthreads() wsim::syncthreads()
+#define __syncthreads() wsim::syncthreads(__LINE__)
 #define __threadfence() ((void)0)
 #define __threadfence_block() ((void)0)
 

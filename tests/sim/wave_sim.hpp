@@ -13,6 +13,7 @@
 //     through atomics / a spin on another workgroup's directory allocation, which cannot happen when workgroups are serial);
 //   * a wave operation must be reached by ALL live lanes of the wave at the same call site (wave-uniform control flow around
 //     cross-lane operations -- the style the kernels are written in); a rendezvous at two different call sites is reported;
+//   * the same holds for the workgroup barrier and the live lanes of ONE wave (syncthreads below); waves may differ;
 //   * lanes that returned from the kernel no longer take part (ballot bit 0, reading their registers is an error);
 //   * atomics are plain read-modify-writes (fibers are cooperative: no preemption).
 #pragma once
@@ -48,6 +49,9 @@ struct Wave {
     uint64_t my_gen[WAVE];         // generation of the rendezvous the lane last took part in
     int lane_site[WAVE];           // last rendezvous each lane arrived at (diagnostics)
     uint64_t lane_count[WAVE];     // rendezvous each lane has taken part in
+    int bar_site = 0;              // workgroup barrier: the call site from which this wave's first lane arrived at the barrier in progress
+    int bar_lane = 0;              // ... and that lane
+    uint64_t bar_round = 0;        // ... barrier generation + 1 of that arrival (0: none yet)
 };
 
 // A fiber switch.  glibc's swapcontext saves and restores the signal mask -- a system call per switch, and a workgroup of the
@@ -227,9 +231,22 @@ inline int dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bou
     return (int)(uint32_t)(w.dep[par][from] == w.my_gen[l] + 1 ? w.in[par][from] : 0ull);
 }
 
-inline void syncthreads()
+// The workgroup barrier.  The hardware only counts arrivals, and so did this function until a kernel ran a whole launch with one
+// fiber a barrier-set out of step (it had read a shared word before the store that the others saw, skipped a loop body and its
+// barriers, and met the others at the NEXT barrier each time).  A wave has one instruction stream: its lanes cannot wait at two
+// barriers at once, so lanes of ONE wave that arrive at a barrier from different call sites (source lines) are reported, as they
+// are at a wave operation.  Different WAVES may meet from different call sites -- the brushfire's helper wave and main wave do so on
+// purpose (lama_kernels.h: S0, F) --, which is why the check is per wave and not per workgroup.
+inline void syncthreads(int site)
 {
     Block* b = blk();
+    Wave& w = wave();
+    if (w.bar_round != b->bar_gen + 1) { w.bar_round = b->bar_gen + 1; w.bar_site = site; w.bar_lane = lane(); }
+    else if (w.bar_site != site) {
+        std::fprintf(stderr, "wave_sim: lanes of one wave met at different workgroup barriers: lane %d waits at source line %d, lane %d arrives from line %d -- one of them is out of step\n",
+                     w.bar_lane, w.bar_site, lane(), site);
+        die("divergent barrier");
+    }
     ++b->bar_arrived;
     ++b->progress;
     if (b->bar_arrived == b->bar_live) { b->bar_arrived = 0; ++b->bar_gen; }
@@ -279,7 +296,7 @@ inline void launch(dim3s grid, dim3s block, std::function<void()> body)
     for (unsigned by = 0; by < grid.y; ++by)
     for (unsigned bx = 0; bx < grid.x; ++bx) {
         b.bidx = dim3s(bx, by, bz);
-        for (auto& w : b.waves) { w.live = 0; w.arrived = 0; w.gen = 0; std::memset(w.alive, 0, sizeof(w.alive)); std::memset(w.lane_site, 0, sizeof(w.lane_site)); std::memset(w.dep, 0, sizeof(w.dep)); std::memset(w.lane_count, 0, sizeof(w.lane_count)); }
+        for (auto& w : b.waves) { w.live = 0; w.arrived = 0; w.gen = 0; w.bar_round = 0; std::memset(w.alive, 0, sizeof(w.alive)); std::memset(w.lane_site, 0, sizeof(w.lane_site)); std::memset(w.dep, 0, sizeof(w.dep)); std::memset(w.lane_count, 0, sizeof(w.lane_count)); }
         for (unsigned t = 0; t < b.nthreads; ++t) {
             Fiber& f = b.fibers[t];
             f.tid = t; f.done = false; f.stack = pool[t];
