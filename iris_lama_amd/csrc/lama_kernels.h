@@ -311,7 +311,9 @@ __device__ inline uint32_t gn_solve(const DevParams& prm, const int16_t* dir, co
             const double g[3] = {t[6], t[7], t[8]};
             const double max_abs_g = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
             int stop = 0;
-            sh.lin_is_final = 1;                            // unless a step is applied below
+            // unless a step is applied below; not after a rejected LM step either: `keep` was linearised before that step and its
+            // revert, which leave the state changed in the last bits (below), and those can move a beam across a cell edge
+            sh.lin_is_final = sh.reuse ? 0 : 1;
             if (lm) for (int k = 0; k < NJ; ++k) sh.keep[k] = t[k];
             if (max_abs_g < eps1) {
                 stop = 1;                                   // h = 0, not applied

@@ -224,6 +224,19 @@ int orc_solve_full(void* dm, const double* pts, int n, const double* origin3, co
     }
     return (int)st.iterations;
 }
+// The same solve with what tells its exits apart: returns the iterations, *evals_out = problem evaluations (solver.cpp:71 and :90;
+// a rejected LevenbergMarquard step saves the next :71).  PFSlam2D::scanMatch counts one more for calculateLikelihood.
+int orc_solve_stats(void* dm, const double* pts, int n, const double* origin3, const double* quat4, double* pose4, uint32_t max_iter,
+                    int lm, uint32_t* evals_out)
+{
+    Scan s = make_scan(pts, n, origin3, quat4);
+    MatchSurface2D ms((const DynamicDistanceMap*)dm, &s, se2_of(pose4));
+    CauchyWeight cauchy(0.15);
+    SolveStats st = lm ? solve_lm(ms, max_iter, cauchy) : solve_gn(ms, max_iter, cauchy);
+    se2_to(ms.state_, pose4);
+    if (evals_out) *evals_out = st.evals;
+    return (int)st.iterations;
+}
 // MatchSurface2D::error (match_surface_2d.cpp:92-116)
 double orc_match_error(void* dm, const double* pts, int n, const double* origin3, const double* quat4, const double* pose4)
 {

@@ -27,8 +27,9 @@ KINDS = [("unit", 0.0), ("tukey", 4.6851), ("tdist", 3.0), ("cauchy", 0.3), ("hu
 
 
 def kernel_constants():
-    src = open(KERNELS_H).read()
-    return {k: int(re.search(r"constexpr int " + k + r" = (\d+);", src).group(1)) for k in ("SM_BLOCK", "SM_NB")}
+    with open(KERNELS_H) as f:
+        src = f.read()
+    return {k: int(re.search(r"constexpr int " + k + r" = (\d+);", src).group(1)) for k in ("SM_BLOCK", "SM_NB", "SM_LUT")}
 
 
 def slicing_sizes():

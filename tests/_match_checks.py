@@ -44,16 +44,17 @@ def world_obstacles(half_len=40.0):
     return np.concatenate([open_corridor(half_len=half_len), np.array(blob)])
 
 
-def build_world(F, l2_max, half_len=40.0):
+def build_world(F, l2_max, half_len=40.0, **cfg):
     """-> (context, oracle map): one particle whose distance map comes from lama_hip_map_add_obstacles, and the oracle's map
-    from DynamicDistanceMap add + update.  The maps are asserted bit-equal first, so every later difference is the kernel's."""
+    from DynamicDistanceMap add + update.  The maps are asserted bit-equal first, so every later difference is the kernel's.
+    cfg: further members of the context's configuration."""
     cells = np.array([[int(c[0]), int(c[1])] for c in (O.w2m([x, y, 0.0]) for x, y in world_obstacles(half_len))], dtype=np.uint32)
     dm = O.DM.new(l2_max=l2_max)
     for x, y in cells:
         dm.add(int(x), int(y))
     dm.update()
     assert dm.max_sqdist() == math.ceil(l2_max * (1.0 / 0.05)) ** 2
-    ctx = F.HipContext(F.default_cfg(particles=1, l2_max=l2_max))
+    ctx = F.HipContext(F.default_cfg(particles=1, l2_max=l2_max, **cfg))
     ctx.add_obstacles(0, cells)
     assert_maps_equal(ctx.download_map(0, F.MAP_DISTANCE), dm.dump(), DM_FIELDS, f"world distance map, l2_max {l2_max}")
     return ctx, dm
@@ -143,10 +144,10 @@ def assert_sum(dev, terms, what):
     assert abs(dev - ref) <= bound, (what, dev, ref, abs(dev - ref), bound)
 
 
-def check_eval(ctx, dm, pts, pose, origin=O.ZERO3, quat=O.IDENT_Q, same_libm=False, what=""):
+def check_eval(ctx, dm, pts, pose, origin=O.ZERO3, quat=O.IDENT_Q, same_libm=False, what="", particle=0):
     """k_match_eval: residuals and Jacobian rows of MatchSurface2D::eval; cell mode: distance(w2m(hit)) of every beam.
     -> the device's (residuals, Jacobian)"""
-    r, J = ctx.match_eval(0, pts, pose, origin, quat)
+    r, J = ctx.match_eval(particle, pts, pose, origin, quat)
     orr, oJ = O.eval_(dm, pts, pose, origin, quat)
     if _bit_equal_pose(pose, same_libm):
         assert np.array_equal(r, orr), (what, np.abs(r - orr).max())
@@ -154,7 +155,7 @@ def check_eval(ctx, dm, pts, pose, origin=O.ZERO3, quat=O.IDENT_Q, same_libm=Fal
     else:
         assert np.abs(r - orr).max() <= R_TOL, (what, np.abs(r - orr).max())
         assert np.abs(J - oJ).max() <= J_TOL, (what, np.abs(J - oJ).max())
-    d = ctx.cell_distances(0, pts, pose, origin, quat)
+    d = ctx.cell_distances(particle, pts, pose, origin, quat)
     od = O.cell_distances(dm, pts, pose, origin, quat)
     assert np.array_equal(d, od), (what, np.flatnonzero(d != od)[:8])
     return r, J

@@ -381,6 +381,18 @@ def solve_full(dm, pts, pose, max_iter=100, lm=False, origin=ZERO3, quat=IDENT_Q
     return pose, it, cov.reshape(3, 3)
 
 
+def solve_stats(dm, pts, pose, max_iter=100, lm=False, origin=ZERO3, quat=IDENT_Q):
+    """Solve(GN | LM, Cauchy(0.15)): (pose, iterations, problem evaluations) -- the two counts tell the solver's exits apart."""
+    L = lib()
+    L.orc_solve_stats.restype = C.c_int
+    L.orc_solve_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    pose = np.array(pose, dtype=np.float64)
+    ev = C.c_uint32(0)
+    it = L.orc_solve_stats(dm.h, _p(pts), len(pts), _p(origin), _p(quat), _p(pose), max_iter, 1 if lm else 0, C.byref(ev))
+    return pose, it, ev.value
+
+
 def match_error(dm, pts, pose, origin=ZERO3, quat=IDENT_Q):
     """MatchSurface2D::error(): rms of the non-interpolated cell distances."""
     L = lib()
