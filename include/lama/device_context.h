@@ -14,6 +14,7 @@ struct lama_hip_cfg;
 namespace lama {
 
 struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
+namespace sdm { struct GridOptions; struct OccupancyGrid; struct DistanceGrid; }      // include/lama/sdm/grid.h
 
 class DeviceContext {
 public:
@@ -41,6 +42,12 @@ public:
     void check(int32_t rc, const char* what) const;
     // one particle's map of a kind (LAMA_HIP_MAP_*) in the reference's record formats; true with empty arrays when it has no patch
     bool download(uint32_t particle, int32_t kind, std::vector<uint64_t>& ids, std::vector<uint8_t>& cells, std::vector<uint64_t>& masks) const;
+    // One particle's map written out dense on the device (lama_hip_map_bounds + lama_hip_map_rasterize, include/lama/sdm/grid.h):
+    // the whole map or the world box of the options.  The snapshots behind download() are neither made nor touched.  Throws
+    // std::runtime_error when the device library lacks the two entry points or refuses the call, std::invalid_argument for a
+    // stride of 0 or a world box whose max lies below its min.
+    bool occupancyGrid(uint32_t particle, double resolution, sdm::OccupancyGrid& grid, const sdm::GridOptions& options) const;
+    bool distanceGrid(uint32_t particle, double resolution, double l2_max, sdm::DistanceGrid& grid, const sdm::GridOptions& options) const;
 
 private:
     std::shared_ptr<HipEngine> eng_;

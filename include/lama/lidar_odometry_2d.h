@@ -16,6 +16,7 @@
 
 #include "device_context.h"
 #include "pose2d.h"
+#include "sdm/grid.h"
 #include "sdm_io.h"
 
 namespace lama {
@@ -42,6 +43,12 @@ struct LidarOdometry2D {
 
     bool downloadDistanceMap(sdm::HostMap& m) const;
     bool downloadOccupancyMap(sdm::HostMap& m) const;      // kind = kProbabilisticOccupancyMap: 4-byte float log-odds cells
+    // Dense grids of the device maps, made on the device (lama/sdm/grid.h); false before the first scan.  The occupancy map holds
+    // log-odds: trinary only (GridOptions::probability is refused, exp is not exact).  The distance map reaches 1 m.
+    bool getOccupancyGrid(sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return device_initialised_ && dev_.occupancyGrid(0, opt_.resolution, grid, options); }
+    bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return device_initialised_ && dev_.distanceGrid(0, opt_.resolution, 1.0, grid, options); }
     uint32_t getLastIterations() const { return last_iterations_; }
     uint32_t getLastDeletedPatches() const { return last_deleted_; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }

@@ -22,6 +22,7 @@
 #include "device_context.h"
 #include "pose2d.h"
 #include "sdm/dynamic_distance_map.h"
+#include "sdm/grid.h"
 #include "sdm/simple_occupancy_map.h"
 
 namespace lama {
@@ -70,6 +71,10 @@ public:
     uint32_t getLastIterations() const { return last_iterations_; }
     // true when the first build of the distance map was replayed on the host and uploaded (iris_lama_amd/host/dm_builder.hpp)
     bool distanceMapBuiltOnHost() const { return host_built_; }
+    // Dense grid of the DEVICE distance map, made on the device (lama/sdm/grid.h); false while there is no device map yet.
+    // (occupancy_map is a host map: walk it on the host.)
+    bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return dev_ && dev_.distanceGrid(0, opt_.resolution, opt_.l2_max, grid, options); }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }
 

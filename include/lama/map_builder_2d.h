@@ -21,6 +21,7 @@
 
 #include "device_context.h"
 #include "pose2d.h"
+#include "sdm/grid.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -65,6 +66,13 @@ public:
     // and lama::Solve run their kernels on the map build() left there.
     const FrequencyOccupancyMap* getOccupancyMap() const;
     const DynamicDistanceMap* getDistanceMap() const;
+
+    // Dense grids of the built maps, made on the device (lama/sdm/grid.h); false before the first build (the distance grid also with
+    // l2_max == 0).  The snapshots above are neither made nor dropped.
+    bool getOccupancyGrid(sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return has_map_ && dev_.occupancyGrid(0, opt_.resolution, grid, options); }
+    bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return has_map_ && opt_.l2_max > 0.0 && dev_.distanceGrid(0, opt_.resolution, opt_.l2_max, grid, options); }
 
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }

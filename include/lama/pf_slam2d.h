@@ -31,6 +31,7 @@
 
 #include "device_context.h"
 #include "pose2d.h"
+#include "sdm/grid.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -179,6 +180,14 @@ public:
         }
         return dm_view_.get();
     }
+
+    // Dense grids of the best particle's / of particle i's device maps, made on the device (lama/sdm/grid.h).  false before the first
+    // scan, for i >= particles, or when the particle lives on another PROCESS' shard (a gpus > 1 object reaches all of its shards).
+    // The snapshots of getOccupancyMap() / getDistanceMap() are neither made nor dropped.
+    bool getOccupancyGrid(sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
+    bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
+    bool getParticleOccupancyGrid(size_t i, sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
+    bool getParticleDistanceGrid(size_t i, sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
 
     // ------------------------------------------------------------------ step-wise API (sharded operation)
     enum Phase { kNoUpdate = 0, kFirstScan = 1, kMatched = 2 };

@@ -16,6 +16,7 @@
 
 #include "device_context.h"
 #include "pose2d.h"
+#include "sdm/grid.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -102,6 +103,13 @@ public:
         }
         return dm_view_.get();
     }
+    // Dense grids of the device maps, made on the device (lama/sdm/grid.h: the whole map or a world box, one element per stride x stride
+    // block) -- what a map publisher needs, without the sparse download and the cell-by-cell walk over bounds().  false before the
+    // first scan.  The snapshots of getOccupancyMap() / getDistanceMap() are neither made nor dropped.
+    bool getOccupancyGrid(sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return has_first_scan && dev_.occupancyGrid(0, resolution_, grid, options); }
+    bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
+    { return has_first_scan && dev_.distanceGrid(0, resolution_, l2_max_, grid, options); }
     // include/lama/slam2d.h:157-161
     void saveOccImage(const std::string& name) const { const FrequencyOccupancyMap* m = getOccupancyMap(); if (m) sdm::export_to_png(m->snapshot(), name); }
     void saveDistImage(const std::string& name) const { const DynamicDistanceMap* m = getDistanceMap(); if (m) sdm::export_to_png(m->snapshot(), name); }

@@ -368,6 +368,31 @@ int32_t lama_hip_map_integrate_scans(lama_hip_ctx* ctx, uint32_t particle, uint3
  * up to `cap` of them are written to cells_xy (NULL: only the number is wanted). */
 int32_t lama_hip_map_occupied_cells(lama_hip_ctx* ctx, uint32_t particle, uint32_t cap, uint32_t* cells_xy, uint32_t* n);
 
+/* Map::bounds (src/sdm/map.cpp:139-157) of `particle`'s device map of `kind` (LAMA_HIP_MAP_*): min over the allocated patches'
+ * anchors, max + 32, in map cells; one small reduction over the window directory on the device.  A map without patches:
+ * *num_patches = 0, min = 0xFFFFFFFF, max = 32 (what lama::Map::bounds of its snapshot gives).  Any output pointer may be NULL. */
+int32_t lama_hip_map_bounds(lama_hip_ctx* ctx, uint32_t particle, int32_t kind, uint32_t min_xy[2], uint32_t max_xy[2], uint32_t* num_patches);
+
+/* `particle`'s map written out DENSE on the device (csrc/lama_raster.h), one element per `stride x stride` block of cells -- what a
+ * nav_msgs/OccupancyGrid, a costmap or a viewer takes -- instead of the sparse reference records of lama_hip_pf_download_map.
+ * Pixel (i, j), stored at out[j * width + i] (row-major, x fastest), covers the map cells [x0 + i * stride, x0 + (i + 1) * stride) x
+ * [y0 + j * stride, y0 + (j + 1) * stride).  stride is 1, 2, 4, 8, 16 or 32; x0 and y0 are multiples of it (a block never straddles a
+ * patch); width and height are 1 .. 32768 pixels; out_bytes == width * height * element size.  Anything else is LAMA_HIP_E_INVALID,
+ * found before `out` is written.  The box may lie partly or wholly outside the allocated patches or the map window: those cells are
+ * "absent", not an error.  Cell rules, exact and in integers:
+ *   frequency cells (cfg.occupancy_policy 0): visited == 0 or absent -> unknown; 4 * occupied > visited -> occupied; 4 * occupied <
+ *     visited -> free; equality -> unknown (identical to the reference's double comparison of occupied / visited with 0.25 for every
+ *     uint16 pair, see csrc/lama_raster.h); probability = (200 * occupied + visited) / (2 * visited), at most 100;
+ *   log-odds cells (policy 1): l < 0 free, l > 0 occupied, otherwise unknown (no probability layer: exp is not exact);
+ *   distance cells: the stored sqdist where the cell is present and valid_obstacle is set, otherwise the context's max_sqdist.
+ * Blocks (stride > 1): occupied if any cell is, else free if any cell is, else unknown; the largest probability of the visited cells,
+ * else -1; the smallest squared distance.  Like every entry point the call first waits for queued map updates. */
+#define LAMA_HIP_RASTER_TRINARY     0   /* int8:  0 free, 100 occupied, -1 otherwise  (isFree / else isOccupied / else, as the ROS nodes do) */
+#define LAMA_HIP_RASTER_PROBABILITY 1   /* int8:  0..100 = round-half-up(100 * occupied / visited), -1 where visited == 0 or absent; policy 0 only */
+#define LAMA_HIP_RASTER_SQDIST      2   /* uint16: squared distance in cells; max_sqdist where the cell is absent or has no valid obstacle */
+int32_t lama_hip_map_rasterize(lama_hip_ctx* ctx, uint32_t particle, int32_t layer, uint32_t x0, uint32_t y0,
+                               uint32_t width, uint32_t height, uint32_t stride, void* out, uint64_t out_bytes);
+
 /* Particle shipping for multi-GPU resampling (one context per GPU): serialise one particle (pose + both
  * maps, used patches only) into a DEVICE buffer / restore it into slot `particle` of this context.
  * export returns the number of bytes needed in *bytes when buf == NULL. */

@@ -318,6 +318,33 @@ int64_t lama_mapbuilder_view_cells(lama_mapbuilder* b, int which, uint32_t* xy_o
 /* lama::Solve(GaussNewton + Cauchy(0.15), MatchSurface2D(getDistanceMap(), scan, pose)): pose4 in / out */
 int lama_mapbuilder_match_solve(lama_mapbuilder* b, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz,
                                 double* pose4, uint32_t max_iterations, uint32_t* iterations);
+/* ---- dense grids (include/lama/sdm/grid.h): getOccupancyGrid / getDistanceGrid of the classes above, made on the device.
+ * options NULL: the defaults (whole map, stride 1, trinary).  Each call returns 1 when the grid was made -- its header in *out, its
+ * pixels (row-major, x fastest; int8 occupancy, uint16 squared cell distances) kept on the calling thread until its next grid call --,
+ * 0 when the object has no such map (before the first scan / build, a particle of another process), -2 on a failure (message through
+ * the object's last_error: a device library without lama_hip_map_rasterize, an invalid stride, ...).  lama_grid_fetch copies the kept
+ * pixels when cap_bytes suffices and returns their size in bytes.  lama_pf_*: particle < 0 is the best particle. */
+typedef struct lama_grid_options {
+    uint32_t stride;
+    int32_t probability, whole_map;
+    double world_min[2], world_max[2];
+} lama_grid_options;
+typedef struct lama_grid {
+    uint32_t x0, y0, width, height, stride, element_bytes;
+    double resolution, cell_size, max_distance;      /* max_distance: distance grids, metres */
+    double origin[3];                                /* Map::m2w of cell (x0, y0), z = 0 */
+} lama_grid;
+void lama_grid_default_options(lama_grid_options* o);
+int64_t lama_grid_fetch(void* out, uint64_t cap_bytes);
+int lama_slam_occupancy_grid(lama_slam* s, const lama_grid_options* options, lama_grid* out);
+int lama_slam_distance_grid(lama_slam* s, const lama_grid_options* options, lama_grid* out);
+int lama_pf_occupancy_grid(lama_pf* pf, int64_t particle, const lama_grid_options* options, lama_grid* out);
+int lama_pf_distance_grid(lama_pf* pf, int64_t particle, const lama_grid_options* options, lama_grid* out);
+int lama_mapbuilder_occupancy_grid(lama_mapbuilder* b, const lama_grid_options* options, lama_grid* out);
+int lama_mapbuilder_distance_grid(lama_mapbuilder* b, const lama_grid_options* options, lama_grid* out);
+int lama_lo_occupancy_grid(lama_lo* l, const lama_grid_options* options, lama_grid* out);
+int lama_lo_distance_grid(lama_lo* l, const lama_grid_options* options, lama_grid* out);
+int lama_loc_distance_grid(lama_loc* l, const lama_grid_options* options, lama_grid* out);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

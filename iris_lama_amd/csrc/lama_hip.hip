@@ -19,6 +19,7 @@
 #include "lama_pgo.h"
 #include "lama_pgo_pcg.h"
 #include "lama_map_build.h"
+#include "lama_raster.h"
 #include "lama_match_batch.h"
 #include "lama_correlative.h"
 #include "../host/pgo_pattern.hpp"
@@ -260,6 +261,8 @@ struct lama_hip_ctx {
     DevBuf<double> d_mb_pts, d_mb_tfs; DevBuf<uint32_t> d_mb_offs; DevBuf<lama_dev::MbRay> d_mb_rays;
     DevBuf<uint32_t> d_mb_table, d_mb_off, d_mb_list, d_mb_bins; DevBuf<int32_t> d_mb_slot; DevBuf<uint64_t> d_mb_meta;
     PinVec<double> h_mb_tfs; PinVec<uint32_t> h_mb_offs; PinVec<uint64_t> h_mb_meta;
+    // lama_hip_map_rasterize / lama_hip_map_bounds (lama_raster.h): the dense grid and its page-locked staging copy, grow-only
+    DevBuf<uint8_t> d_raster; PinVec<uint8_t> h_raster;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
     // lama_hip_match_solve_batch (lama_match_batch.h), grow-only: [out8 8B | poses 4B | mounts 12B | points 3N] and
     // [iterations B | status B | problems 4B], with their page-locked staging copies
@@ -2973,6 +2976,74 @@ int32_t lama_hip_map_occupied_cells(lama_hip_ctx* c, uint32_t particle, uint32_t
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(cells_xy, d_out, sizeof(uint32_t) * 2 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LAMA_HIP_OK;
+}
+
+// ---- lama_raster.h: the box of a map's patches, and a map written out as a dense grid ----------------------------------------------
+int32_t lama_hip_map_bounds(lama_hip_ctx* c, uint32_t particle, int32_t kind, uint32_t min_xy[2], uint32_t max_xy[2], uint32_t* num_patches)
+{
+    if (!c || particle >= c->P || (kind != LAMA_HIP_MAP_DISTANCE && kind != LAMA_HIP_MAP_OCCUPANCY)) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // Map::bounds of a map without patches (src/sdm/map.cpp:139-157): min stays at its start value, max is 0 + patch_length
+    uint32_t lo[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, hi[2] = {32u, 32u}, n = 0;
+    if (c->h_counts[2 * particle + (kind == LAMA_HIP_MAP_DISTANCE ? 0 : 1)] != 0) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, c->d_raster.grow(sizeof(MapBoundsRec), (size_t)1 << 16));
+        c->h_raster.reserve(sizeof(MapBoundsRec));
+        MapBoundsRec* const d_rec = reinterpret_cast<MapBoundsRec*>(c->d_raster.p);
+        hipLaunchKernelGGL(k_map_bounds, dim3(1), dim3(MB_SCAN_BLOCK), 0, c->stream, make_params(c), (int)particle, kind == LAMA_HIP_MAP_DISTANCE ? 0 : 1, d_rec);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_raster.data(), d_rec, sizeof(MapBoundsRec), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        MapBoundsRec r;
+        std::memcpy(&r, c->h_raster.data(), sizeof(r));
+        n = r.n;
+        if (n) { lo[0] = c->wx0 + 32u * r.x0; lo[1] = c->wy0 + 32u * r.y0; hi[0] = c->wx0 + 32u * r.x1 + 32u; hi[1] = c->wy0 + 32u * r.y1 + 32u; }
+    }
+    if (min_xy) { min_xy[0] = lo[0]; min_xy[1] = lo[1]; }
+    if (max_xy) { max_xy[0] = hi[0]; max_xy[1] = hi[1]; }
+    if (num_patches) *num_patches = n;
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_map_rasterize(lama_hip_ctx* c, uint32_t particle, int32_t layer, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                               uint32_t stride, void* out, uint64_t out_bytes)
+{
+    if (!c || !out || particle >= c->P) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // ---- everything that can refuse the call comes before anything is written ----
+    if (layer != LAMA_HIP_RASTER_TRINARY && layer != LAMA_HIP_RASTER_PROBABILITY && layer != LAMA_HIP_RASTER_SQDIST) return fail(c, LAMA_HIP_E_INVALID, "unknown raster layer");
+    if (layer == LAMA_HIP_RASTER_PROBABILITY && c->cfg.occupancy_policy != 0)
+        return fail(c, LAMA_HIP_E_INVALID, "the probability layer is exact for the frequency occupancy policy only (cfg.occupancy_policy 0)");
+    uint32_t log2s = 0;
+    while (log2s < 6u && (1u << log2s) != stride) ++log2s;
+    if (log2s > 5u) return fail(c, LAMA_HIP_E_INVALID, "the raster stride must be 1, 2, 4, 8, 16 or 32");
+    if ((x0 & (stride - 1u)) || (y0 & (stride - 1u))) return fail(c, LAMA_HIP_E_INVALID, "the raster origin must be a multiple of the stride");
+    if (width < 1u || height < 1u || width > 32768u || height > 32768u) return fail(c, LAMA_HIP_E_INVALID, "raster width and height must be 1 .. 32768 pixels");
+    const size_t esize = layer == LAMA_HIP_RASTER_SQDIST ? 2 : 1, bytes = (size_t)width * height * esize;
+    if (out_bytes != (uint64_t)bytes) return fail(c, LAMA_HIP_E_INVALID, "out_bytes is not width * height * element size");
+    const bool dm = layer == LAMA_HIP_RASTER_SQDIST;
+    if (c->h_counts[2 * particle + (dm ? 0 : 1)] == 0) {            // no patch at all (a context before its first scan has no window yet): every cell is absent
+        if (dm) std::fill_n(static_cast<uint16_t*>(out), (size_t)width * height, (uint16_t)c->max_sqdist);
+        else std::memset(out, 0xFF, bytes);
+        return LAMA_HIP_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, c->d_raster.grow(bytes, (size_t)1 << 16));
+    c->h_raster.reserve(bytes);
+    const RasterBox box{x0, y0, width, height, stride, log2s};
+    // the patch positions the box touches (its last cell may lie past 2^32 - 1: 64 bits)
+    const uint64_t xe = (uint64_t)x0 + (uint64_t)width * stride - 1u, ye = (uint64_t)y0 + (uint64_t)height * stride - 1u;
+    const dim3 grid((unsigned)((xe >> 5) - (x0 >> 5) + 1u), (unsigned)((ye >> 5) - (y0 >> 5) + 1u));
+    const DevParams prm = make_params(c);
+    uint8_t* const d_out = c->d_raster;
+    if (layer == LAMA_HIP_RASTER_TRINARY) hipLaunchKernelGGL(k_raster<RASTER_TRINARY>, grid, dim3(256), 0, c->stream, prm, (int)particle, box, reinterpret_cast<int8_t*>(d_out));
+    else if (layer == LAMA_HIP_RASTER_PROBABILITY) hipLaunchKernelGGL(k_raster<RASTER_PROBABILITY>, grid, dim3(256), 0, c->stream, prm, (int)particle, box, reinterpret_cast<int8_t*>(d_out));
+    else hipLaunchKernelGGL(k_raster<RASTER_SQDIST>, grid, dim3(256), 0, c->stream, prm, (int)particle, box, reinterpret_cast<uint16_t*>(d_out));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_raster.data(), d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_raster.data(), bytes);
     return LAMA_HIP_OK;
 }
 

@@ -79,6 +79,7 @@ def _hip_signatures():
     # groups the engine test double (tests/cpu_engine) may lack: a library has a whole group or none of it, probed by its first name
     optional = [
         {"lama_hip_map_integrate_scans": [vp, u32, u32, vp, vp, vp, vp, vp, u32], "lama_hip_map_occupied_cells": [vp, u32, u32, vp, vp]},
+        {"lama_hip_map_bounds": [vp, u32, i32, vp, vp, vp], "lama_hip_map_rasterize": [vp, u32, i32, u32, u32, u32, u32, u32, vp, u64]},
         {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
         {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
         {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
@@ -183,6 +184,7 @@ _Z3 = np.zeros(3)
 
 
 MAP_BUILD_FULL, MAP_BUILD_PRUNE = 1, 2
+RASTER_TRINARY, RASTER_PROBABILITY, RASTER_SQDIST = 0, 1, 2      # LAMA_HIP_RASTER_*
 ROBUST_KINDS = {"unit": 0, "tukey": 1, "tdist": 2, "cauchy": 3, "huber": 4}      # LAMA_HIP_ROBUST_*
 ROBUST_STORED = 0x100     # LAMA_HIP_ROBUST_STORED: robust_param is the constant as the class stores it (b * b, 1 / param^2)
 E_NUMERIC = -6
@@ -234,11 +236,66 @@ def device_count():
     return n.value
 
 
+class GridOptions(C.Structure):
+    """lama_grid_options (include/lama_host.h): lama::sdm::GridOptions"""
+    _fields_ = [("stride", C.c_uint32), ("probability", C.c_int32), ("whole_map", C.c_int32), ("world_min", C.c_double * 2), ("world_max", C.c_double * 2)]
+
+
+class GridHeader(C.Structure):
+    """lama_grid (include/lama_host.h)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32),
+                ("element_bytes", C.c_uint32), ("resolution", C.c_double), ("cell_size", C.c_double), ("max_distance", C.c_double),
+                ("origin", C.c_double * 3)]
+
+
+class Grid:
+    """A dense grid of a device map (lama::sdm::OccupancyGrid / DistanceGrid): `data` is (height, width), int8 occupancy values
+    (0 free, 100 occupied, -1 unknown; or 0 .. 100) or uint16 squared cell distances; pixel (i, j) = data[j, i] covers the map cells
+    from (x0 + i * stride, y0 + j * stride); origin = Map::m2w of cell (x0, y0)."""
+
+    def __init__(self, hdr, data):
+        for name, _ in GridHeader._fields_:
+            setattr(self, name, getattr(hdr, name))
+        self.origin = np.array(list(hdr.origin))
+        self.data = data
+
+    def metres(self):
+        """DistanceGrid::metres of every pixel: sqrt(sqdist) * resolution"""
+        return np.sqrt(self.data.astype(np.float64)) * self.resolution
+
+
 class _Handle:
     """A native handle `h` of the library `L`: the names of its destroy and last-error entry points and -- for the host classes --
     of the accessor of the device context, whose particle count is `_ctx_P`."""
     _destroy = _last_error = _context = None
     _ctx_P = 1
+    _grid_prefix = None            # "lama_slam", ...: the class has <prefix>_occupancy_grid / <prefix>_distance_grid
+
+    def _grid(self, what, args, stride, probability, world_box):
+        o = GridOptions()
+        self.L.lama_grid_default_options(C.byref(o))
+        o.stride, o.probability = int(stride), 1 if probability else 0
+        if world_box is not None:
+            o.whole_map = 0
+            o.world_min[0], o.world_min[1], o.world_max[0], o.world_max[1] = (float(v) for v in world_box)
+        hdr = GridHeader()
+        rc = getattr(self.L, f"{self._grid_prefix}_{what}_grid")(self.h, *args, C.byref(o), C.byref(hdr))
+        if rc < 0:
+            raise LamaError(self._error())
+        if rc == 0:
+            return None
+        data = np.zeros((hdr.height, hdr.width), dtype=np.uint16 if hdr.element_bytes == 2 else np.int8)
+        assert self.L.lama_grid_fetch(_p(data), data.nbytes) == data.nbytes
+        return Grid(hdr, data)
+
+    def occupancy_grid(self, stride=1, probability=False, world_box=None):
+        """getOccupancyGrid: the dense occupancy grid made on the device -> Grid, or None while there is no map.  world_box =
+        (min x, min y, max x, max y) in metres instead of the whole map."""
+        return self._grid("occupancy", (), stride, probability, world_box)
+
+    def distance_grid(self, stride=1, world_box=None):
+        """getDistanceGrid -> Grid of uint16 squared cell distances (Grid.metres()), or None while there is no map."""
+        return self._grid("distance", (), stride, False, world_box)
 
     def close(self):
         if getattr(self, "h", None) and not getattr(self, "_is_borrowed", False):
@@ -459,6 +516,19 @@ class HipContext(_Handle):
             self._chk(self.L.lama_hip_map_occupied_cells(self.h, particle, n.value, _p(out), C.byref(n)))
         return out
 
+    def map_bounds(self, particle, kind):
+        """lama_hip_map_bounds: Map::bounds of the device map -> (min (2,) uint32, max (2,) uint32, number of patches)."""
+        lo, hi, n = np.zeros(2, dtype=np.uint32), np.zeros(2, dtype=np.uint32), C.c_uint32(0)
+        self._chk(self.L.lama_hip_map_bounds(self.h, particle, kind, _p(lo), _p(hi), C.byref(n)))
+        return lo, hi, int(n.value)
+
+    def rasterize(self, particle, layer, x0, y0, width, height, stride=1):
+        """lama_hip_map_rasterize: the dense grid of a box of the map, shape (height, width); int8 for RASTER_TRINARY (0 free, 100
+        occupied, -1 unknown) and RASTER_PROBABILITY (0 .. 100, -1), uint16 squared cell distances for RASTER_SQDIST."""
+        out = np.zeros((int(height), int(width)), dtype=np.uint16 if layer == RASTER_SQDIST else np.int8)
+        self._chk(self.L.lama_hip_map_rasterize(self.h, particle, int(layer), int(x0), int(y0), int(width), int(height), int(stride), _p(out), out.nbytes))
+        return out
+
     def match_solve(self, particle, pts, pose4, origin=None, quat=None, solve=True):
         """-> (pose, JtJ lower [00,10,11,20,21,22], sum r^2 (unweighted), iterations)"""
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -662,6 +732,9 @@ HOST_SYMBOLS = [
     "lama_mapbuilder_engine_origin", "lama_mapbuilder_device_context", "lama_mapbuilder_add", "lama_mapbuilder_set_pose",
     "lama_mapbuilder_set_poses", "lama_mapbuilder_build", "lama_mapbuilder_reset", "lama_mapbuilder_occupied_cells",
     "lama_mapbuilder_timing", "lama_mapbuilder_view_cells", "lama_mapbuilder_match_solve",
+    "lama_grid_default_options", "lama_grid_fetch", "lama_slam_occupancy_grid", "lama_slam_distance_grid", "lama_pf_occupancy_grid",
+    "lama_pf_distance_grid", "lama_mapbuilder_occupancy_grid", "lama_mapbuilder_distance_grid", "lama_lo_occupancy_grid",
+    "lama_lo_distance_grid", "lama_loc_distance_grid",
 ]
 
 
@@ -731,6 +804,12 @@ def _bind_host(L):
         "lama_mapbuilder_occupied_cells": (C.c_int64, [vp, vp, C.c_uint64]), "lama_mapbuilder_timing": (i32, [vp, vp]),
         "lama_mapbuilder_view_cells": (C.c_int64, [vp, i32, vp, C.c_uint64]),
         "lama_mapbuilder_match_solve": (i32, [vp, vp, u32, vp, vp, vp, u32, vp]),
+        "lama_grid_default_options": (None, [vp]), "lama_grid_fetch": (C.c_int64, [vp, C.c_uint64]),
+        "lama_slam_occupancy_grid": (i32, [vp, vp, vp]), "lama_slam_distance_grid": (i32, [vp, vp, vp]),
+        "lama_pf_occupancy_grid": (i32, [vp, C.c_int64, vp, vp]), "lama_pf_distance_grid": (i32, [vp, C.c_int64, vp, vp]),
+        "lama_mapbuilder_occupancy_grid": (i32, [vp, vp, vp]), "lama_mapbuilder_distance_grid": (i32, [vp, vp, vp]),
+        "lama_lo_occupancy_grid": (i32, [vp, vp, vp]), "lama_lo_distance_grid": (i32, [vp, vp, vp]),
+        "lama_loc_distance_grid": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -778,6 +857,15 @@ def pose_from_xyr(x, y, yaw):
 class PFSlam2D(_Handle):
     """ctypes view of the host-side lama::PFSlam2D (include/lama/pf_slam2d.h)."""
     _destroy, _last_error, _context = "lama_pf_destroy", "lama_pf_last_error", "lama_pf_device_context"
+    _grid_prefix = "lama_pf"
+
+    def occupancy_grid(self, stride=1, probability=False, world_box=None, particle=None):
+        """getOccupancyGrid (the best particle's) / getParticleOccupancyGrid(particle) -> Grid, or None (no map yet, or the
+        particle lives in another process)."""
+        return self._grid("occupancy", (-1 if particle is None else int(particle),), stride, probability, world_box)
+
+    def distance_grid(self, stride=1, world_box=None, particle=None):
+        return self._grid("distance", (-1 if particle is None else int(particle),), stride, False, world_box)
 
     def __init__(self, opts):
         self.L = _hostlib()
@@ -920,6 +1008,7 @@ class SlamOptions(C.Structure):
 class Slam2D(_Handle):
     """ctypes view of the host-side lama::Slam2D (include/lama/slam2d.h): online SLAM, one pose + one map pair."""
     _destroy, _last_error, _context = "lama_slam_destroy", "lama_slam_last_error", "lama_slam_device_context"
+    _grid_prefix = "lama_slam"
 
     def __init__(self, **kw):
         self.L = _hostlib()
@@ -1073,6 +1162,10 @@ class Slam2D(_Handle):
 class Loc2D(_Handle):
     """ctypes view of the host-side lama::Loc2D (include/lama/loc2d.h): localisation on a fixed distance map."""
     _destroy, _last_error, _context = "lama_loc_destroy", "lama_loc_last_error", "lama_loc_device_context"
+    _grid_prefix = "lama_loc"
+
+    def occupancy_grid(self, *a, **kw):
+        raise LamaError("lama::Loc2D has no device occupancy map: occupancy_map is a host map (distance_grid() is available)")
 
     def __init__(self, trans_thresh=0.5, rot_thresh=0.5, l2_max=1.0, resolution=0.05, max_iter=100, gpu_device=0,
                  gloc_particles=3000, gloc_iters=10, gloc_thresh=0.15, cov_blend=0.0, strategy="gn"):
@@ -1488,6 +1581,7 @@ def pose_graph_optimize(nodes, factors, device=0, solver=None, pcg_rel_tol=1e-10
 class LidarOdometry2D(_Handle):
     """ctypes view of the host-side lama::LidarOdometry2D (include/lama/lidar_odometry_2d.h)."""
     _destroy, _last_error, _context = "lama_lo_destroy", "lama_lo_last_error", "lama_lo_device_context"
+    _grid_prefix = "lama_lo"
 
     def __init__(self, resolution=0.05, max_iter=100, gpu_device=0):
         self.L = _hostlib()
@@ -1524,6 +1618,7 @@ class MapBuilderOptions(C.Structure):
 class MapBuilder2D(_Handle):
     """ctypes view of the host-side lama::MapBuilder2D (include/lama/map_builder_2d.h): a map rebuilt from posed key scans."""
     _destroy, _last_error, _context = "lama_mapbuilder_destroy", "lama_mapbuilder_last_error", "lama_mapbuilder_device_context"
+    _grid_prefix = "lama_mapbuilder"
 
     def __init__(self, **kw):
         self.L = _hostlib()

@@ -1,9 +1,13 @@
 // device_context.cpp -- lama::DeviceContext (include/lama/device_context.h) and the text of a refused device call.
 #include "lama/device_context.h"
 
+#include <algorithm>
+#include <cmath>
 #include <stdexcept>
 
 #include "hip_engine.hpp"
+#include "lama/sdm/grid.h"
+#include "lama/sdm_maps.h"
 
 namespace lama {
 
@@ -50,6 +54,76 @@ bool DeviceContext::download(uint32_t particle, int32_t kind, std::vector<uint64
     masks.assign((size_t)n * kMaskWordsPerPatch, 0);
     if (n == 0) return true;
     return eng_->pf_download_map(ctx_, particle, kind, n, ids.data(), cells.data(), masks.data(), &got) == 0 && got == n;
+}
+
+// ---- dense grids (include/lama/sdm/grid.h) ------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kMaxGridSide = 32768;            // pixels (lama_hip_map_rasterize)
+
+// the box of the grid: Map::bounds of the device map, or the world box in cells (Map::w2m) widened outwards to multiples of the
+// stride; a side is clipped to kMaxGridSide pixels.  false: the map has no patch (whole_map) -- nothing to rasterise.
+bool grid_box(const HipEngine& e, lama_hip_ctx* ctx, const char* owner, uint32_t particle, int32_t kind, double resolution,
+              const sdm::GridOptions& o, sdm::GridHeader& g)
+{
+    if (!e.map_bounds || !e.map_rasterize)
+        throw std::runtime_error(std::string(owner) + ": the device library " + e.origin + " has no lama_hip_map_bounds / lama_hip_map_rasterize (dense grids)");
+    if (o.stride == 0) throw std::invalid_argument(std::string(owner) + ": a grid stride of 0");
+    const Map frame(resolution, sdm::kDistanceMap);                 // w2m / m2w of every map of this resolution
+    uint64_t lo[2], hi[2];                                          // cells, hi exclusive
+    if (o.whole_map) {
+        uint32_t a[2], b[2], n = 0;
+        const int32_t rc = e.map_bounds(ctx, particle, kind, a, b, &n);
+        if (rc) throw std::runtime_error(deviceFailure(e, ctx, owner, "lama_hip_map_bounds", rc));
+        if (n == 0) return false;
+        for (int k = 0; k < 2; ++k) { lo[k] = a[k]; hi[k] = b[k]; }
+    } else {
+        if (!(o.world_min[0] <= o.world_max[0]) || !(o.world_min[1] <= o.world_max[1]))
+            throw std::invalid_argument(std::string(owner) + ": the world box of a grid needs min <= max");
+        const Vector3ui a = frame.w2m(Vector3d(o.world_min[0], o.world_min[1], 0.0)), b = frame.w2m(Vector3d(o.world_max[0], o.world_max[1], 0.0));
+        for (int k = 0; k < 2; ++k) { lo[k] = a(k); hi[k] = (uint64_t)b(k) + 1u; }
+    }
+    const uint64_t s = o.stride;
+    for (int k = 0; k < 2; ++k) { lo[k] = lo[k] / s * s; hi[k] = (hi[k] + s - 1u) / s * s; }
+    g.x0 = (uint32_t)lo[0]; g.y0 = (uint32_t)lo[1]; g.stride = o.stride;
+    g.width = (uint32_t)std::min<uint64_t>((hi[0] - lo[0]) / s, kMaxGridSide);
+    g.height = (uint32_t)std::min<uint64_t>((hi[1] - lo[1]) / s, kMaxGridSide);
+    g.resolution = resolution; g.cell_size = (double)o.stride * resolution;
+    const Vector3d w = frame.m2w(Vector3ui(g.x0, g.y0, 0));
+    g.origin = Vector3d(w[0], w[1], 0.0);
+    return true;
+}
+
+template <class T>
+void grid_raster(const HipEngine& e, lama_hip_ctx* ctx, const char* owner, uint32_t particle, int32_t layer, const sdm::GridHeader& g, std::vector<T>& out)
+{
+    out.assign((size_t)g.width * g.height, T(0));
+    const int32_t rc = e.map_rasterize(ctx, particle, layer, g.x0, g.y0, g.width, g.height, g.stride, out.data(), (uint64_t)out.size() * sizeof(T));
+    if (rc) throw std::runtime_error(deviceFailure(e, ctx, owner, "lama_hip_map_rasterize", rc));
+}
+
+} // namespace
+
+bool DeviceContext::occupancyGrid(uint32_t particle, double resolution, sdm::OccupancyGrid& grid, const sdm::GridOptions& options) const
+{
+    if (!ctx_) return false;
+    static_cast<sdm::GridHeader&>(grid) = sdm::GridHeader();
+    grid.data.clear();
+    if (!grid_box(*eng_, ctx_, owner_, particle, LAMA_HIP_MAP_OCCUPANCY, resolution, options, grid)) return true;     // a map without patches: an empty grid
+    grid_raster(*eng_, ctx_, owner_, particle, options.probability ? LAMA_HIP_RASTER_PROBABILITY : LAMA_HIP_RASTER_TRINARY, grid, grid.data);
+    return true;
+}
+
+bool DeviceContext::distanceGrid(uint32_t particle, double resolution, double l2_max, sdm::DistanceGrid& grid, const sdm::GridOptions& options) const
+{
+    if (!ctx_) return false;
+    static_cast<sdm::GridHeader&>(grid) = sdm::GridHeader();
+    grid.sqdist.clear();
+    const uint32_t r = (uint32_t)std::ceil(l2_max * (1.0 / resolution));         // DynamicDistanceMap::setMaxDistance / maxDistance
+    grid.max_distance = std::sqrt((double)(r * r)) * resolution;
+    if (!grid_box(*eng_, ctx_, owner_, particle, LAMA_HIP_MAP_DISTANCE, resolution, options, grid)) return true;
+    grid_raster(*eng_, ctx_, owner_, particle, LAMA_HIP_RASTER_SQDIST, grid, grid.sqdist);
+    return true;
 }
 
 } // namespace lama

@@ -101,6 +101,8 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     e->match_search_lattice = reinterpret_cast<decltype(e->match_search_lattice)>(dlsym(dl, "lama_hip_match_search_lattice"));
     e->pf_match_and_map = reinterpret_cast<decltype(e->pf_match_and_map)>(dlsym(dl, "lama_hip_pf_match_and_map"));
     e->pf_step_groups = reinterpret_cast<decltype(e->pf_step_groups)>(dlsym(dl, "lama_hip_pf_step_groups"));
+    e->map_bounds = reinterpret_cast<decltype(e->map_bounds)>(dlsym(dl, "lama_hip_map_bounds"));
+    e->map_rasterize = reinterpret_cast<decltype(e->map_rasterize)>(dlsym(dl, "lama_hip_map_rasterize"));
     return e;
 }
 

@@ -61,6 +61,10 @@ struct HipEngine {
     // step runs scan match -> resample -> map update through the calls above
     decltype(&lama_hip_pf_match_and_map) pf_match_and_map = nullptr;
     decltype(&lama_hip_pf_step_groups) pf_step_groups = nullptr;
+    // dense grids of a map (getOccupancyGrid / getDistanceGrid of the host classes); optional in the same way: those methods throw
+    // on a library without them
+    decltype(&lama_hip_map_bounds) map_bounds = nullptr;
+    decltype(&lama_hip_map_rasterize) map_rasterize = nullptr;
     ~HipEngine();
 };
 

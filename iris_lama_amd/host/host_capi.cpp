@@ -1048,4 +1048,85 @@ int lama_mapbuilder_match_solve(lama_mapbuilder* h, const double* pts, uint32_t 
     } catch (const std::exception& e) { h->error = e.what(); return -2; }
 }
 
+}   // extern "C"
+// ---- dense grids (include/lama/sdm/grid.h) of the classes above ----
+namespace {
+thread_local std::vector<uint8_t> g_grid_data;              // the pixels of the last grid made on this thread (lama_grid_fetch)
+lama::sdm::GridOptions grid_options(const lama_grid_options* o)
+{
+    lama::sdm::GridOptions g;
+    if (o) {
+        g.stride = o->stride; g.probability = o->probability != 0; g.whole_map = o->whole_map != 0;
+        g.world_min = Vector2d(o->world_min[0], o->world_min[1]); g.world_max = Vector2d(o->world_max[0], o->world_max[1]);
+    }
+    return g;
+}
+template <class T>
+void grid_keep(const lama::sdm::GridHeader& g, double max_distance, const std::vector<T>& pixels, lama_grid* out)
+{
+    out->x0 = g.x0; out->y0 = g.y0; out->width = g.width; out->height = g.height; out->stride = g.stride; out->element_bytes = (uint32_t)sizeof(T);
+    out->resolution = g.resolution; out->cell_size = g.cell_size; out->max_distance = max_distance;
+    for (int k = 0; k < 3; ++k) out->origin[k] = g.origin[k];
+    g_grid_data.resize(pixels.size() * sizeof(T));
+    if (!pixels.empty()) std::memcpy(g_grid_data.data(), pixels.data(), g_grid_data.size());
+}
+// 1: the grid was made (header in *out, pixels kept for lama_grid_fetch), 0: the object has no such map (yet / here), -2: failure
+template <class H, class F>
+int occupancy_grid_of(H* h, const lama_grid_options* o, lama_grid* out, F&& get)
+{
+    try {
+        lama::sdm::OccupancyGrid g;
+        if (!get(g, grid_options(o))) return 0;
+        grid_keep(g, 0.0, g.data, out);
+        return 1;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+template <class H, class F>
+int distance_grid_of(H* h, const lama_grid_options* o, lama_grid* out, F&& get)
+{
+    try {
+        lama::sdm::DistanceGrid g;
+        if (!get(g, grid_options(o))) return 0;
+        grid_keep(g, g.max_distance, g.sqdist, out);
+        return 1;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+}
+extern "C" {
+void lama_grid_default_options(lama_grid_options* o)
+{
+    const lama::sdm::GridOptions d;
+    o->stride = d.stride; o->probability = d.probability ? 1 : 0; o->whole_map = d.whole_map ? 1 : 0;
+    o->world_min[0] = o->world_min[1] = o->world_max[0] = o->world_max[1] = 0.0;
+}
+int64_t lama_grid_fetch(void* out, uint64_t cap_bytes)
+{
+    if (out && cap_bytes >= g_grid_data.size() && !g_grid_data.empty()) std::memcpy(out, g_grid_data.data(), g_grid_data.size());
+    return (int64_t)g_grid_data.size();
+}
+int lama_slam_occupancy_grid(lama_slam* h, const lama_grid_options* o, lama_grid* out)
+{ return occupancy_grid_of(h, o, out, [h](lama::sdm::OccupancyGrid& g, const lama::sdm::GridOptions& go) { return h->s->getOccupancyGrid(g, go); }); }
+int lama_slam_distance_grid(lama_slam* h, const lama_grid_options* o, lama_grid* out)
+{ return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->s->getDistanceGrid(g, go); }); }
+int lama_pf_occupancy_grid(lama_pf* h, int64_t particle, const lama_grid_options* o, lama_grid* out)
+{
+    return occupancy_grid_of(h, o, out, [h, particle](lama::sdm::OccupancyGrid& g, const lama::sdm::GridOptions& go) {
+        return particle < 0 ? h->pf->getOccupancyGrid(g, go) : h->pf->getParticleOccupancyGrid((size_t)particle, g, go); });
+}
+int lama_pf_distance_grid(lama_pf* h, int64_t particle, const lama_grid_options* o, lama_grid* out)
+{
+    return distance_grid_of(h, o, out, [h, particle](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) {
+        return particle < 0 ? h->pf->getDistanceGrid(g, go) : h->pf->getParticleDistanceGrid((size_t)particle, g, go); });
+}
+int lama_mapbuilder_occupancy_grid(lama_mapbuilder* h, const lama_grid_options* o, lama_grid* out)
+{ return occupancy_grid_of(h, o, out, [h](lama::sdm::OccupancyGrid& g, const lama::sdm::GridOptions& go) { return h->b->getOccupancyGrid(g, go); }); }
+int lama_mapbuilder_distance_grid(lama_mapbuilder* h, const lama_grid_options* o, lama_grid* out)
+{ return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->b->getDistanceGrid(g, go); }); }
+int lama_lo_occupancy_grid(lama_lo* h, const lama_grid_options* o, lama_grid* out)
+{ return occupancy_grid_of(h, o, out, [h](lama::sdm::OccupancyGrid& g, const lama::sdm::GridOptions& go) { return h->l->getOccupancyGrid(g, go); }); }
+int lama_lo_distance_grid(lama_lo* h, const lama_grid_options* o, lama_grid* out)
+{ return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->l->getDistanceGrid(g, go); }); }
+int lama_loc_distance_grid(lama_loc* h, const lama_grid_options* o, lama_grid* out)
+{ return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->l.getDistanceGrid(g, go); }); }
+
 } // extern "C"

@@ -671,6 +671,32 @@ bool PFSlam2D::downloadOccupancyMap(std::vector<uint64_t>& ids, std::vector<uint
     return has_first_scan && downloadParticleOccupancyMap(getBestParticleIdx(), ids, cells, masks);
 }
 
+bool PFSlam2D::getParticleOccupancyGrid(size_t i, sdm::OccupancyGrid& grid, const sdm::GridOptions& options) const
+{
+    if (!has_first_scan || i >= particles_.size()) return false;
+    if (group_) return ownerOf((uint32_t)i)->getParticleOccupancyGrid(i, grid, options);
+    if (!ownsParticle((uint32_t)i)) return false;
+    return dev_.occupancyGrid((uint32_t)i - lo_, options_.resolution, grid, options);
+}
+
+bool PFSlam2D::getParticleDistanceGrid(size_t i, sdm::DistanceGrid& grid, const sdm::GridOptions& options) const
+{
+    if (!has_first_scan || i >= particles_.size()) return false;
+    if (group_) return ownerOf((uint32_t)i)->getParticleDistanceGrid(i, grid, options);
+    if (!ownsParticle((uint32_t)i)) return false;
+    return dev_.distanceGrid((uint32_t)i - lo_, options_.resolution, options_.l2_max, grid, options);
+}
+
+bool PFSlam2D::getOccupancyGrid(sdm::OccupancyGrid& grid, const sdm::GridOptions& options) const
+{
+    return has_first_scan && getParticleOccupancyGrid(getBestParticleIdx(), grid, options);
+}
+
+bool PFSlam2D::getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options) const
+{
+    return has_first_scan && getParticleDistanceGrid(getBestParticleIdx(), grid, options);
+}
+
 std::shared_ptr<const FrequencyOccupancyMap> PFSlam2D::getParticleOccupancyMap(size_t i) const
 {
     sdm::HostMap m;
