@@ -213,7 +213,11 @@ int32_t lama_hip_ctx_device(const lama_hip_ctx* ctx);
 /* Patch bookkeeping for transient maps (LidarOdometry2D::updateMaps, src/lidar_odometry_2d.cpp:128-199):
  *   lama_hip_pf_patch_ids     : Map::visit_all_patches -- the reference patch indices (Map::m2p) of the allocated patches;
  *   lama_hip_pf_delete_patches: Map::deletePatchAt (src/sdm/map.cpp:465-488) on BOTH maps of the particle for every listed patch
- *                               index (absent patches are skipped); the arenas stay dense.  *deleted = distance-map patches removed. */
+ *                               index (absent patches, duplicates and indices outside the window are skipped); the arenas stay dense.
+ *                               *deleted = distance-map patches removed.  Cells of the surviving patches keep their obstacle offsets
+ *                               into a deleted patch, as the reference's do; from the first removed distance-map patch on, the
+ *                               context's brushfire re-creates such a patch when it reads the obstacle cell ("What a
+ *                               deletion leaves behind"). */
 int32_t lama_hip_pf_patch_ids(lama_hip_ctx* ctx, uint32_t particle, int32_t kind, uint32_t cap, uint64_t* patch_ids, uint32_t* num_patches);
 /* One 64-bit checksum per particle of its distance / occupancy map, computed on the device: order-independent sum over the
  * allocated patches (reference patch indices, Map::m2p) and their cells of a hash of what the reference stores per cell

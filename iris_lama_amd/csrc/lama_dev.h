@@ -143,6 +143,7 @@ struct DevParams {
     uint32_t occ_policy, ray_rule;
     uint32_t strategy;     // 0 = GaussNewton, 1 = LevenbergMarquard (cfg.solver_strategy; Slam2D / Loc2D "lm")
     double lo_miss, lo_hit, lo_min, lo_max;   // ProbabilisticOccupancyMap parameters (float-rounded, as the reference stores them)
+    uint32_t ghosts;       // 1 = distance-map patches of this context have been deleted: obstacle offsets may dangle (k_brushfire, obstacle_get)
 };
 
 // A block of at most ARG_BLOCK particles (a group of the grouped step schedule) brings the small tables the host rewrites before every

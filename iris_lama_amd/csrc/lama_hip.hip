@@ -198,6 +198,8 @@ struct lama_hip_ctx {
     size_t ev_used = 0;
     bool initialised = false;   // first scan done
     bool poisoned = false;      // a resample ran out of device memory half-way: every later call fails (LAMA_HIP_E_STATE)
+    bool dm_deleted = false;    // lama_hip_pf_delete_patches has removed a distance-map patch: obstacle offsets of the cells around it may
+                                // dangle from now on (DevParams::ghosts; sticky: the offsets outlive any number of updates)
 
     uint32_t P = 0, W = 0, WC = 0, wx0 = 0, wy0 = 0;
     uint32_t max_sqdist = 0;
@@ -367,8 +369,13 @@ void host_scan_tf(const double* pose4, const Affine& m, double* out12)
     }
 }
 
-// how many patches beyond an obstacle's own the brushfire can reach (and allocate): ceil(l2_max / resolution) + 1 cells
-uint32_t guard_radius(const lama_hip_ctx* c) { return ((uint32_t)std::ceil(std::sqrt((double)c->max_sqdist)) + 1u + 31u) / 32u; }
+// how many patches beyond an obstacle's own the brushfire can reach (and allocate): ceil(l2_max / resolution) + 1 cells.  After a
+// deletion it can also re-create the patch of an obstacle cell that a cell in that reach still points at: as many cells again.
+uint32_t guard_radius(const lama_hip_ctx* c)
+{
+    const uint32_t r = (uint32_t)std::ceil(std::sqrt((double)c->max_sqdist));
+    return ((c->dm_deleted ? 2u * r + 1u : r) + 1u + 31u) / 32u;
+}
 
 DevParams make_params(const lama_hip_ctx* c)
 {
@@ -391,6 +398,7 @@ DevParams make_params(const lama_hip_ctx* c)
     // float argument, stored in double members
     auto logods = [](float prob) { return (double)(float)std::log(prob / (1.0 - prob)); };
     p.lo_miss = logods(0.4f); p.lo_hit = logods(0.7f); p.lo_min = logods(0.12f); p.lo_max = logods(0.97f);
+    p.ghosts = c->dm_deleted ? 1u : 0u;
     return p;
 }
 
@@ -2126,6 +2134,7 @@ int32_t lama_hip_pf_delete_patches(lama_hip_ctx* c, uint32_t particle, const uin
             --count;
             touched = true;
             if (dm && deleted) ++*deleted;
+            if (dm) c->dm_deleted = true;
         }
         if (touched) {
             HIPCHK(c, hipMemcpyAsync(d_dir, dir.data(), WW * 2, hipMemcpyHostToDevice, c->stream));

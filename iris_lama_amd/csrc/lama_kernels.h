@@ -856,7 +856,9 @@ __global__ __launch_bounds__(UM_BLOCK) void k_raycast(DevParams prm, const doubl
 // Which get() calls of the reference have side effects (patch allocation + mask bit, src/sdm/map.cpp:371-412)?
 //   - the popped cell: none (it was get()-ed when it was queued);
 //   - obstacle cells reached through a valid cell's offset: none (an obstacle was get()-ed when it was added;
-//     a cleared cell has offset 0 = itself);
+//     a cleared cell has offset 0 = itself) -- UNLESS patches have been deleted (lama_hip_pf_delete_patches): an offset
+//     may then point into a patch that is gone, or into one that came back without that cell, and the read brings the
+//     patch and the cell's mask bit back.  prm.ghosts says so; every pop then takes the general code (obstacle_get);
 //   - the neighbours: YES -- all four in raise(), and in lower() those that pass the "away from the obstacle"
 //     test, and only when lower() really runs.  They are prefetched side-effect free and the allocation /
 //     mask update is applied once the decision is known.
@@ -1236,7 +1238,9 @@ __device__ __forceinline__ bool lds_push_list(uint64_t* heap, uint32_t& n, const
 // Which get() calls of the reference have side effects (patch allocation + mask bit, src/sdm/map.cpp:371-412)?
 //   - the popped cell: none (it was get()-ed when it was queued);
 //   - obstacle cells reached through a valid cell's offset: none (an obstacle was get()-ed when it was added;
-//     a cleared cell has offset 0 = itself);
+//     a cleared cell has offset 0 = itself) -- UNLESS patches have been deleted (lama_hip_pf_delete_patches): an offset
+//     may then point into a patch that is gone, or into one that came back without that cell, and the read brings the
+//     patch and the cell's mask bit back.  prm.ghosts says so; every pop then takes the general code (obstacle_get);
 //   - the neighbours: YES -- all four in raise(), and in lower() those that pass the "away from the obstacle"
 //     test, and only when lower() really runs.  They are prefetched side-effect free and the allocation /
 //     mask update is applied once the decision is known.
@@ -1374,6 +1378,21 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
         return;
     }
     const DirCache dc{sh.dc, dir, prm.W};
+    // Patches of this context have been deleted: an obstacle offset may dangle.  The reference reads the obstacle cell through the
+    // non-const Map::get (raise() :259, update() :187, the tie of lower() :314), which re-creates the patch, empty, and turns the
+    // cell's mask bit on; so does obstacle_get for the lanes that `want` it (called by the whole wave).  A new patch is all zero,
+    // so what the caller has read of the cell -- nothing: 0 -- stands.
+    const bool ghosts = prm.ghosts != 0u;
+    auto obstacle_get = [&](const bool want, const int gx, const int gy) {
+        const bool in = (uint32_t)gx < prm.WC && (uint32_t)gy < prm.WC;
+        if (want && !in) atomicOr(prm.err, ERR_WINDOW);
+        const bool w = want && in;
+        if (!__ballot(w)) return;
+        const uint32_t gpidx = ((uint32_t)gy >> 5) * prm.W + ((uint32_t)gx >> 5);
+        const uint32_t gci = ((uint32_t)gx & 31u) | (((uint32_t)gy & 31u) << 5);
+        const int gs = coop_slot(dc, dir, count, (int)dm_cap, w, gpidx, ERR_DM_CAP, prm.err);
+        if (w && gs >= 0) atomicOr((unsigned long long*)(mask + (size_t)gs * 16 + (gci >> 6)), 1ull << (gci & 63));
+    };
 
     const int ddx = lane == 0 ? 1 : (lane == 2 ? -1 : 0), ddy = lane == 1 ? 1 : (lane == 3 ? -1 : 0);
     const bool is_cur = lane == 4, is_nb = lane < 4;
@@ -1485,6 +1504,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 if (fresh || !(s & (SV_VALID | SV_QUEUED))) atomicOr((unsigned long long*)(mask + (size_t)slot * 16 + (ci >> 6)), (unsigned long long)bit);
             }
             const bool cand = nbok && !(s & SV_QUEUED) && (s & SV_VALID);        // :253
+            if (ghosts) obstacle_get(cand, ox, oy);                              // :259
             bool ovalid = (os & SV_VALID) != 0;
             bool clear = cand && !ovalid;
             #pragma unroll 1
@@ -1553,7 +1573,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 const unsigned long long rarem = __ballot((rare0 | adj) != 0u);
                 const uint32_t cos_ = (uint32_t)__builtin_amdgcn_readlane((int)s, 5);
                 uint32_t ovalid = (cos_ & SV_VALID) ? 0xFFFFFFFFu : 0u;   // (lanes whose obstacle cell is lane 5's)
-                general = rarem != 0ull;
+                general = (rarem != 0ull) | ghosts;
                 if (!general && __builtin_expect(__ballot(other != 0u) != 0ull, 0)) {
                     const uint32_t oin = opq((other != 0u && (uint32_t)ox < prm.WC && (uint32_t)oy < prm.WC) ? 0xFFFFFFFFu : 0u);
                     const uint32_t opidx = bf_mul24((uint32_t)oy >> 5, prm.W) + ((uint32_t)ox >> 5);
@@ -1654,6 +1674,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
         }
         // :253  skip queued or invalid neighbours
         const bool cand = nbok && !(s & SV_QUEUED) && (s & SV_VALID);
+        if (ghosts) obstacle_get(cand, ox, oy);          // :259
         bool ovalid = (os & SV_VALID) != 0;
         // sequential semantics: neighbour i is handled before j > i; if i gets cleared and j's offset points
         // at i, j must see i as invalid (only possible through stale offsets; replayed here to stay exact)
@@ -1734,6 +1755,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 }
                 cos_ = t;
             }
+            if (ghosts && (cs & SV_VALID)) obstacle_get(is_cur, rx + obs_x(cob), ry + obs_y(cob));      // :187
             // :183-192  valid, its obstacle still has sqdist 0 (valid NOT tested), and lower() :283 still queued
             const bool fire = (cs & SV_VALID) && (cos_ & SV_SQMASK) == 0 && (cs & SV_QUEUED);
             if (!fire) return 0u;
@@ -1758,6 +1780,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 // the neighbour's own obstacle cell: usually the very cell the popped cell points to, whose state lane 5 holds
                 const int ox = x + obs_x(ob), oy = y + obs_y(ob);
                 const bool same = ox == obx && oy == oby;
+                if (ghosts) obstacle_get(tie, ox, oy);                                  // :314
                 sv_t os = cos_;
                 if (__ballot(tie && !same)) {
                     if (tie && !same) {
@@ -1848,7 +1871,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 // (one compare of the packed offsets, one of both flags: this test is scalar code on the chain of every pop)
                 const bool stale = cob != pack_obs(eox, eoy);
                 const bool fire0 = (cs & (uint32_t)(SV_VALID | SV_QUEUED)) == (uint32_t)(SV_VALID | SV_QUEUED);      // :183, lower() :283
-                general = (unk != 0ull) | (fire0 & stale);
+                general = (unk != 0ull) | (fire0 & stale) | ghosts;
                 BFT(1); BFF(1);
 #ifdef LAMA_PROFILE_BF_COUNT
                 prof[2] += unk != 0ull ? 1 : 0; prof[3] += (fire0 & stale) ? 1 : 0; prof[6] += (fire0 & ((cos_ & SV_SQMASK) == 0u)) ? 1 : 0;
@@ -2014,6 +2037,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
             }
             cos_ = t;
         }
+        if (ghosts && (cs & SV_VALID)) obstacle_get(is_cur, rx + obs_x(cob), ry + obs_y(cob));      // :187
         // :183-192  valid, its obstacle still has sqdist 0 (valid NOT tested), and lower() :283 still queued
         const bool fire = (cs & SV_VALID) && (cos_ & SV_SQMASK) == 0 && (cs & SV_QUEUED);
         BFT(3);
@@ -2046,6 +2070,7 @@ __device__ __forceinline__ void bf_particle(const DevParams& prm, const int p_an
                 // reached from the same obstacle), whose state lane 5 already holds -- no second load round then
                 const int ox = x + obs_x(ob), oy = y + obs_y(ob);
                 const bool same = ox == obx && oy == oby;
+                if (ghosts) obstacle_get(tie, ox, oy);                                  // :314
                 sv_t os = cos_;
 #ifdef LAMA_PROFILE_BF_COUNT
                 prof[4] += __ballot(tie && !same) ? 1 : 0;

@@ -175,6 +175,11 @@ void orc_occ_bounds(void* h, uint32_t* mn3, uint32_t* mx3, double* wmn3, double*
 void orc_dm_bounds(void* h, uint32_t* mn3, uint32_t* mx3, double* wmn3, double* wmx3) { map_bounds((const DynamicDistanceMap*)h, mn3, mx3, wmn3, wmx3); }
 int64_t orc_occ_cells(void* h, uint32_t* xy, uint64_t cap) { return map_cells((const FrequencyOccupancyMap*)h, xy, cap); }
 int64_t orc_dm_cells(void* h, uint32_t* xy, uint64_t cap) { return map_cells((const DynamicDistanceMap*)h, xy, cap); }
+// Map::deletePatchAt of the patch with the reference index `patch_id` (Map::m2p): 1 if it was there
+static int map_delete_patch(Map* m, uint64_t patch_id) { return m->deletePatchAt(m->p2m(patch_id)) ? 1 : 0; }
+int orc_dm_delete_patch(void* h, uint64_t patch_id) { return map_delete_patch((DynamicDistanceMap*)h, patch_id); }
+int orc_occ_delete_patch(void* h, uint64_t patch_id) { return map_delete_patch((FrequencyOccupancyMap*)h, patch_id); }
+int orc_pocc_delete_patch(void* h, uint64_t patch_id) { return map_delete_patch((ProbabilisticOccupancyMap*)h, patch_id); }
 int orc_occ_patch_ids(void* h, uint64_t* ids, int cap) { return patch_ids((const FrequencyOccupancyMap*)h, ids, cap); }
 int orc_occ_patch_read(void* h, uint64_t id, uint8_t* cells, uint64_t* mask) { return patch_read((const FrequencyOccupancyMap*)h, id, cells, mask); }
 
@@ -554,6 +559,15 @@ void orc_lo_set_odom(void* h, const double* pose4) { ((LoBox*)h)->l->odom = se2_
 void* orc_lo_dm(void* h) { return &((LoBox*)h)->l->dm(); }
 void* orc_lo_occ(void* h) { return &((LoBox*)h)->l->occ(); }
 uint32_t orc_lo_deleted_last(void* h) { return ((LoBox*)h)->l->deleted_last; }
+// LidarOdometry2D::updateMaps at a given pose, without the scan match; prune != 0: with its transient-map step
+uint32_t orc_lo_update_maps_at(void* h, const double* pts, int n, const double* origin3, const double* quat4, const double* pose4, int prune)
+{
+    LoBox* b = (LoBox*)h;
+    b->scan = make_scan(pts, n, origin3, quat4);
+    b->l->updateMapsAt(b->scan, se2_of(pose4), prune != 0);
+    b->l->map_update_odom = b->l->odom;
+    return b->l->deleted_last;
+}
 uint32_t orc_lo_map_updates(void* h) { return ((LoBox*)h)->l->map_updates; }
 uint32_t orc_lo_iterations(void* h) { return ((LoBox*)h)->l->last_solve.iterations; }
 int orc_pocc_patch_ids(void* h, uint64_t* ids, int cap) { return patch_ids((const ProbabilisticOccupancyMap*)h, ids, cap); }

@@ -79,6 +79,8 @@ def lib():
             "orc_lo_deleted_last": (u32, [vp]), "orc_lo_map_updates": (u32, [vp]), "orc_lo_iterations": (u32, [vp]),
             "orc_pocc_patch_ids": (i32, [vp, vp, i32]), "orc_pocc_patch_read": (i32, [vp, u64, vp, vp]), "orc_pocc_free": (None, [vp]),
             "orc_pocc_params": (None, [vp]),
+            "orc_dm_delete_patch": (i32, [vp, u64]), "orc_occ_delete_patch": (i32, [vp, u64]), "orc_pocc_delete_patch": (i32, [vp, u64]),
+            "orc_lo_update_maps_at": (u32, [vp, vp, i32, vp, vp, vp, i32]),
             "orc_pgo_linearize": (None, [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
             "orc_map_write": (i32, [vp, C.c_char_p]), "orc_map_read": (i32, [vp, C.c_char_p]),
             "orc_map_image": (i32, [vp, i32, vp, vp, vp, C.c_uint64]),
@@ -193,6 +195,10 @@ class _MapBase:
         r = getattr(lib(), self._pre + "_patch_read")(self.h, int(pid), _p(cells), _p(mask))
         assert r == cells.nbytes, r
         return cells, mask
+
+    def delete_patch(self, pid):
+        """Map::deletePatchAt of the patch with the id `pid`: True if it was there"""
+        return bool(getattr(lib(), self._pre + "_delete_patch")(self.h, int(pid)))
 
     def dump(self):
         """{patch_id: (cells[1024], mask[16])}"""
@@ -312,6 +318,11 @@ class LidarOdometry:
     def update(self, pts, ts=0.0, origin=ZERO3, quat=IDENT_Q):
         pts = np.ascontiguousarray(pts, dtype=np.float64)
         return bool(lib().orc_lo_update(self.h, _p(pts), len(pts), _p(origin), _p(quat), ts))
+
+    def update_maps_at(self, pts, pose4, prune=False, origin=ZERO3, quat=IDENT_Q):
+        """LidarOdometry2D::updateMaps of the scan at `pose4`, no scan match; prune: with the transient-map step -> patches it deleted"""
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        return lib().orc_lo_update_maps_at(self.h, _p(pts), len(pts), _p(origin), _p(quat), _p(np.ascontiguousarray(pose4, dtype=np.float64)), 1 if prune else 0)
 
     def odom(self):
         out = np.zeros(4)

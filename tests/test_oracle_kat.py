@@ -241,3 +241,39 @@ def test_gn_recovers_pose_offset_on_wall_map():
     assert abs(pose[2] - 2.0) < 5e-3 and abs(pose[3] - 3.0) < 5e-3
     assert abs(math.atan2(pose[1], pose[0]) - th) < 2e-3
     assert O.loglik(dm, pts, pose) > O.loglik(dm, pts, start)
+
+
+def test_delete_patch_of_an_absent_and_of_a_present_patch():
+    """Map::deletePatchAt through the oracle's C API (all three map classes share Map's): false for a patch that is not there, true
+    for one that is, which patch_ids() then no longer lists; the other patches stay as they were."""
+    dm, occ = O.DM.new(), O.Occ.new()
+    dm.add(OFF + 3, OFF + 3)
+    dm.add(OFF + 40, OFF + 3)
+    occ.set_occupied(OFF + 3, OFF + 3)
+    here, there, absent = 1321122 * 2642244 + 1321122, 1321123 * 2642244 + 1321122, 1321122 * 2642244 + 1321123
+    assert dm.patch_ids().tolist() == [here, there] and occ.patch_ids().tolist() == [here]
+    assert not dm.delete_patch(absent) and not occ.delete_patch(there)
+    kept = dm.patch(there)
+    assert dm.delete_patch(here) and dm.patch_ids().tolist() == [there]
+    assert all(np.array_equal(a, b) for a, b in zip(dm.patch(there), kept))
+    assert not dm.delete_patch(here)
+    assert occ.delete_patch(here) and occ.patch_ids().tolist() == []
+
+
+def test_update_maps_at_of_a_first_scan_is_the_first_update():
+    """orc_lo_update_maps_at with the transient step at the start pose is LidarOdometry2D::update of a first scan; without the
+    step it deletes nothing and leaves the same maps (a first scan lies within its own box)."""
+    th = np.linspace(-2.0, 2.0, 90)
+    pts = np.stack([2.5 * np.cos(th), 2.5 * np.sin(th), np.zeros_like(th)], 1)
+    a, b, c = O.LidarOdometry(), O.LidarOdometry(), O.LidarOdometry()
+    assert a.update(pts, 0.0)
+    assert b.update_maps_at(pts, O.se2(0.0, 0.0, 0.0), prune=True) == a.deleted_last() == 0
+    assert c.update_maps_at(pts, O.se2(0.0, 0.0, 0.0), prune=False) == 0
+    for o in (b, c):
+        for x, y in ((a.dm().dump(), o.dm().dump()), (a.occ().dump(), o.occ().dump())):
+            assert sorted(x) == sorted(y) and len(x) >= 4
+            assert all(x[k][0].tobytes() == y[k][0].tobytes() and np.array_equal(x[k][1], y[k][1]) for k in x)
+        assert o.map_updates() == 1 and np.array_equal(o.odom(), a.odom())
+    # ... and the pocc handle deletes like the others
+    pid = int(c.occ().patch_ids()[0])
+    assert c.occ().delete_patch(pid) and pid not in c.occ().patch_ids().tolist() and not c.occ().delete_patch(pid)
