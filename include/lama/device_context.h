@@ -15,6 +15,9 @@ namespace lama {
 
 struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
 namespace sdm { struct GridOptions; struct OccupancyGrid; struct DistanceGrid; }      // include/lama/sdm/grid.h
+namespace sdm { struct RayCastOptions; struct RayCastResult; }                        // include/lama/sdm/ray_cast.h
+struct Pose2D;
+struct PointCloudXYZ;
 
 class DeviceContext {
 public:
@@ -48,6 +51,12 @@ public:
     // stride of 0 or a world box whose max lies below its min.
     bool occupancyGrid(uint32_t particle, double resolution, sdm::OccupancyGrid& grid, const sdm::GridOptions& options) const;
     bool distanceGrid(uint32_t particle, double resolution, double l2_max, sdm::DistanceGrid& grid, const sdm::GridOptions& options) const;
+    // What a sensor at each pose would see in one particle's device map (lama_hip_map_cast_rays, include/lama/sdm/ray_cast.h): the
+    // first cell of every beam of `surface` that stops the ray, ranges included.  false without a context.  Throws
+    // std::runtime_error when the device library lacks the entry point or refuses the call (no pose, no point, a beam of more than
+    // 8191 cells, stop_at_unknown on the distance map, ...).  No map, pose or snapshot changes.
+    bool castRays(uint32_t particle, double resolution, const std::vector<Pose2D>& poses, const PointCloudXYZ& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options) const;
 
 private:
     std::shared_ptr<HipEngine> eng_;

@@ -17,6 +17,7 @@
 #include "device_context.h"
 #include "pose2d.h"
 #include "sdm/grid.h"
+#include "sdm/ray_cast.h"
 #include "sdm_io.h"
 
 namespace lama {
@@ -49,6 +50,11 @@ struct LidarOdometry2D {
     { return device_initialised_ && dev_.occupancyGrid(0, opt_.resolution, grid, options); }
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
     { return device_initialised_ && dev_.distanceGrid(0, opt_.resolution, 1.0, grid, options); }
+    // What a sensor at each of `poses` would see in the device map (lama/sdm/ray_cast.h): per pose and point of `surface` the first
+    // cell that stops the beam, made on the device.  false before the first scan.  No snapshot is made or dropped.
+    bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
+    { return device_initialised_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options); }
     uint32_t getLastIterations() const { return last_iterations_; }
     uint32_t getLastDeletedPatches() const { return last_deleted_; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }

@@ -23,6 +23,7 @@
 #include "pose2d.h"
 #include "sdm/dynamic_distance_map.h"
 #include "sdm/grid.h"
+#include "sdm/ray_cast.h"
 #include "sdm/simple_occupancy_map.h"
 
 namespace lama {
@@ -75,6 +76,17 @@ public:
     // (occupancy_map is a host map: walk it on the host.)
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
     { return dev_ && dev_.distanceGrid(0, opt_.resolution, opt_.l2_max, grid, options); }
+    // What a sensor at each of `poses` would see in the DEVICE distance map (lama/sdm/ray_cast.h; the occupancy map is a host map, so
+    // options.map must be kRayDistanceMap: a beam stops at the first obstacle cell).  Obstacles added since the last update() are
+    // brought in first.  false while there is no device map yet.
+    bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options = distanceRays());
+    // The scan checked against the map at the current pose, one RayLabel per point: kRayAgrees (it ends within tolerance_cells of a
+    // mapped obstacle), kRayBlocked (it passes through a mapped obstacle more than tolerance_cells before its end: the pose is off or
+    // the map is stale), kRayNovel (it ends where the map has nothing: a person, a moved pallet -- points to drop before matching).
+    // Empty while there is no device map yet.
+    std::vector<uint8_t> checkScan(const PointCloudXYZ::Ptr& surface, int32_t tolerance_cells = 2);
+    static sdm::RayCastOptions distanceRays() { sdm::RayCastOptions o; o.map = sdm::kRayDistanceMap; return o; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }
 

@@ -22,6 +22,7 @@
 #include "device_context.h"
 #include "pose2d.h"
 #include "sdm/grid.h"
+#include "sdm/ray_cast.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -73,6 +74,11 @@ public:
     { return has_map_ && dev_.occupancyGrid(0, opt_.resolution, grid, options); }
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
     { return has_map_ && opt_.l2_max > 0.0 && dev_.distanceGrid(0, opt_.resolution, opt_.l2_max, grid, options); }
+    // What a sensor at each of `poses` would see in the device map (lama/sdm/ray_cast.h): per pose and point of `surface` the first
+    // cell that stops the beam, made on the device.  false before the first build.  No snapshot is made or dropped.
+    bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
+    { return has_map_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options); }
 
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }

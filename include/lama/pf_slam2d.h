@@ -32,6 +32,7 @@
 #include "device_context.h"
 #include "pose2d.h"
 #include "sdm/grid.h"
+#include "sdm/ray_cast.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -188,6 +189,12 @@ public:
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
     bool getParticleOccupancyGrid(size_t i, sdm::OccupancyGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
     bool getParticleDistanceGrid(size_t i, sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const;
+    // What a sensor at each of `poses` would see in the best particle's / in particle i's device map (lama/sdm/ray_cast.h), made on
+    // the shard that holds the particle.  false where the grid methods return false.
+    bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options = sdm::RayCastOptions()) const;
+    bool castParticleRays(size_t i, const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                          const sdm::RayCastOptions& options = sdm::RayCastOptions()) const;
 
     // ------------------------------------------------------------------ step-wise API (sharded operation)
     enum Phase { kNoUpdate = 0, kFirstScan = 1, kMatched = 2 };

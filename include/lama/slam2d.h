@@ -17,6 +17,7 @@
 #include "device_context.h"
 #include "pose2d.h"
 #include "sdm/grid.h"
+#include "sdm/ray_cast.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -110,6 +111,11 @@ public:
     { return has_first_scan && dev_.occupancyGrid(0, resolution_, grid, options); }
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
     { return has_first_scan && dev_.distanceGrid(0, resolution_, l2_max_, grid, options); }
+    // What a sensor at each of `poses` would see in the device map (lama/sdm/ray_cast.h): per pose and point of `surface` the first
+    // cell that stops the beam, made on the device.  false before the first scan.  No snapshot is made or dropped.
+    bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                  const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
+    { return has_first_scan && surface && dev_.castRays(0, resolution_, poses, *surface, result, options); }
     // include/lama/slam2d.h:157-161
     void saveOccImage(const std::string& name) const { const FrequencyOccupancyMap* m = getOccupancyMap(); if (m) sdm::export_to_png(m->snapshot(), name); }
     void saveDistImage(const std::string& name) const { const DynamicDistanceMap* m = getDistanceMap(); if (m) sdm::export_to_png(m->snapshot(), name); }

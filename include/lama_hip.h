@@ -397,6 +397,49 @@ int32_t lama_hip_map_bounds(lama_hip_ctx* ctx, uint32_t particle, int32_t kind, 
 int32_t lama_hip_map_rasterize(lama_hip_ctx* ctx, uint32_t particle, int32_t layer, uint32_t x0, uint32_t y0,
                                uint32_t width, uint32_t height, uint32_t stride, void* out, uint64_t out_bytes);
 
+/* What a sensor at each of num_poses poses WOULD see in `particle`'s device map of `kind` (LAMA_HIP_MAP_*): per (pose, beam) the first
+ * cell that stops the ray (csrc/lama_raycast_query.h), one lane each -- the expected ranges of a beam model, a scan check (which beams
+ * of a real scan agree with the map, which pass through a mapped obstacle, which end in mapped free space), visibility gating of many
+ * candidate poses at once.  Inputs as for lama_hip_map_integrate_scans: poses4 [num_poses][4] {c, s, tx, ty}; pts_xyz [n][3], the
+ * SAME n points for every pose (a fan of max_range, or a real scan); one sensor mount (NULL: zero / identity).
+ * A beam's cells are the map update's: tf = T(pose) * T(sensor origin) * R(sensor orientation) composed on the host, start cell
+ * w2m(tf.translation()), hit cell w2m(tf * p) (PFSlam2D::updateParticleMaps, src/pf_slam2d.cpp:458-493, with no truncated_ray /
+ * truncated_range, as in the map rebuild: the question is about the whole beam), then the SEQUENCE Map::computeRay(start, hit) in
+ * order followed by the hit cell: nn entries, nn = the largest cell delta over the three axes, none when start == hit.  The start
+ * cell is never tested.  The ray stops at the first entry that is
+ *   occupancy map, frequency cells (cfg.occupancy_policy 0): visited != 0 and 4 * occupied > visited;  log-odds cells (policy 1): mask
+ *     bit on and l > 0;  with LAMA_HIP_RAY_STOP_UNKNOWN in `flags` also at an unknown cell: visited == 0, 4 * occupied == visited,
+ *     mask bit off or l == 0, a cell in an absent patch, a cell outside the map window;
+ *   distance map: the cell is present, valid_obstacle is set and the stored squared distance is 0 -- an obstacle cell (the only device
+ *     map of lama::Loc2D).  LAMA_HIP_RAY_STOP_UNKNOWN has no meaning there and is refused.
+ * The same exact integer rules as lama_hip_map_rasterize.  Outputs, [num_poses][n] each, every one but `status` may be NULL:
+ *   status uint8       LAMA_HIP_RAY_NONE / _OCCUPIED / _UNKNOWN;
+ *   step int32         0-based index into the sequence, -1 for NONE;             nn uint32: the beam's step count;
+ *   cell_xy uint32[2]  the stopping cell; the hit cell where nothing stopped the ray;
+ *   end_sqdist uint32  the distance map's squared distance in cells at the HIT cell, the context's max_sqdist where that cell is
+ *                      absent or has no valid obstacle (always, on a context without a distance map);
+ *   label uint8        written when tolerance_cells >= 0: LAMA_HIP_RAY_BLOCKED where status is OCCUPIED and nn - 1 - step >
+ *                      tolerance_cells (the map has an obstacle in front of the measured end point); else LAMA_HIP_RAY_AGREES where
+ *                      end_sqdist <= tolerance_cells^2; else LAMA_HIP_RAY_NOVEL (the beam ends where the map has nothing).
+ * No range is formed in floating point on the device: start_xy [num_poses][2] (may be NULL) is the start cell of each pose's beams, and
+ * a caller takes resolution * sqrt(dx * dx + dy * dy) of the stopping cell's integer offset from it.  kernel_ms (may be NULL): device
+ * time of the launch.  No map, pose or counter of the context changes; like every entry point the call first waits for queued
+ * map updates.  LAMA_HIP_E_INVALID, found before anything is uploaded and with every output untouched: n == 0 or num_poses == 0, a
+ * NULL status, a non-finite point, pose or mount, a particle out of range, an unknown kind or flag, LAMA_HIP_RAY_STOP_UNKNOWN on the
+ * distance map, num_poses * n >= 2^31, a start or hit cell outside the 32-bit range of map cell coordinates.  LAMA_HIP_E_WINDOW, in
+ * the same way: a beam of more than 8191 steps (the map update's own limit).  Scans of any n are accepted. */
+#define LAMA_HIP_RAY_STOP_UNKNOWN 1u
+#define LAMA_HIP_RAY_NONE     0
+#define LAMA_HIP_RAY_OCCUPIED 1
+#define LAMA_HIP_RAY_UNKNOWN  2
+#define LAMA_HIP_RAY_AGREES   0
+#define LAMA_HIP_RAY_BLOCKED  1
+#define LAMA_HIP_RAY_NOVEL    2
+int32_t lama_hip_map_cast_rays(lama_hip_ctx* ctx, uint32_t particle, int32_t kind, uint32_t num_poses, const double* poses4,
+                               const double* pts_xyz, uint32_t n, const double* sensor_origin3, const double* sensor_quat_wxyz,
+                               uint32_t flags, int32_t tolerance_cells, uint8_t* status, int32_t* step, uint32_t* nn,
+                               uint32_t* cell_xy, uint32_t* end_sqdist, uint8_t* label, uint32_t* start_xy, double* kernel_ms);
+
 /* Particle shipping for multi-GPU resampling (one context per GPU): serialise one particle (pose + both
  * maps, used patches only) into a DEVICE buffer / restore it into slot `particle` of this context.
  * export returns the number of bytes needed in *bytes when buf == NULL. */

@@ -345,6 +345,40 @@ int lama_mapbuilder_distance_grid(lama_mapbuilder* b, const lama_grid_options* o
 int lama_lo_occupancy_grid(lama_lo* l, const lama_grid_options* options, lama_grid* out);
 int lama_lo_distance_grid(lama_lo* l, const lama_grid_options* options, lama_grid* out);
 int lama_loc_distance_grid(lama_loc* l, const lama_grid_options* options, lama_grid* out);
+/* ---- ray casts (include/lama/sdm/ray_cast.h): castRays of the classes above -- what a sensor at each of num_poses poses {c, s, tx, ty}
+ * would see in the object's device map, per pose and point of the scan the first cell that stops the beam.  options NULL: the defaults
+ * (occupancy map -- lama_loc_*: the distance map, the only one it has on the device --, unknown cells do not stop a beam, no labels).
+ * Every array of *out may be NULL; the others hold num_poses * n elements (cell_xy twice as many, start_xy 2 * num_poses), label is
+ * written with tolerance_cells >= 0 only, range is in metres (+inf where nothing stopped the beam).  Returns 1 when the rays were cast,
+ * 0 when the object has no such map (before the first scan / build, a particle of another process), -2 on a failure (message through
+ * the object's last_error: a device library without lama_hip_map_cast_rays, a beam of more than 8191 cells, ...).  lama_pf_*:
+ * particle < 0 is the best particle.  lama_loc_check_scan: Loc2D::checkScan -- one label per point (0 agrees, 1 blocked, 2 novel) at the
+ * current pose; returns their number, 0 while there is no device map, -2 on a failure. */
+typedef struct lama_ray_options {
+    int32_t map;                 /* 0 distance map, 1 occupancy map (LAMA_HIP_MAP_*) */
+    int32_t stop_at_unknown;     /* occupancy map only */
+    int32_t tolerance_cells;     /* >= 0: label the beams */
+} lama_ray_options;
+typedef struct lama_ray_result {
+    uint8_t* status; int32_t* step; uint32_t* nn; uint32_t* cell_xy; uint32_t* end_sqdist; uint8_t* label; uint32_t* start_xy; double* range;
+} lama_ray_result;
+void lama_ray_default_options(lama_ray_options* o);
+/* the host loop a caller had before castRays, for comparison (tools/raycast_query_bench.py): getOccupancyMap()'s snapshot walked per
+ * pose and point from the sensor's cell to the point's, isOccupied per cell; step_out [num_poses][n]: the index of the first occupied
+ * cell, -1 for none.  Returns 0, -1 before the first scan, -2 on a failure. */
+int lama_slam_view_cast_rays(lama_slam* s, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, int32_t* step_out);
+int lama_slam_cast_rays(lama_slam* s, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, const double* origin3,
+                        const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
+int lama_pf_cast_rays(lama_pf* pf, int64_t particle, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, const double* origin3,
+                      const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
+int lama_mapbuilder_cast_rays(lama_mapbuilder* b, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, const double* origin3,
+                              const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
+int lama_lo_cast_rays(lama_lo* l, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, const double* origin3,
+                      const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
+int lama_loc_cast_rays(lama_loc* l, const double* poses4, uint32_t num_poses, const double* pts_xyz, uint32_t n, const double* origin3,
+                       const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
+int64_t lama_loc_check_scan(lama_loc* l, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz, int32_t tolerance_cells,
+                            uint8_t* labels_out);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

@@ -20,6 +20,7 @@
 #include "lama_pgo_pcg.h"
 #include "lama_map_build.h"
 #include "lama_raster.h"
+#include "lama_raycast_query.h"
 #include "lama_match_batch.h"
 #include "lama_correlative.h"
 #include "../host/pgo_pattern.hpp"
@@ -265,6 +266,8 @@ struct lama_hip_ctx {
     PinVec<double> h_mb_tfs; PinVec<uint32_t> h_mb_offs; PinVec<uint64_t> h_mb_meta;
     // lama_hip_map_rasterize / lama_hip_map_bounds (lama_raster.h): the dense grid and its page-locked staging copy, grow-only
     DevBuf<uint8_t> d_raster; PinVec<uint8_t> h_raster;
+    // lama_hip_map_cast_rays (lama_raycast_query.h), grow-only: [points 3n | pose transforms 12K] and the outputs, 22 bytes a beam
+    DevBuf<double> d_rq_in; DevBuf<uint8_t> d_rq_out; PinVec<double> h_rq_tfs;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
     // lama_hip_match_solve_batch (lama_match_batch.h), grow-only: [out8 8B | poses 4B | mounts 12B | points 3N] and
     // [iterations B | status B | problems 4B], with their page-locked staging copies
@@ -3053,6 +3056,105 @@ int32_t lama_hip_map_rasterize(lama_hip_ctx* c, uint32_t particle, int32_t layer
     HIPCHK(c, hipMemcpyAsync(c->h_raster.data(), d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(out, c->h_raster.data(), bytes);
+    return LAMA_HIP_OK;
+}
+
+// ---- lama_raycast_query.h: the first cell of every beam that stops the ray ---------------------------------------------------------
+namespace {
+// One beam's start and hit cell as beam_geometry forms them without truncation, in double BEFORE the cast (Map::w2m casts: a value
+// outside [0, 2^32) is undefined behaviour there) -> 0, or 1: a cell leaves the 32-bit range, 2: more than 8191 steps
+int cast_beam_check(const lama_hip_ctx* c, const double* T, const double* pt)
+{
+    const double h[3] = {((T[0] * pt[0] + T[1] * pt[1]) + T[2] * pt[2]) + T[9], ((T[3] * pt[0] + T[4] * pt[1]) + T[5] * pt[2]) + T[10],
+                         ((T[6] * pt[0] + T[7] * pt[1]) + T[8] * pt[2]) + T[11]};
+    int64_t nn = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double mh = (c->scale * h[a] + c->off) + 0.5, ms = (c->scale * T[9 + a] + c->off) + 0.5;
+        if (!(mh >= 0.0) || !(mh < 4294967296.0) || !(ms >= 0.0) || !(ms < 4294967296.0)) return 1;
+        const int64_t d = (int64_t)(uint32_t)mh - (int64_t)(uint32_t)ms;
+        nn = std::max(nn, d < 0 ? -d : d);
+    }
+    return nn > 8191 ? 2 : 0;
+}
+} // namespace
+
+int32_t lama_hip_map_cast_rays(lama_hip_ctx* c, uint32_t particle, int32_t kind, uint32_t num_poses, const double* poses4, const double* pts, uint32_t n,
+                               const double* origin3, const double* quat, uint32_t flags, int32_t tolerance_cells, uint8_t* status, int32_t* step,
+                               uint32_t* nn_out, uint32_t* cell_xy, uint32_t* end_sqdist, uint8_t* label, uint32_t* start_xy, double* kernel_ms)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // ---- everything that can refuse the call, before anything is uploaded or written
+    const char* const me = "lama_hip_map_cast_rays: ";
+    if (!status || !poses4 || !pts) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "status, poses4 or pts_xyz is NULL");
+    if (n == 0 || num_poses == 0) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "no beam or no pose");
+    if (particle >= c->P) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "particle out of range");
+    if (kind != LAMA_HIP_MAP_DISTANCE && kind != LAMA_HIP_MAP_OCCUPANCY) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "unknown map kind");
+    if (flags & ~(uint32_t)LAMA_HIP_RAY_STOP_UNKNOWN) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "unknown flag");
+    if (kind == LAMA_HIP_MAP_DISTANCE && (flags & LAMA_HIP_RAY_STOP_UNKNOWN))
+        return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "LAMA_HIP_RAY_STOP_UNKNOWN has no meaning on the distance map (a cell without a valid obstacle is not unknown)");
+    const uint64_t total = (uint64_t)num_poses * n;
+    if (total >= (1ull << 31)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "num_poses * n must stay below 2^31");
+    for (int k = 0; origin3 && k < 3; ++k) if (!std::isfinite(origin3[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the sensor origin is not finite");
+    for (int k = 0; quat && k < 4; ++k) if (!std::isfinite(quat[k])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the sensor orientation is not finite");
+    double r2 = 0.0;
+    if (!scan_reach2(pts, n, true, r2)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the scan holds a non-finite point (filter NaN / inf ranges first, as iris_lama_ros does)");
+    const Affine mtf = moving_tf(origin3, quat);
+    const double reach = std::sqrt(r2);
+    c->h_rq_tfs.resize(12 * (size_t)num_poses);
+    for (uint32_t k = 0; k < num_poses; ++k) {
+        double* const t = &c->h_rq_tfs[12 * (size_t)k];
+        for (int j = 0; j < 4; ++j) if (!std::isfinite(poses4[4 * (size_t)k + j])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a pose is not finite");
+        host_scan_tf(poses4 + 4 * (size_t)k, mtf, t);
+        for (int j = 0; j < 12; ++j) if (!std::isfinite(t[j])) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a pose or sensor transform is not finite");
+        // Every hit lies within |row of R| * reach of the transform's translation on each axis: where that bound keeps all cells inside
+        // the 32-bit range and below the step limit with two cells to spare, no beam of the pose needs a look; else each gets one.
+        bool sure = true;
+        for (int a = 0; a < 3; ++a) {
+            const double row = std::sqrt(t[3 * a] * t[3 * a] + t[3 * a + 1] * t[3 * a + 1] + t[3 * a + 2] * t[3 * a + 2]) * reach;
+            const double lo = c->scale * (t[9 + a] - row) + c->off, hi = c->scale * (t[9 + a] + row) + c->off;
+            sure = sure && lo >= 2.0 && hi < 4294967290.0 && c->scale * row + 2.0 < 8191.0;
+        }
+        if (sure) continue;
+        for (uint32_t i = 0; i < n; ++i) {
+            const int bad = cast_beam_check(c, t, pts + 3 * (size_t)i);
+            if (bad == 1) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "a start or hit cell leaves the 32-bit range of map cell coordinates");
+            if (bad == 2) return fail(c, LAMA_HIP_E_WINDOW, std::string(me) + "a beam is longer than 8191 cells");
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t n_in = 3 * (size_t)n + 12 * (size_t)num_poses;
+    // outputs, the widest first so that every array is aligned: cell_xy 8 | step 4 | nn 4 | end_sqdist 4 | status 1 | label 1 bytes a beam
+    const size_t T64 = (size_t)total, o_cell = 0, o_step = 8 * T64, o_nn = 12 * T64, o_end = 16 * T64, o_status = 20 * T64, o_label = 21 * T64;
+    HIPCHK(c, c->d_rq_in.grow(n_in, (size_t)1 << 14));
+    HIPCHK(c, c->d_rq_out.grow(22 * T64, (size_t)1 << 16));
+    double* const d_pts = c->d_rq_in; double* const d_tfs = d_pts + 3 * (size_t)n;
+    uint8_t* const d_out = c->d_rq_out;
+    HIPCHK(c, hipMemcpyAsync(d_pts, pts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tfs, c->h_rq_tfs.data(), sizeof(double) * 12 * (size_t)num_poses, hipMemcpyHostToDevice, c->stream));
+    DevParams prm = make_params(c);
+    prm.trunc_ray = 0.0; prm.trunc_range = 0.0;                    // the whole beam, as the map rebuild takes it
+    const bool want_label = label && tolerance_cells >= 0;
+    const CastOut out{d_out + o_status, step ? reinterpret_cast<int32_t*>(d_out + o_step) : nullptr, nn_out ? reinterpret_cast<uint32_t*>(d_out + o_nn) : nullptr,
+                      cell_xy ? reinterpret_cast<uint32_t*>(d_out + o_cell) : nullptr, (end_sqdist || want_label) ? reinterpret_cast<uint32_t*>(d_out + o_end) : nullptr,
+                      want_label ? d_out + o_label : nullptr};
+    const dim3 grid((n + 255u) / 256u, std::min<uint32_t>(num_poses, 65535u));
+    if (kernel_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if (kind == LAMA_HIP_MAP_DISTANCE) hipLaunchKernelGGL(k_cast_rays<true>, grid, dim3(256), 0, c->stream, prm, (int)particle, (const double*)d_pts, n, (const double*)d_tfs, num_poses, flags, tolerance_cells, out);
+    else hipLaunchKernelGGL(k_cast_rays<false>, grid, dim3(256), 0, c->stream, prm, (int)particle, (const double*)d_pts, n, (const double*)d_tfs, num_poses, flags, tolerance_cells, out);
+    HIPCHK(c, hipGetLastError());
+    if (kernel_ms) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, d_out + o_status, T64, hipMemcpyDeviceToHost, c->stream));
+    if (step) HIPCHK(c, hipMemcpyAsync(step, d_out + o_step, 4 * T64, hipMemcpyDeviceToHost, c->stream));
+    if (nn_out) HIPCHK(c, hipMemcpyAsync(nn_out, d_out + o_nn, 4 * T64, hipMemcpyDeviceToHost, c->stream));
+    if (cell_xy) HIPCHK(c, hipMemcpyAsync(cell_xy, d_out + o_cell, 8 * T64, hipMemcpyDeviceToHost, c->stream));
+    if (end_sqdist) HIPCHK(c, hipMemcpyAsync(end_sqdist, d_out + o_end, 4 * T64, hipMemcpyDeviceToHost, c->stream));
+    if (want_label) HIPCHK(c, hipMemcpyAsync(label, d_out + o_label, T64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (kernel_ms) { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1)); *kernel_ms = ms; }
+    // the start cell of a pose's beams, w2m(tf.translation()): the same arithmetic as the device's w2m (checked above to be in range)
+    for (uint32_t k = 0; start_xy && k < num_poses; ++k)
+        for (int a = 0; a < 2; ++a) start_xy[2 * (size_t)k + a] = (uint32_t)((c->scale * c->h_rq_tfs[12 * (size_t)k + 9 + a] + c->off) + 0.5);
     return LAMA_HIP_OK;
 }
 

@@ -80,6 +80,7 @@ def _hip_signatures():
     optional = [
         {"lama_hip_map_integrate_scans": [vp, u32, u32, vp, vp, vp, vp, vp, u32], "lama_hip_map_occupied_cells": [vp, u32, u32, vp, vp]},
         {"lama_hip_map_bounds": [vp, u32, i32, vp, vp, vp], "lama_hip_map_rasterize": [vp, u32, i32, u32, u32, u32, u32, u32, vp, u64]},
+        {"lama_hip_map_cast_rays": [vp, u32, i32, u32, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]},
         {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
         {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
         {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
@@ -185,6 +186,9 @@ _Z3 = np.zeros(3)
 
 MAP_BUILD_FULL, MAP_BUILD_PRUNE = 1, 2
 RASTER_TRINARY, RASTER_PROBABILITY, RASTER_SQDIST = 0, 1, 2      # LAMA_HIP_RASTER_*
+RAY_STOP_UNKNOWN = 1                                               # LAMA_HIP_RAY_STOP_UNKNOWN
+RAY_NONE, RAY_OCCUPIED, RAY_UNKNOWN = 0, 1, 2                      # LAMA_HIP_RAY_* status
+RAY_AGREES, RAY_BLOCKED, RAY_NOVEL = 0, 1, 2                       # LAMA_HIP_RAY_* label
 ROBUST_KINDS = {"unit": 0, "tukey": 1, "tdist": 2, "cauchy": 3, "huber": 4}      # LAMA_HIP_ROBUST_*
 ROBUST_STORED = 0x100     # LAMA_HIP_ROBUST_STORED: robust_param is the constant as the class stores it (b * b, 1 / param^2)
 E_NUMERIC = -6
@@ -264,6 +268,48 @@ class Grid:
         return np.sqrt(self.data.astype(np.float64)) * self.resolution
 
 
+class RayOptions(C.Structure):
+    """lama_ray_options (include/lama_host.h): lama::sdm::RayCastOptions"""
+    _fields_ = [("map", C.c_int32), ("stop_at_unknown", C.c_int32), ("tolerance_cells", C.c_int32)]
+
+
+class RayResultPointers(C.Structure):
+    """lama_ray_result (include/lama_host.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("status", "step", "nn", "cell_xy", "end_sqdist", "label", "start_xy", "range")]
+
+
+def ray_ranges(resolution, start_xy, cell_xy, status):
+    """lama::sdm::rayRange over a result: resolution * sqrt(dx^2 + dy^2) of the stopping cell's integer offset from its pose's start
+    cell (one correctly rounded square root of an exact integer), +inf where status is RAY_NONE.  start_xy (K, 2), cell_xy (K, n, 2)."""
+    d = (cell_xy.astype(np.int64) - start_xy.astype(np.int64)[:, None, :]).astype(np.float64)     # (below 2^14 cells where a ray stopped: exact)
+    r = float(resolution) * np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])
+    return np.where(status != RAY_NONE, r, np.inf)
+
+
+class RayCast:
+    """What lama_hip_map_cast_rays / castRays returned, every array (num_poses, n) -- cell_xy (num_poses, n, 2), start_xy
+    (num_poses, 2): status (RAY_NONE / RAY_OCCUPIED / RAY_UNKNOWN), step (-1: nothing stopped the beam), nn, cell_xy (the stopping
+    cell, else the point's), end_sqdist, label (RAY_AGREES / RAY_BLOCKED / RAY_NOVEL, None without a tolerance), range in metres
+    (+inf where nothing stopped the beam), kernel_ms (context-level calls)."""
+
+    def __init__(self, K, n, labels):
+        self.status = np.zeros((K, n), dtype=np.uint8)
+        self.step = np.zeros((K, n), dtype=np.int32)
+        self.nn = np.zeros((K, n), dtype=np.uint32)
+        self.cell_xy = np.zeros((K, n, 2), dtype=np.uint32)
+        self.end_sqdist = np.zeros((K, n), dtype=np.uint32)
+        self.label = np.zeros((K, n), dtype=np.uint8) if labels else None
+        self.start_xy = np.zeros((K, 2), dtype=np.uint32)
+        self.range = None
+        self.kernel_ms = None
+
+
+def fan_points(n, angle_min, angle_increment, max_range):
+    """lama::sdm::makeFan: the points (n, 3) of n beams from angle_min with angle_increment, each max_range long (sensor frame)"""
+    a = [angle_min + float(i) * angle_increment for i in range(int(n))]      # (libm's cos / sin per beam, as the C++ helper takes them)
+    return np.array([(max_range * math.cos(t), max_range * math.sin(t), 0.0) for t in a], dtype=np.float64).reshape(-1, 3)
+
+
 class _Handle:
     """A native handle `h` of the library `L`: the names of its destroy and last-error entry points and -- for the host classes --
     of the accessor of the device context, whose particle count is `_ctx_P`."""
@@ -296,6 +342,26 @@ class _Handle:
     def distance_grid(self, stride=1, world_box=None):
         """getDistanceGrid -> Grid of uint16 squared cell distances (Grid.metres()), or None while there is no map."""
         return self._grid("distance", (), stride, False, world_box)
+
+    def cast_rays(self, poses4, pts, origin=None, quat=None, distance_map=False, stop_at_unknown=False, tolerance_cells=-1, _args=()):
+        """castRays: what a sensor at each pose {c, s, tx, ty} of poses4 (K, 4) would see in the object's device map -- the
+        occupancy map, or with distance_map=True the distance map (lama::Loc2D: always) -> RayCast, or None while there is no map."""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        poses4 = np.ascontiguousarray(poses4, dtype=np.float64).reshape(-1, 4)
+        o = RayOptions(0 if distance_map or self._grid_prefix == "lama_loc" else 1, 1 if stop_at_unknown else 0, int(tolerance_cells))
+        r = RayCast(len(poses4), len(pts), tolerance_cells >= 0)
+        r.range = np.zeros(r.status.shape)
+        ptrs = RayResultPointers(*[_p(a) for a in (r.status, r.step, r.nn, r.cell_xy, r.end_sqdist, r.label, r.start_xy, r.range)])
+        rc = getattr(self.L, f"{self._grid_prefix}_cast_rays")(self.h, *_args, _p(poses4), len(poses4), _p(pts), len(pts), _p(origin), _p(quat), C.byref(o), C.byref(ptrs))
+        if rc < 0:
+            raise LamaError(self._error())
+        return r if rc else None
+
+    def expected_ranges(self, poses4, n, angle_min, angle_increment, max_range, origin=None, quat=None, **kw):
+        """The simulated scan of a beam model: the range (K, n) at which each beam of a fan of max_range first meets an occupied
+        cell, +inf where it meets none; None while there is no map."""
+        r = self.cast_rays(poses4, fan_points(n, angle_min, angle_increment, max_range), origin, quat, **kw)
+        return None if r is None else r.range
 
     def close(self):
         if getattr(self, "h", None) and not getattr(self, "_is_borrowed", False):
@@ -529,6 +595,24 @@ class HipContext(_Handle):
         self._chk(self.L.lama_hip_map_rasterize(self.h, particle, int(layer), int(x0), int(y0), int(width), int(height), int(stride), _p(out), out.nbytes))
         return out
 
+    def cast_rays(self, particle, kind, poses4, pts, origin=None, quat=None, stop_at_unknown=False, tolerance_cells=-1, resolution=None):
+        """lama_hip_map_cast_rays: per pose of poses4 (K, 4) and point of pts (n, 3) the first cell of `particle`'s map of `kind`
+        (MAP_DISTANCE / MAP_OCCUPANCY) that stops the beam -> RayCast (range from `resolution`, default the context's cfg)."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        poses4 = np.ascontiguousarray(poses4, dtype=np.float64).reshape(-1, 4)
+        origin = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64)
+        quat = None if quat is None else np.ascontiguousarray(quat, dtype=np.float64)
+        r = RayCast(len(poses4), len(pts), tolerance_cells >= 0)
+        ms = C.c_double(0.0)
+        self._chk(self.L.lama_hip_map_cast_rays(self.h, int(particle), int(kind), len(poses4), _p(poses4), _p(pts), len(pts), _p(origin), _p(quat),
+                                                RAY_STOP_UNKNOWN if stop_at_unknown else 0, int(tolerance_cells), _p(r.status), _p(r.step), _p(r.nn),
+                                                _p(r.cell_xy), _p(r.end_sqdist), _p(r.label), _p(r.start_xy), C.byref(ms)))
+        r.kernel_ms = ms.value
+        res = resolution if resolution is not None else (self.cfg.resolution if self.cfg is not None else None)
+        if res is not None:
+            r.range = ray_ranges(res, r.start_xy, r.cell_xy, r.status)
+        return r
+
     def match_solve(self, particle, pts, pose4, origin=None, quat=None, solve=True):
         """-> (pose, JtJ lower [00,10,11,20,21,22], sum r^2 (unweighted), iterations)"""
         pts, origin, quat = self._scan(pts, origin, quat)
@@ -735,6 +819,8 @@ HOST_SYMBOLS = [
     "lama_grid_default_options", "lama_grid_fetch", "lama_slam_occupancy_grid", "lama_slam_distance_grid", "lama_pf_occupancy_grid",
     "lama_pf_distance_grid", "lama_mapbuilder_occupancy_grid", "lama_mapbuilder_distance_grid", "lama_lo_occupancy_grid",
     "lama_lo_distance_grid", "lama_loc_distance_grid",
+    "lama_ray_default_options", "lama_slam_cast_rays", "lama_pf_cast_rays", "lama_mapbuilder_cast_rays", "lama_lo_cast_rays",
+    "lama_loc_cast_rays", "lama_loc_check_scan", "lama_slam_view_cast_rays",
 ]
 
 
@@ -810,6 +896,12 @@ def _bind_host(L):
         "lama_mapbuilder_occupancy_grid": (i32, [vp, vp, vp]), "lama_mapbuilder_distance_grid": (i32, [vp, vp, vp]),
         "lama_lo_occupancy_grid": (i32, [vp, vp, vp]), "lama_lo_distance_grid": (i32, [vp, vp, vp]),
         "lama_loc_distance_grid": (i32, [vp, vp, vp]),
+        "lama_ray_default_options": (None, [vp]),
+        "lama_slam_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_pf_cast_rays": (i32, [vp, C.c_int64, vp, u32, vp, u32, vp, vp, vp, vp]),
+        "lama_mapbuilder_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_lo_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
+        "lama_loc_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
+        "lama_loc_check_scan": (C.c_int64, [vp, vp, u32, vp, vp, i32, vp]),
+        "lama_slam_view_cast_rays": (i32, [vp, vp, u32, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -866,6 +958,11 @@ class PFSlam2D(_Handle):
 
     def distance_grid(self, stride=1, world_box=None, particle=None):
         return self._grid("distance", (-1 if particle is None else int(particle),), stride, False, world_box)
+
+    def cast_rays(self, poses4, pts, origin=None, quat=None, particle=None, **kw):
+        """castRays (the best particle's maps) / castParticleRays(particle) -> RayCast, or None (no map yet, or the particle lives
+        in another process)."""
+        return _Handle.cast_rays(self, poses4, pts, origin, quat, _args=(-1 if particle is None else int(particle),), **kw)
 
     def __init__(self, opts):
         self.L = _hostlib()
@@ -1078,6 +1175,13 @@ class Slam2D(_Handle):
             return None
         return fr.astype(bool), oc.astype(bool), un.astype(bool), pr
 
+    def view_cast_rays(self, poses4, pts):
+        """the host loop over getOccupancyMap()'s snapshot that castRays replaces (lama_slam_view_cast_rays) -> step (K, n), -1: none"""
+        poses4 = np.ascontiguousarray(poses4, dtype=np.float64).reshape(-1, 4)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros((len(poses4), len(pts)), dtype=np.int32)
+        return out if self.L.lama_slam_view_cast_rays(self.h, _p(poses4), len(poses4), _p(pts), len(pts), _p(out)) >= 0 else None
+
     def view_distance_cells(self, cells_xy):
         c = np.ascontiguousarray(cells_xy, dtype=np.uint32)
         out = np.zeros(len(c))
@@ -1166,6 +1270,17 @@ class Loc2D(_Handle):
 
     def occupancy_grid(self, *a, **kw):
         raise LamaError("lama::Loc2D has no device occupancy map: occupancy_map is a host map (distance_grid() is available)")
+
+    def check_scan(self, pts, origin=None, quat=None, tolerance_cells=2):
+        """Loc2D::checkScan: one label per point at the current pose on the distance map (RAY_AGREES: it ends within
+        tolerance_cells of a mapped obstacle; RAY_BLOCKED: it passes through one; RAY_NOVEL: it ends where the map has
+        nothing) -> uint8 (n,), or None while there is no device map."""
+        pts, origin, quat = self._scan(pts, origin, quat)
+        out = np.zeros(len(pts), dtype=np.uint8)
+        n = self.L.lama_loc_check_scan(self.h, _p(pts), len(pts), _p(origin), _p(quat), int(tolerance_cells), _p(out))
+        if n < 0:
+            raise LamaError(self._error())
+        return out if n else None
 
     def __init__(self, trans_thresh=0.5, rot_thresh=0.5, l2_max=1.0, resolution=0.05, max_iter=100, gpu_device=0,
                  gloc_particles=3000, gloc_iters=10, gloc_thresh=0.15, cov_blend=0.0, strategy="gn"):

@@ -6,7 +6,10 @@
 #include <stdexcept>
 
 #include "hip_engine.hpp"
+#include "lama/pose2d.h"
 #include "lama/sdm/grid.h"
+#include "lama/sdm/ray_cast.h"
+#include "scan_arrays.hpp"
 #include "lama/sdm_maps.h"
 
 namespace lama {
@@ -123,6 +126,31 @@ bool DeviceContext::distanceGrid(uint32_t particle, double resolution, double l2
     grid.max_distance = std::sqrt((double)(r * r)) * resolution;
     if (!grid_box(*eng_, ctx_, owner_, particle, LAMA_HIP_MAP_DISTANCE, resolution, options, grid)) return true;
     grid_raster(*eng_, ctx_, owner_, particle, LAMA_HIP_RASTER_SQDIST, grid, grid.sqdist);
+    return true;
+}
+
+// ---- ray casts (include/lama/sdm/ray_cast.h) ------------------------------------------------------------------------------------
+bool DeviceContext::castRays(uint32_t particle, double resolution, const std::vector<Pose2D>& poses, const PointCloudXYZ& surface, sdm::RayCastResult& r,
+                             const sdm::RayCastOptions& o) const
+{
+    if (!ctx_) return false;
+    if (!eng_->map_cast_rays)
+        throw std::runtime_error(std::string(owner_) + ": the device library " + eng_->origin + " has no lama_hip_map_cast_rays (ray casts through device maps)");
+    r = sdm::RayCastResult();
+    r.num_poses = (uint32_t)poses.size(); r.n = (uint32_t)surface.points.size(); r.resolution = resolution;
+    const size_t total = poses.size() * surface.points.size();
+    std::vector<double> poses4(4 * poses.size());
+    for (size_t k = 0; k < poses.size(); ++k) poses[k].state.toArray(&poses4[4 * k]);
+    const detail::ScanArrays a(surface);
+    r.status.assign(total, 0); r.step.assign(total, -1); r.nn.assign(total, 0); r.cell_xy.assign(2 * total, 0); r.end_sqdist.assign(total, 0);
+    r.start_xy.assign(2 * poses.size(), 0);
+    if (o.tolerance_cells >= 0) r.label.assign(total, 0);
+    // (an empty pose list or scan goes to the device library too: it is the one place that says what is refused)
+    check(eng_->map_cast_rays(ctx_, particle, (int32_t)o.map, r.num_poses, poses4.data(), a.pts.data(), r.n, a.o, a.q,
+                              o.stop_at_unknown ? LAMA_HIP_RAY_STOP_UNKNOWN : 0u, o.tolerance_cells, r.status.data(), r.step.data(), r.nn.data(), r.cell_xy.data(),
+                              r.end_sqdist.data(), r.label.empty() ? nullptr : r.label.data(), r.start_xy.data(), nullptr),
+          "lama_hip_map_cast_rays");
+    sdm::fillRayRanges(r);
     return true;
 }
 

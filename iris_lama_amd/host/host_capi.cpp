@@ -390,6 +390,33 @@ int lama_slam_view_occupancy(lama_slam* h, uint64_t n, const uint32_t* xy, uint8
         return 0;
     } catch (const std::exception& e) { h->error = e.what(); return -2; }
 }
+// the host loop a caller had before castRays (tools/raycast_query_bench.py measures it): per pose and point the cells from the sensor's
+// cell to the point's over getOccupancyMap()'s snapshot -- Map::computeRay's cells in the closed form floor((2 t a + nn) / (2 nn)) of the
+// map update, then the point's cell -- with isOccupied per cell; step_out: the index of the first occupied one, -1 for none
+int lama_slam_view_cast_rays(lama_slam* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, int32_t* step_out)
+{
+    try {
+        const FrequencyOccupancyMap* m = h->s->getOccupancyMap();
+        if (!m) return -1;
+        for (uint32_t k = 0; k < num_poses; ++k) {
+            const double c = poses4[4 * (size_t)k], s = poses4[4 * (size_t)k + 1], tx = poses4[4 * (size_t)k + 2], ty = poses4[4 * (size_t)k + 3];
+            const Vector3ui ms = m->w2m(Vector3d(tx, ty, 0.0));
+            for (uint32_t i = 0; i < n; ++i) {
+                const double px = pts[3 * (size_t)i], py = pts[3 * (size_t)i + 1];
+                const Vector3ui mh = m->w2m(Vector3d((c * px - s * py) + tx, (s * px + c * py) + ty, pts[3 * (size_t)i + 2]));
+                const int64_t d0 = (int64_t)mh(0) - (int64_t)ms(0), d1 = (int64_t)mh(1) - (int64_t)ms(1), d2 = (int64_t)mh(2) - (int64_t)ms(2);
+                const int64_t a0 = d0 < 0 ? -d0 : d0, a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2, nn = std::max(a0, std::max(a1, a2));
+                int32_t step = -1;
+                for (int64_t t = 1; t <= nn && step < 0; ++t) {
+                    const int64_t x = (int64_t)ms(0) + (d0 < 0 ? -1 : 1) * ((2 * t * a0 + nn) / (2 * nn)), y = (int64_t)ms(1) + (d1 < 0 ? -1 : 1) * ((2 * t * a1 + nn) / (2 * nn));
+                    if (m->isOccupied(Vector3ui((uint32_t)x, (uint32_t)y, 0))) step = (int32_t)(t - 1);
+                }
+                step_out[(size_t)k * n + i] = step;
+            }
+        }
+        return 0;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
 int lama_slam_view_distance_cells(lama_slam* h, uint64_t n, const uint32_t* xy, double* distance)
 {
     try {
@@ -1128,5 +1155,79 @@ int lama_lo_distance_grid(lama_lo* h, const lama_grid_options* o, lama_grid* out
 { return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->l->getDistanceGrid(g, go); }); }
 int lama_loc_distance_grid(lama_loc* h, const lama_grid_options* o, lama_grid* out)
 { return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->l.getDistanceGrid(g, go); }); }
+}   // extern "C"
+// ---- ray casts (include/lama/sdm/ray_cast.h) of the classes above ----
+namespace {
+// 1: cast (the arrays of *out that are not NULL are filled), 0: the object has no such map (yet / here), -2: failure
+template <class H, class F>
+int cast_rays_of(H* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q, const lama_ray_options* opt,
+                 lama_ray_result* out, F&& cast)
+{
+    try {
+        lama::sdm::RayCastOptions ro;
+        if (opt) { ro.map = opt->map == 0 ? lama::sdm::kRayDistanceMap : lama::sdm::kRayOccupancyMap; ro.stop_at_unknown = opt->stop_at_unknown != 0; ro.tolerance_cells = opt->tolerance_cells; }
+        if (opt && opt->map != 0 && opt->map != 1) throw std::invalid_argument("lama_ray_options: map is 0 (distance) or 1 (occupancy)");
+        std::vector<Pose2D> poses;
+        poses.reserve(num_poses);
+        for (uint32_t k = 0; k < num_poses; ++k) poses.push_back(Pose2D(SE2d::fromArray(poses4 + 4 * (size_t)k)));
+        lama::sdm::RayCastResult r;
+        if (!cast(poses, cloud_of(pts, n, o, q), r, ro)) return 0;
+        auto copy = [](auto* dst, const auto& src) { if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(src[0])); };
+        if (out) {
+            copy(out->status, r.status); copy(out->step, r.step); copy(out->nn, r.nn); copy(out->cell_xy, r.cell_xy); copy(out->end_sqdist, r.end_sqdist);
+            copy(out->label, r.label); copy(out->start_xy, r.start_xy); copy(out->range, r.range);
+        }
+        return 1;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+using lama::sdm::RayCastOptions;
+using lama::sdm::RayCastResult;
+}
+extern "C" {
+void lama_ray_default_options(lama_ray_options* o)
+{
+    const RayCastOptions d;
+    o->map = (int32_t)d.map; o->stop_at_unknown = d.stop_at_unknown ? 1 : 0; o->tolerance_cells = d.tolerance_cells;
+}
+int lama_slam_cast_rays(lama_slam* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q,
+                        const lama_ray_options* opt, lama_ray_result* out)
+{
+    return cast_rays_of(h, poses4, num_poses, pts, n, o, q, opt, out, [h](const std::vector<Pose2D>& p, const PointCloudXYZ::Ptr& s, RayCastResult& r, const RayCastOptions& ro) {
+        return h->s->castRays(p, s, r, ro); });
+}
+int lama_pf_cast_rays(lama_pf* h, int64_t particle, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q,
+                      const lama_ray_options* opt, lama_ray_result* out)
+{
+    return cast_rays_of(h, poses4, num_poses, pts, n, o, q, opt, out, [h, particle](const std::vector<Pose2D>& p, const PointCloudXYZ::Ptr& s, RayCastResult& r, const RayCastOptions& ro) {
+        return particle < 0 ? h->pf->castRays(p, s, r, ro) : h->pf->castParticleRays((size_t)particle, p, s, r, ro); });
+}
+int lama_mapbuilder_cast_rays(lama_mapbuilder* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q,
+                              const lama_ray_options* opt, lama_ray_result* out)
+{
+    return cast_rays_of(h, poses4, num_poses, pts, n, o, q, opt, out, [h](const std::vector<Pose2D>& p, const PointCloudXYZ::Ptr& s, RayCastResult& r, const RayCastOptions& ro) {
+        return h->b->castRays(p, s, r, ro); });
+}
+int lama_lo_cast_rays(lama_lo* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q,
+                      const lama_ray_options* opt, lama_ray_result* out)
+{
+    return cast_rays_of(h, poses4, num_poses, pts, n, o, q, opt, out, [h](const std::vector<Pose2D>& p, const PointCloudXYZ::Ptr& s, RayCastResult& r, const RayCastOptions& ro) {
+        return h->l->castRays(p, s, r, ro); });
+}
+int lama_loc_cast_rays(lama_loc* h, const double* poses4, uint32_t num_poses, const double* pts, uint32_t n, const double* o, const double* q,
+                       const lama_ray_options* opt, lama_ray_result* out)
+{
+    lama_ray_options dm;
+    if (!opt) { lama_ray_default_options(&dm); dm.map = 0; opt = &dm; }      // Loc2D's only device map
+    return cast_rays_of(h, poses4, num_poses, pts, n, o, q, opt, out, [h](const std::vector<Pose2D>& p, const PointCloudXYZ::Ptr& s, RayCastResult& r, const RayCastOptions& ro) {
+        return h->l.castRays(p, s, r, ro); });
+}
+int64_t lama_loc_check_scan(lama_loc* h, const double* pts, uint32_t n, const double* o, const double* q, int32_t tolerance_cells, uint8_t* labels_out)
+{
+    try {
+        const std::vector<uint8_t> labels = h->l.checkScan(cloud_of(pts, n, o, q), tolerance_cells);
+        if (labels_out && !labels.empty()) std::memcpy(labels_out, labels.data(), labels.size());
+        return (int64_t)labels.size();
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
 
 } // extern "C"

@@ -153,6 +153,24 @@ bool Loc2D::update(const PointCloudXYZ::Ptr& surface, const Pose2D& odometry, do
     return true;
 }
 
+// Additions: ray casts through the device distance map (include/lama/sdm/ray_cast.h)
+bool Loc2D::castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result, const sdm::RayCastOptions& options)
+{
+    if (options.map != sdm::kRayDistanceMap) throw std::invalid_argument("lama::Loc2D::castRays: only the distance map is on the device (RayCastOptions::map = kRayDistanceMap)");
+    if (distance_map && distance_map->hasPending()) distance_map->update();
+    return dev_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options);
+}
+
+std::vector<uint8_t> Loc2D::checkScan(const PointCloudXYZ::Ptr& surface, int32_t tolerance_cells)
+{
+    if (tolerance_cells < 0) throw std::invalid_argument("lama::Loc2D::checkScan: tolerance_cells must not be negative");
+    sdm::RayCastOptions o = distanceRays();
+    o.tolerance_cells = tolerance_cells;
+    sdm::RayCastResult r;
+    if (!castRays(std::vector<Pose2D>(1, pose_), surface, r, o)) return std::vector<uint8_t>();
+    return std::move(r.label);
+}
+
 void Loc2D::triggerGlobalLocalization() { do_global_localization_ = true; }      // :194-197
 
 // An addition: the lattice search of lama::CorrelativeSearch2D over the occupancy map's extent, on this object's context.

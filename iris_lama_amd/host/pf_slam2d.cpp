@@ -697,6 +697,20 @@ bool PFSlam2D::getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& 
     return has_first_scan && getParticleDistanceGrid(getBestParticleIdx(), grid, options);
 }
 
+bool PFSlam2D::castParticleRays(size_t i, const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
+                                const sdm::RayCastOptions& options) const
+{
+    if (!has_first_scan || i >= particles_.size() || !surface) return false;
+    if (group_) return ownerOf((uint32_t)i)->castParticleRays(i, poses, surface, result, options);
+    if (!ownsParticle((uint32_t)i)) return false;
+    return dev_.castRays((uint32_t)i - lo_, options_.resolution, poses, *surface, result, options);
+}
+
+bool PFSlam2D::castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result, const sdm::RayCastOptions& options) const
+{
+    return has_first_scan && castParticleRays(getBestParticleIdx(), poses, surface, result, options);
+}
+
 std::shared_ptr<const FrequencyOccupancyMap> PFSlam2D::getParticleOccupancyMap(size_t i) const
 {
     sdm::HostMap m;
