@@ -16,6 +16,7 @@ namespace lama {
 struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
 namespace sdm { struct GridOptions; struct OccupancyGrid; struct DistanceGrid; }      // include/lama/sdm/grid.h
 namespace sdm { struct RayCastOptions; struct RayCastResult; }                        // include/lama/sdm/ray_cast.h
+namespace sdm { struct FrontierOptions; struct FrontierSet; }                         // include/lama/sdm/frontier.h
 struct Pose2D;
 struct PointCloudXYZ;
 
@@ -57,6 +58,10 @@ public:
     // 8191 cells, stop_at_unknown on the distance map, ...).  No map, pose or snapshot changes.
     bool castRays(uint32_t particle, double resolution, const std::vector<Pose2D>& poses, const PointCloudXYZ& surface, sdm::RayCastResult& result,
                   const sdm::RayCastOptions& options) const;
+    // The frontier clusters of one particle's occupancy map (lama_hip_map_frontiers, include/lama/sdm/frontier.h), over the box
+    // occupancyGrid would take.  false without a context.  Throws std::runtime_error when the device library lacks the entry point
+    // or refuses the call, std::invalid_argument as occupancyGrid does.  No map, pose or snapshot changes.
+    bool frontiers(uint32_t particle, double resolution, sdm::FrontierSet& set, const sdm::FrontierOptions& options) const;
 
 private:
     std::shared_ptr<HipEngine> eng_;

@@ -18,6 +18,7 @@
 #include "pose2d.h"
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
+#include "sdm/frontier.h"
 #include "sdm_io.h"
 
 namespace lama {
@@ -55,6 +56,9 @@ struct LidarOdometry2D {
     bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
                   const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
     { return device_initialised_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options); }
+    // The frontier clusters of the device occupancy map (lama/sdm/frontier.h), labelled on the device.  false before the first scan.
+    bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
+    { return device_initialised_ && dev_.frontiers(0, opt_.resolution, set, options); }
     uint32_t getLastIterations() const { return last_iterations_; }
     uint32_t getLastDeletedPatches() const { return last_deleted_; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }

@@ -73,7 +73,8 @@ public:
     // true when the first build of the distance map was replayed on the host and uploaded (iris_lama_amd/host/dm_builder.hpp)
     bool distanceMapBuiltOnHost() const { return host_built_; }
     // Dense grid of the DEVICE distance map, made on the device (lama/sdm/grid.h); false while there is no device map yet.
-    // (occupancy_map is a host map: walk it on the host.)
+    // (occupancy_map is a host map: walk it on the host.  For the same reason there is no getFrontiers() here: lama/sdm/frontier.h
+    // works on a DEVICE occupancy map, which Loc2D does not have.)
     bool getDistanceGrid(sdm::DistanceGrid& grid, const sdm::GridOptions& options = sdm::GridOptions()) const
     { return dev_ && dev_.distanceGrid(0, opt_.resolution, opt_.l2_max, grid, options); }
     // What a sensor at each of `poses` would see in the DEVICE distance map (lama/sdm/ray_cast.h; the occupancy map is a host map, so

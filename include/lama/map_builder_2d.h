@@ -23,6 +23,7 @@
 #include "pose2d.h"
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
+#include "sdm/frontier.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -79,6 +80,9 @@ public:
     bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
                   const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
     { return has_map_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options); }
+    // The frontier clusters of the built occupancy map (lama/sdm/frontier.h), labelled on the device.  false before the first build.
+    bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
+    { return has_map_ && dev_.frontiers(0, opt_.resolution, set, options); }
 
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }

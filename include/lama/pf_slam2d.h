@@ -33,6 +33,7 @@
 #include "pose2d.h"
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
+#include "sdm/frontier.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -195,6 +196,10 @@ public:
                   const sdm::RayCastOptions& options = sdm::RayCastOptions()) const;
     bool castParticleRays(size_t i, const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
                           const sdm::RayCastOptions& options = sdm::RayCastOptions()) const;
+    // The frontier clusters of the best particle's / of particle i's device occupancy map (lama/sdm/frontier.h), labelled on the shard
+    // that holds the particle.  false where the grid methods return false.
+    bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const;
+    bool getParticleFrontiers(size_t i, sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const;
 
     // ------------------------------------------------------------------ step-wise API (sharded operation)
     enum Phase { kNoUpdate = 0, kFirstScan = 1, kMatched = 2 };

@@ -18,6 +18,7 @@
 #include "pose2d.h"
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
+#include "sdm/frontier.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -116,6 +117,10 @@ public:
     bool castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr& surface, sdm::RayCastResult& result,
                   const sdm::RayCastOptions& options = sdm::RayCastOptions()) const
     { return has_first_scan && surface && dev_.castRays(0, resolution_, poses, *surface, result, options); }
+    // The frontier clusters of the device occupancy map (lama/sdm/frontier.h): where free space meets unknown space, labelled on the
+    // device; only the cluster list comes down.  false before the first scan.  No snapshot is made or dropped.
+    bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
+    { return has_first_scan && dev_.frontiers(0, resolution_, set, options); }
     // include/lama/slam2d.h:157-161
     void saveOccImage(const std::string& name) const { const FrequencyOccupancyMap* m = getOccupancyMap(); if (m) sdm::export_to_png(m->snapshot(), name); }
     void saveDistImage(const std::string& name) const { const DynamicDistanceMap* m = getDistanceMap(); if (m) sdm::export_to_png(m->snapshot(), name); }

@@ -397,6 +397,40 @@ int32_t lama_hip_map_bounds(lama_hip_ctx* ctx, uint32_t particle, int32_t kind, 
 int32_t lama_hip_map_rasterize(lama_hip_ctx* ctx, uint32_t particle, int32_t layer, uint32_t x0, uint32_t y0,
                                uint32_t width, uint32_t height, uint32_t stride, void* out, uint64_t out_bytes);
 
+/* The FRONTIERS of `particle`'s occupancy map inside a box: where mapped free space ends and unknown space begins, grouped into
+ * connected clusters with a size, a box and the sums a centroid needs (csrc/lama_frontier.h) -- the candidate places an exploring robot
+ * drives to, and the seeds lama_hip_map_cast_rays(LAMA_HIP_RAY_STOP_UNKNOWN) takes.  Only the cluster list comes down, not the grid.
+ * The definition is exact, in integers, and independent of how the device schedules the work:
+ *   grid      the pixels of lama_hip_map_rasterize(LAMA_HIP_RASTER_TRINARY, x0, y0, width, height, stride), either occupancy policy;
+ *             the same rules for x0, y0 and stride; pixel (i, j) has the index j * width + i;
+ *   frontier  a pixel of the box with value 0 (free) of whose four EDGE neighbours at least one is -1 (unknown).  A diagonal unknown
+ *             neighbour alone does not count, an occupied neighbour does not count.  Neighbours outside the box are classified from the
+ *             map as well, as the raster of the box widened by one pixel per side gives them (absent patches and cells outside the map
+ *             window are unknown) -- except that a neighbour whose cells would lie below coordinate 0 or above 2^32 - 1 does not exist
+ *             and is not unknown.  The free cells on the rim of Map::bounds are therefore frontiers;
+ *   cluster   an 8-connected component of the frontier pixels of the box (pixels outside the box never belong to one, nor do they
+ *             join two); its label is the smallest pixel index among its pixels.
+ * Outputs: *n = the number of clusters with pixels >= min_pixels (0 is taken as 1); *frontier_pixels (may be NULL) = ALL frontier
+ * pixels, those of smaller clusters included; out[0 .. min(cap, *n)) = the records ordered by pixels descending, then label ascending
+ * (out may be NULL with cap == 0; entries past *n are left alone); labels_out (may be NULL) [height][width] = the cluster's label at
+ * every frontier pixel, small clusters included, 0xFFFFFFFF elsewhere; kernel_ms (may be NULL) = the device time of the call's
+ * launches, from events (two brackets: the launches before and the one after the read-back of the count).
+ * LAMA_HIP_E_INVALID, found before anything is written: the stride and origin rules of lama_hip_map_rasterize; width or height 0 or
+ * above 32766 (room for the halo within the raster's 32768); width * height > 2^28; a particle out of range; n == NULL; out == NULL
+ * with cap != 0.  A map without any occupancy patch: *n = 0, *frontier_pixels = 0, labels_out all 0xFFFFFFFF, no launch.
+ * No map, pose or counter of the context changes; like every entry point the call first waits for queued map updates.  Temporary
+ * device memory is grow-only and the context's: below 12 bytes per pixel of the widened box (the raster's buffer) plus 40 bytes per
+ * reported cluster. */
+typedef struct lama_hip_frontier {          /* 40 bytes */
+    uint32_t label;                         /* smallest pixel index j * width + i of the cluster: itself a frontier pixel (free) */
+    uint32_t pixels;                        /* number of frontier pixels in the cluster */
+    uint32_t min_i, min_j, max_i, max_j;    /* bounding box in pixels of the box */
+    uint64_t sum_i, sum_j;                  /* sums of the pixel indices: centroid = sum / pixels */
+} lama_hip_frontier;
+int32_t lama_hip_map_frontiers(lama_hip_ctx* ctx, uint32_t particle, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height,
+                               uint32_t stride, uint32_t min_pixels, uint32_t cap, lama_hip_frontier* out, uint32_t* n,
+                               uint64_t* frontier_pixels, uint32_t* labels_out, double* kernel_ms);
+
 /* What a sensor at each of num_poses poses WOULD see in `particle`'s device map of `kind` (LAMA_HIP_MAP_*): per (pose, beam) the first
  * cell that stops the ray (csrc/lama_raycast_query.h), one lane each -- the expected ranges of a beam model, a scan check (which beams
  * of a real scan agree with the map, which pass through a mapped obstacle, which end in mapped free space), visibility gating of many

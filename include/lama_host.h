@@ -379,6 +379,39 @@ int lama_loc_cast_rays(lama_loc* l, const double* poses4, uint32_t num_poses, co
                        const double* quat_wxyz, const lama_ray_options* options, lama_ray_result* out);
 int64_t lama_loc_check_scan(lama_loc* l, const double* pts_xyz, uint32_t n, const double* origin3, const double* quat_wxyz, int32_t tolerance_cells,
                             uint8_t* labels_out);
+/* ---- frontiers (include/lama/sdm/frontier.h): getFrontiers of the classes above -- the clusters of free pixels that border unknown
+ * space in the object's device occupancy map, labelled on the device.  options NULL: the defaults (whole map, stride 1, every cluster,
+ * no label grid).  Each call returns 1 when the frontiers were made -- the box and the counts in *out, the records (by pixels
+ * descending, then label ascending) and the label grid ([height][width] uint32, 0xFFFFFFFF where the pixel is no frontier; with
+ * options->labels only) kept on the calling thread until its next frontier call --, 0 when the object has no map (before the first scan
+ * / build, a particle of another process), -2 on a failure (message through the object's last_error: a device library without
+ * lama_hip_map_frontiers, an invalid stride, ...).  lama_frontiers_fetch copies the kept records and labels, each when its pointer is
+ * not NULL and its capacity (in elements) suffices, and returns the number of records.  lama_pf_*: particle < 0 is the best particle.
+ * (lama_loc has none: its occupancy map is a host map.) */
+typedef struct lama_frontier_options {
+    uint32_t stride;
+    int32_t whole_map;
+    double world_min[2], world_max[2];
+    uint32_t min_pixels, max_frontiers;      /* max_frontiers 0: all */
+    int32_t labels;
+} lama_frontier_options;
+typedef struct lama_frontier {
+    uint32_t label, pixels, min_i, min_j, max_i, max_j;
+    uint64_t sum_i, sum_j;
+    double centroid[2], seed[2];             /* world metres */
+} lama_frontier;
+typedef struct lama_frontier_set {
+    uint32_t x0, y0, width, height, stride, count;   /* count: the records kept (clusters, or max_frontiers if that is smaller) */
+    double resolution, cell_size;
+    double origin[3];                                /* Map::m2w of cell (x0, y0), z = 0 */
+    uint64_t frontier_pixels, clusters;
+} lama_frontier_set;
+void lama_frontier_default_options(lama_frontier_options* o);
+int64_t lama_frontiers_fetch(lama_frontier* records, uint64_t cap_records, uint32_t* labels, uint64_t cap_labels);
+int lama_slam_frontiers(lama_slam* s, const lama_frontier_options* options, lama_frontier_set* out);
+int lama_pf_frontiers(lama_pf* pf, int64_t particle, const lama_frontier_options* options, lama_frontier_set* out);
+int lama_mapbuilder_frontiers(lama_mapbuilder* b, const lama_frontier_options* options, lama_frontier_set* out);
+int lama_lo_frontiers(lama_lo* l, const lama_frontier_options* options, lama_frontier_set* out);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

@@ -20,6 +20,7 @@
 #include "lama_pgo_pcg.h"
 #include "lama_map_build.h"
 #include "lama_raster.h"
+#include "lama_frontier.h"
 #include "lama_raycast_query.h"
 #include "lama_match_batch.h"
 #include "lama_correlative.h"
@@ -266,6 +267,8 @@ struct lama_hip_ctx {
     PinVec<double> h_mb_tfs; PinVec<uint32_t> h_mb_offs; PinVec<uint64_t> h_mb_meta;
     // lama_hip_map_rasterize / lama_hip_map_bounds (lama_raster.h): the dense grid and its page-locked staging copy, grow-only
     DevBuf<uint8_t> d_raster; PinVec<uint8_t> h_raster;
+    // lama_hip_map_frontiers (lama_frontier.h): the compacted records, 40 bytes a reported cluster, grow-only (the rest is in d_raster)
+    DevBuf<lama_dev::FrontierRec> d_frontier_rec;
     // lama_hip_map_cast_rays (lama_raycast_query.h), grow-only: [points 3n | pose transforms 12K] and the outputs, 22 bytes a beam
     DevBuf<double> d_rq_in; DevBuf<uint8_t> d_rq_out; PinVec<double> h_rq_tfs;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
@@ -3056,6 +3059,101 @@ int32_t lama_hip_map_rasterize(lama_hip_ctx* c, uint32_t particle, int32_t layer
     HIPCHK(c, hipMemcpyAsync(c->h_raster.data(), d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(out, c->h_raster.data(), bytes);
+    return LAMA_HIP_OK;
+}
+
+// ---- lama_frontier.h: the frontier clusters of a box of the occupancy map ----------------------------------------------------------
+static_assert(sizeof(lama_hip_frontier) == 40 && sizeof(FrontierRec) == 40 && offsetof(lama_hip_frontier, sum_i) == offsetof(FrontierRec, sum_i) &&
+              offsetof(lama_hip_frontier, max_j) == offsetof(FrontierRec, max_j), "FrontierRec is lama_hip_frontier");
+int32_t lama_hip_map_frontiers(lama_hip_ctx* c, uint32_t particle, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t stride,
+                               uint32_t min_pixels, uint32_t cap, lama_hip_frontier* out, uint32_t* n, uint64_t* frontier_pixels, uint32_t* labels_out,
+                               double* kernel_ms)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // ---- everything that can refuse the call comes before anything is written ----
+    const char* const me = "lama_hip_map_frontiers: ";
+    if (!n) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "n is NULL");
+    if (!out && cap != 0u) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "out is NULL with cap != 0");
+    if (particle >= c->P) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "particle out of range");
+    uint32_t log2s = 0;
+    while (log2s < 6u && (1u << log2s) != stride) ++log2s;
+    if (log2s > 5u) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the stride must be 1, 2, 4, 8, 16 or 32");
+    if ((x0 & (stride - 1u)) || (y0 & (stride - 1u))) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "the origin must be a multiple of the stride");
+    if (width < 1u || height < 1u || width > 32766u || height > 32766u) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "width and height must be 1 .. 32766 pixels");
+    if ((uint64_t)width * height > (1ull << 28)) return fail(c, LAMA_HIP_E_INVALID, std::string(me) + "width * height must not exceed 2^28 pixels");
+    if (min_pixels == 0u) min_pixels = 1u;
+    const size_t npix = (size_t)width * height;
+    if (c->h_counts[2 * particle + 1] == 0) {                       // no occupancy patch: nothing is free, so nothing is a frontier
+        *n = 0;
+        if (frontier_pixels) *frontier_pixels = 0;
+        if (labels_out) std::memset(labels_out, 0xFF, npix * sizeof(uint32_t));
+        if (kernel_ms) *kernel_ms = 0.0;
+        return LAMA_HIP_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // the box widened by one pixel per side; a halo column / row whose cells would lie below 0 or above 2^32 - 1 does not exist
+    // (x0 is a multiple of the stride, so x0 < stride means x0 == 0)
+    FrontierBox fb;
+    fb.width = width; fb.height = height;
+    fb.ox = x0 >= stride ? 1u : 0u; fb.oy = y0 >= stride ? 1u : 0u;
+    fb.has_right = (uint64_t)x0 + (uint64_t)width * stride <= 0xFFFFFFFFull ? 1u : 0u;
+    fb.has_down = (uint64_t)y0 + (uint64_t)height * stride <= 0xFFFFFFFFull ? 1u : 0u;
+    fb.rw = width + fb.ox + 1u; fb.rh = height + fb.oy + 1u;
+    fb.sw = (width + 1u) >> 1; fb.nslots = fb.sw * ((height + 1u) >> 1);
+    // [head 16 | widened raster, later the compacted slot list | sums and boxes 24 a slot | counts 4 a slot | L 4 a pixel]: 28 bytes per
+    // 2 x 2 block, 4 per pixel and 1 per pixel of the widened box -- below 12 bytes per pixel of the widened box
+    const size_t ras_bytes = ((size_t)fb.rw * fb.rh + 7u) & ~(size_t)7u;                       // (>= 4 * nslots: (w + 1)(h + 1) >= 4 ceil(w / 2) ceil(h / 2))
+    const size_t o_ras = sizeof(FrontierHead), o_sums = o_ras + ras_bytes, o_cnt = o_sums + 24u * (size_t)fb.nslots, o_L = o_cnt + 4u * (size_t)fb.nslots;
+    const size_t bytes = o_L + 4u * npix;
+    HIPCHK(c, c->d_raster.grow(bytes, (size_t)1 << 16));
+    uint8_t* const base = c->d_raster;
+    FrontierHead* const d_head = reinterpret_cast<FrontierHead*>(base);
+    int8_t* const d_ras = reinterpret_cast<int8_t*>(base + o_ras);
+    uint32_t* const d_ids = reinterpret_cast<uint32_t*>(base + o_ras);
+    unsigned long long* const d_sums = reinterpret_cast<unsigned long long*>(base + o_sums);
+    const FrontierSlots st{d_sums, d_sums + fb.nslots, d_sums + 2u * (size_t)fb.nslots, reinterpret_cast<uint32_t*>(base + o_cnt)};
+    uint32_t* const d_L = reinterpret_cast<uint32_t*>(base + o_L);
+    const RasterBox box{x0 - fb.ox * stride, y0 - fb.oy * stride, fb.rw, fb.rh, stride, log2s};
+    const uint64_t xe = (uint64_t)box.x0 + (uint64_t)box.width * stride - 1u, ye = (uint64_t)box.y0 + (uint64_t)box.height * stride - 1u;
+    const dim3 rgrid((unsigned)((xe >> 5) - (box.x0 >> 5) + 1u), (unsigned)((ye >> 5) - (box.y0 >> 5) + 1u));
+    const dim3 pgrid((unsigned)((npix + 255u) / 256u)), sgrid((fb.nslots + 255u) / 256u);
+    const DevParams prm = make_params(c);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_head, 0, sizeof(FrontierHead), c->stream));
+    hipLaunchKernelGGL(k_raster<RASTER_TRINARY>, rgrid, dim3(256), 0, c->stream, prm, (int)particle, box, d_ras);
+    hipLaunchKernelGGL(k_frontier_mark, pgrid, dim3(256), 0, c->stream, fb, (const int8_t*)d_ras, d_L, st, d_head);
+    hipLaunchKernelGGL(k_frontier_merge, pgrid, dim3(256), 0, c->stream, fb, d_L);
+    hipLaunchKernelGGL(k_frontier_reduce, pgrid, dim3(256), 0, c->stream, fb, d_L, st);
+    hipLaunchKernelGGL(k_frontier_compact, sgrid, dim3(256), 0, c->stream, fb, st, min_pixels, d_head, d_ids);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->h_raster.reserve(sizeof(FrontierHead));
+    HIPCHK(c, hipMemcpyAsync(c->h_raster.data(), d_head, sizeof(FrontierHead), hipMemcpyDeviceToHost, c->stream));
+    if (labels_out) HIPCHK(c, hipMemcpyAsync(labels_out, d_L, 4u * npix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    FrontierHead head;
+    std::memcpy(&head, c->h_raster.data(), sizeof(head));
+    float ms = 0, ms2 = 0;
+    if (kernel_ms) HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    // the records of the kept clusters: a dense array sized by their number, sorted here (pixels descending, then label ascending)
+    std::vector<FrontierRec> recs(head.n);
+    if (head.n) {
+        HIPCHK(c, c->d_frontier_rec.grow(head.n, 1024));
+        FrontierRec* const d_rec = c->d_frontier_rec;
+        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        hipLaunchKernelGGL(k_frontier_gather, dim3((head.n + 255u) / 256u), dim3(256), 0, c->stream, fb, (const uint32_t*)d_L, st, (const uint32_t*)d_ids, head.n, d_rec);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(recs.data(), d_rec, sizeof(FrontierRec) * (size_t)head.n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (kernel_ms) HIPCHK(c, hipEventElapsedTime(&ms2, c->ev0, c->ev1));
+        std::sort(recs.begin(), recs.end(), [](const FrontierRec& a, const FrontierRec& b) { return a.pixels != b.pixels ? a.pixels > b.pixels : a.label < b.label; });
+    }
+    *n = head.n;
+    if (frontier_pixels) *frontier_pixels = head.pixels;
+    if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
+    if (out && head.n) std::memcpy(out, recs.data(), sizeof(FrontierRec) * (size_t)std::min(cap, head.n));
     return LAMA_HIP_OK;
 }
 

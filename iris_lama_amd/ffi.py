@@ -81,6 +81,7 @@ def _hip_signatures():
         {"lama_hip_map_integrate_scans": [vp, u32, u32, vp, vp, vp, vp, vp, u32], "lama_hip_map_occupied_cells": [vp, u32, u32, vp, vp]},
         {"lama_hip_map_bounds": [vp, u32, i32, vp, vp, vp], "lama_hip_map_rasterize": [vp, u32, i32, u32, u32, u32, u32, u32, vp, u64]},
         {"lama_hip_map_cast_rays": [vp, u32, i32, u32, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]},
+        {"lama_hip_map_frontiers": [vp, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]},
         {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
         {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
         {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
@@ -268,6 +269,48 @@ class Grid:
         return np.sqrt(self.data.astype(np.float64)) * self.resolution
 
 
+# lama_hip_frontier (include/lama_hip.h), 40 bytes
+FRONTIER_T = np.dtype([("label", "<u4"), ("pixels", "<u4"), ("min_i", "<u4"), ("min_j", "<u4"), ("max_i", "<u4"), ("max_j", "<u4"),
+                       ("sum_i", "<u8"), ("sum_j", "<u8")])
+NO_FRONTIER = 0xFFFFFFFF                                            # labels: not a frontier pixel
+
+
+class Frontiers:
+    """What lama_hip_map_frontiers returned: records (FRONTIER_T, the first min(cap, n) clusters by pixels descending, then label
+    ascending), n (clusters with pixels >= min_pixels), frontier_pixels (all of them), labels ((height, width) uint32, NO_FRONTIER
+    where the pixel is none; None unless asked for), kernel_ms."""
+
+    def __init__(self, records, n, frontier_pixels, labels, kernel_ms):
+        self.records, self.n, self.frontier_pixels, self.labels, self.kernel_ms = records, n, frontier_pixels, labels, kernel_ms
+
+
+class FrontierOptions(C.Structure):
+    """lama_frontier_options (include/lama_host.h): lama::sdm::FrontierOptions"""
+    _fields_ = [("stride", C.c_uint32), ("whole_map", C.c_int32), ("world_min", C.c_double * 2), ("world_max", C.c_double * 2),
+                ("min_pixels", C.c_uint32), ("max_frontiers", C.c_uint32), ("labels", C.c_int32)]
+
+
+class FrontierSetHeader(C.Structure):
+    """lama_frontier_set (include/lama_host.h)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("count", C.c_uint32),
+                ("resolution", C.c_double), ("cell_size", C.c_double), ("origin", C.c_double * 3), ("frontier_pixels", C.c_uint64), ("clusters", C.c_uint64)]
+
+
+# lama_frontier (include/lama_host.h), 72 bytes: the device record plus centroid and seed in world metres
+HOST_FRONTIER_T = np.dtype(FRONTIER_T.descr + [("centroid", "<f8", (2,)), ("seed", "<f8", (2,))])
+
+
+class FrontierSet:
+    """lama::sdm::FrontierSet: the box (x0, y0, width, height, stride, resolution, cell_size, origin as in Grid), `frontiers`
+    (HOST_FRONTIER_T, by pixels descending then label ascending), frontier_pixels, clusters, labels ((height, width) uint32 or None)."""
+
+    def __init__(self, hdr, frontiers, labels):
+        for name, _ in FrontierSetHeader._fields_:
+            setattr(self, name, getattr(hdr, name))
+        self.origin = np.array(list(hdr.origin))
+        self.frontiers, self.labels = frontiers, labels
+
+
 class RayOptions(C.Structure):
     """lama_ray_options (include/lama_host.h): lama::sdm::RayCastOptions"""
     _fields_ = [("map", C.c_int32), ("stop_at_unknown", C.c_int32), ("tolerance_cells", C.c_int32)]
@@ -342,6 +385,26 @@ class _Handle:
     def distance_grid(self, stride=1, world_box=None):
         """getDistanceGrid -> Grid of uint16 squared cell distances (Grid.metres()), or None while there is no map."""
         return self._grid("distance", (), stride, False, world_box)
+
+    def frontiers(self, stride=1, min_pixels=1, max_frontiers=0, labels=False, world_box=None, _args=()):
+        """getFrontiers: the clusters of free pixels that border unknown space in the object's device occupancy map, labelled on the
+        device -> FrontierSet, or None while there is no map.  world_box as for occupancy_grid."""
+        o = FrontierOptions()
+        self.L.lama_frontier_default_options(C.byref(o))
+        o.stride, o.min_pixels, o.max_frontiers, o.labels = int(stride), int(min_pixels), int(max_frontiers), 1 if labels else 0
+        if world_box is not None:
+            o.whole_map = 0
+            o.world_min[0], o.world_min[1], o.world_max[0], o.world_max[1] = (float(v) for v in world_box)
+        hdr = FrontierSetHeader()
+        rc = getattr(self.L, f"{self._grid_prefix}_frontiers")(self.h, *_args, C.byref(o), C.byref(hdr))
+        if rc < 0:
+            raise LamaError(self._error())
+        if rc == 0:
+            return None
+        recs = np.zeros(hdr.count, dtype=HOST_FRONTIER_T)
+        lab = np.full((hdr.height, hdr.width), NO_FRONTIER, dtype=np.uint32) if labels else None
+        assert self.L.lama_frontiers_fetch(_p(recs), len(recs), _p(lab), 0 if lab is None else lab.size) == hdr.count
+        return FrontierSet(hdr, recs, lab)
 
     def cast_rays(self, poses4, pts, origin=None, quat=None, distance_map=False, stop_at_unknown=False, tolerance_cells=-1, _args=()):
         """castRays: what a sensor at each pose {c, s, tx, ty} of poses4 (K, 4) would see in the object's device map -- the
@@ -595,6 +658,21 @@ class HipContext(_Handle):
         self._chk(self.L.lama_hip_map_rasterize(self.h, particle, int(layer), int(x0), int(y0), int(width), int(height), int(stride), _p(out), out.nbytes))
         return out
 
+    def map_frontiers(self, particle, x0, y0, width, height, stride=1, min_pixels=1, cap=None, labels=False):
+        """lama_hip_map_frontiers: the frontier clusters (free pixels with an unknown edge neighbour, 8-connected) of a box of
+        `particle`'s occupancy map -> Frontiers.  cap=None: every cluster (a second call where more than 1024 exist)."""
+        lab = np.zeros((int(height), int(width)), dtype=np.uint32) if labels else None
+        n, fp, ms = C.c_uint32(0), C.c_uint64(0), C.c_double(0.0)
+        want = 1024 if cap is None else int(cap)
+        while True:
+            rec = np.zeros(want, dtype=FRONTIER_T)
+            self._chk(self.L.lama_hip_map_frontiers(self.h, int(particle), int(x0), int(y0), int(width), int(height), int(stride), int(min_pixels), want,
+                                                    _p(rec) if want else None, C.byref(n), C.byref(fp), _p(lab), C.byref(ms)))
+            if cap is not None or n.value <= want:
+                break
+            want = n.value
+        return Frontiers(rec[:min(want, n.value)], int(n.value), int(fp.value), lab, ms.value)
+
     def cast_rays(self, particle, kind, poses4, pts, origin=None, quat=None, stop_at_unknown=False, tolerance_cells=-1, resolution=None):
         """lama_hip_map_cast_rays: per pose of poses4 (K, 4) and point of pts (n, 3) the first cell of `particle`'s map of `kind`
         (MAP_DISTANCE / MAP_OCCUPANCY) that stops the beam -> RayCast (range from `resolution`, default the context's cfg)."""
@@ -808,6 +886,7 @@ HOST_SYMBOLS = [
     "lama_loc_create2", "lama_loc_occ_set_cells", "lama_loc_occ_bounds", "lama_loc_trigger_global_localization",
     "lama_loc_global_localization_active", "lama_loc_gloc_candidates", "lama_loc_sampling_likelihoods",
     "lama_random_set_seed", "lama_random_uniform",
+    "lama_frontier_default_options", "lama_frontiers_fetch", "lama_slam_frontiers", "lama_pf_frontiers", "lama_mapbuilder_frontiers", "lama_lo_frontiers",
     "lama_sdm_write", "lama_sdm_read", "lama_sdm_image", "lama_sdm_export_png", "lama_dm_build", "lama_dm_build_fetch",
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
@@ -897,6 +976,9 @@ def _bind_host(L):
         "lama_lo_occupancy_grid": (i32, [vp, vp, vp]), "lama_lo_distance_grid": (i32, [vp, vp, vp]),
         "lama_loc_distance_grid": (i32, [vp, vp, vp]),
         "lama_ray_default_options": (None, [vp]),
+        "lama_frontier_default_options": (None, [vp]), "lama_frontiers_fetch": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64]),
+        "lama_slam_frontiers": (i32, [vp, vp, vp]), "lama_pf_frontiers": (i32, [vp, C.c_int64, vp, vp]),
+        "lama_mapbuilder_frontiers": (i32, [vp, vp, vp]), "lama_lo_frontiers": (i32, [vp, vp, vp]),
         "lama_slam_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_pf_cast_rays": (i32, [vp, C.c_int64, vp, u32, vp, u32, vp, vp, vp, vp]),
         "lama_mapbuilder_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_lo_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
         "lama_loc_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
@@ -958,6 +1040,10 @@ class PFSlam2D(_Handle):
 
     def distance_grid(self, stride=1, world_box=None, particle=None):
         return self._grid("distance", (-1 if particle is None else int(particle),), stride, False, world_box)
+
+    def frontiers(self, particle=None, **kw):
+        """getFrontiers (the best particle's) / getParticleFrontiers(particle) -> FrontierSet, or None"""
+        return _Handle.frontiers(self, _args=(-1 if particle is None else int(particle),), **kw)
 
     def cast_rays(self, poses4, pts, origin=None, quat=None, particle=None, **kw):
         """castRays (the best particle's maps) / castParticleRays(particle) -> RayCast, or None (no map yet, or the particle lives
@@ -1270,6 +1356,9 @@ class Loc2D(_Handle):
 
     def occupancy_grid(self, *a, **kw):
         raise LamaError("lama::Loc2D has no device occupancy map: occupancy_map is a host map (distance_grid() is available)")
+
+    def frontiers(self, *a, **kw):
+        raise LamaError("lama::Loc2D has no device occupancy map: occupancy_map is a host map, frontiers are made from a device map")
 
     def check_scan(self, pts, origin=None, quat=None, tolerance_cells=2):
         """Loc2D::checkScan: one label per point at the current pose on the distance map (RAY_AGREES: it ends within

@@ -9,6 +9,7 @@
 #include "lama/pose2d.h"
 #include "lama/sdm/grid.h"
 #include "lama/sdm/ray_cast.h"
+#include "lama/sdm/frontier.h"
 #include "scan_arrays.hpp"
 #include "lama/sdm_maps.h"
 
@@ -63,11 +64,12 @@ bool DeviceContext::download(uint32_t particle, int32_t kind, std::vector<uint64
 namespace {
 
 constexpr uint32_t kMaxGridSide = 32768;            // pixels (lama_hip_map_rasterize)
+constexpr uint32_t kMaxFrontierSide = 32766;        // pixels (lama_hip_map_frontiers: a pixel of halo on either side)
 
 // the box of the grid: Map::bounds of the device map, or the world box in cells (Map::w2m) widened outwards to multiples of the
-// stride; a side is clipped to kMaxGridSide pixels.  false: the map has no patch (whole_map) -- nothing to rasterise.
+// stride; a side is clipped to max_side pixels.  false: the map has no patch (whole_map) -- nothing to rasterise.
 bool grid_box(const HipEngine& e, lama_hip_ctx* ctx, const char* owner, uint32_t particle, int32_t kind, double resolution,
-              const sdm::GridOptions& o, sdm::GridHeader& g)
+              const sdm::GridOptions& o, sdm::GridHeader& g, uint32_t max_side = kMaxGridSide)
 {
     if (!e.map_bounds || !e.map_rasterize)
         throw std::runtime_error(std::string(owner) + ": the device library " + e.origin + " has no lama_hip_map_bounds / lama_hip_map_rasterize (dense grids)");
@@ -89,8 +91,8 @@ bool grid_box(const HipEngine& e, lama_hip_ctx* ctx, const char* owner, uint32_t
     const uint64_t s = o.stride;
     for (int k = 0; k < 2; ++k) { lo[k] = lo[k] / s * s; hi[k] = (hi[k] + s - 1u) / s * s; }
     g.x0 = (uint32_t)lo[0]; g.y0 = (uint32_t)lo[1]; g.stride = o.stride;
-    g.width = (uint32_t)std::min<uint64_t>((hi[0] - lo[0]) / s, kMaxGridSide);
-    g.height = (uint32_t)std::min<uint64_t>((hi[1] - lo[1]) / s, kMaxGridSide);
+    g.width = (uint32_t)std::min<uint64_t>((hi[0] - lo[0]) / s, max_side);
+    g.height = (uint32_t)std::min<uint64_t>((hi[1] - lo[1]) / s, max_side);
     g.resolution = resolution; g.cell_size = (double)o.stride * resolution;
     const Vector3d w = frame.m2w(Vector3ui(g.x0, g.y0, 0));
     g.origin = Vector3d(w[0], w[1], 0.0);
@@ -126,6 +128,42 @@ bool DeviceContext::distanceGrid(uint32_t particle, double resolution, double l2
     grid.max_distance = std::sqrt((double)(r * r)) * resolution;
     if (!grid_box(*eng_, ctx_, owner_, particle, LAMA_HIP_MAP_DISTANCE, resolution, options, grid)) return true;
     grid_raster(*eng_, ctx_, owner_, particle, LAMA_HIP_RASTER_SQDIST, grid, grid.sqdist);
+    return true;
+}
+
+// ---- frontiers (include/lama/sdm/frontier.h) ------------------------------------------------------------------------------------
+bool DeviceContext::frontiers(uint32_t particle, double resolution, sdm::FrontierSet& set, const sdm::FrontierOptions& o) const
+{
+    if (!ctx_) return false;
+    if (!eng_->map_frontiers)
+        throw std::runtime_error(std::string(owner_) + ": the device library " + eng_->origin + " has no lama_hip_map_frontiers (frontier clusters of device maps)");
+    set = sdm::FrontierSet();
+    sdm::GridOptions go;
+    go.stride = o.stride; go.whole_map = o.whole_map; go.world_min = o.world_min; go.world_max = o.world_max;
+    if (!grid_box(*eng_, ctx_, owner_, particle, LAMA_HIP_MAP_OCCUPANCY, resolution, go, set, kMaxFrontierSide)) return true;     // a map without patches: no frontier
+    if (o.labels) set.labels.assign((size_t)set.width * set.height, 0xFFFFFFFFu);
+    // the count first where the list is not capped: the records are 40 bytes each, the labelling itself is the smaller part of a call
+    std::vector<lama_hip_frontier> recs(o.max_frontiers ? o.max_frontiers : 256u);
+    uint32_t n = 0;
+    for (;;) {
+        check(eng_->map_frontiers(ctx_, particle, set.x0, set.y0, set.width, set.height, set.stride, o.min_pixels, (uint32_t)recs.size(), recs.data(), &n,
+                                  &set.frontier_pixels, o.labels ? set.labels.data() : nullptr, nullptr),
+              "lama_hip_map_frontiers");
+        if (o.max_frontiers || n <= recs.size()) break;
+        recs.resize(n);                                             // more clusters than the first guess: once more, with room for all
+    }
+    set.clusters = n;
+    recs.resize(std::min<size_t>(recs.size(), n));
+    set.frontiers.resize(recs.size());
+    const double s = (double)set.stride, half = ((double)set.stride - 1.0) / 2.0;
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const lama_hip_frontier& r = recs[k];
+        sdm::Frontier& f = set.frontiers[k];
+        f.label = r.label; f.pixels = r.pixels; f.min_i = r.min_i; f.min_j = r.min_j; f.max_i = r.max_i; f.max_j = r.max_j; f.sum_i = r.sum_i; f.sum_j = r.sum_j;
+        const double ci = (double)r.sum_i / (double)r.pixels, cj = (double)r.sum_j / (double)r.pixels;
+        f.centroid = Vector2d(set.origin[0] + resolution * (s * ci + half), set.origin[1] + resolution * (s * cj + half));
+        f.seed = Vector2d(set.origin[0] + resolution * (s * (double)(r.label % set.width) + half), set.origin[1] + resolution * (s * (double)(r.label / set.width) + half));
+    }
     return true;
 }
 

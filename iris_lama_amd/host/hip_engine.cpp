@@ -103,6 +103,7 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     e->pf_step_groups = reinterpret_cast<decltype(e->pf_step_groups)>(dlsym(dl, "lama_hip_pf_step_groups"));
     e->map_bounds = reinterpret_cast<decltype(e->map_bounds)>(dlsym(dl, "lama_hip_map_bounds"));
     e->map_rasterize = reinterpret_cast<decltype(e->map_rasterize)>(dlsym(dl, "lama_hip_map_rasterize"));
+    e->map_frontiers = reinterpret_cast<decltype(e->map_frontiers)>(dlsym(dl, "lama_hip_map_frontiers"));
     e->map_cast_rays = reinterpret_cast<decltype(e->map_cast_rays)>(dlsym(dl, "lama_hip_map_cast_rays"));
     return e;
 }

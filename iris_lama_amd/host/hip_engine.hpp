@@ -65,6 +65,7 @@ struct HipEngine {
     // on a library without them
     decltype(&lama_hip_map_bounds) map_bounds = nullptr;
     decltype(&lama_hip_map_rasterize) map_rasterize = nullptr;
+    decltype(&lama_hip_map_frontiers) map_frontiers = nullptr;
     // ray casts through a map (castRays of the host classes, Loc2D::checkScan); optional in the same way: those methods throw on a
     // library without it
     decltype(&lama_hip_map_cast_rays) map_cast_rays = nullptr;

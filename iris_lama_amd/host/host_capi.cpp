@@ -1156,6 +1156,64 @@ int lama_lo_distance_grid(lama_lo* h, const lama_grid_options* o, lama_grid* out
 int lama_loc_distance_grid(lama_loc* h, const lama_grid_options* o, lama_grid* out)
 { return distance_grid_of(h, o, out, [h](lama::sdm::DistanceGrid& g, const lama::sdm::GridOptions& go) { return h->l.getDistanceGrid(g, go); }); }
 }   // extern "C"
+// ---- frontiers (include/lama/sdm/frontier.h) of the classes above ----
+namespace {
+thread_local std::vector<lama_frontier> g_frontier_records;  // the result of the last frontier call on this thread (lama_frontiers_fetch)
+thread_local std::vector<uint32_t> g_frontier_labels;
+// 1: made (box and counts in *out, records and labels kept), 0: the object has no map (yet / here), -2: failure
+template <class H, class F>
+int frontiers_of(H* h, const lama_frontier_options* o, lama_frontier_set* out, F&& get)
+{
+    try {
+        lama::sdm::FrontierOptions fo;
+        if (o) {
+            fo.stride = o->stride; fo.whole_map = o->whole_map != 0; fo.min_pixels = o->min_pixels; fo.max_frontiers = o->max_frontiers; fo.labels = o->labels != 0;
+            fo.world_min = Vector2d(o->world_min[0], o->world_min[1]); fo.world_max = Vector2d(o->world_max[0], o->world_max[1]);
+        }
+        lama::sdm::FrontierSet s;
+        if (!get(s, fo)) return 0;
+        out->x0 = s.x0; out->y0 = s.y0; out->width = s.width; out->height = s.height; out->stride = s.stride; out->count = (uint32_t)s.frontiers.size();
+        out->resolution = s.resolution; out->cell_size = s.cell_size;
+        for (int k = 0; k < 3; ++k) out->origin[k] = s.origin[k];
+        out->frontier_pixels = s.frontier_pixels; out->clusters = s.clusters;
+        g_frontier_records.resize(s.frontiers.size());
+        for (size_t k = 0; k < s.frontiers.size(); ++k) {
+            const lama::sdm::Frontier& f = s.frontiers[k];
+            g_frontier_records[k] = lama_frontier{f.label, f.pixels, f.min_i, f.min_j, f.max_i, f.max_j, f.sum_i, f.sum_j,
+                                                  {f.centroid[0], f.centroid[1]}, {f.seed[0], f.seed[1]}};
+        }
+        g_frontier_labels.swap(s.labels);
+        return 1;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+}
+extern "C" {
+void lama_frontier_default_options(lama_frontier_options* o)
+{
+    const lama::sdm::FrontierOptions d;
+    o->stride = d.stride; o->whole_map = d.whole_map ? 1 : 0; o->min_pixels = d.min_pixels; o->max_frontiers = d.max_frontiers; o->labels = d.labels ? 1 : 0;
+    o->world_min[0] = o->world_min[1] = o->world_max[0] = o->world_max[1] = 0.0;
+}
+int64_t lama_frontiers_fetch(lama_frontier* records, uint64_t cap_records, uint32_t* labels, uint64_t cap_labels)
+{
+    if (records && cap_records >= g_frontier_records.size() && !g_frontier_records.empty())
+        std::memcpy(records, g_frontier_records.data(), g_frontier_records.size() * sizeof(lama_frontier));
+    if (labels && cap_labels >= g_frontier_labels.size() && !g_frontier_labels.empty())
+        std::memcpy(labels, g_frontier_labels.data(), g_frontier_labels.size() * sizeof(uint32_t));
+    return (int64_t)g_frontier_records.size();
+}
+int lama_slam_frontiers(lama_slam* h, const lama_frontier_options* o, lama_frontier_set* out)
+{ return frontiers_of(h, o, out, [h](lama::sdm::FrontierSet& s, const lama::sdm::FrontierOptions& fo) { return h->s->getFrontiers(s, fo); }); }
+int lama_pf_frontiers(lama_pf* h, int64_t particle, const lama_frontier_options* o, lama_frontier_set* out)
+{
+    return frontiers_of(h, o, out, [h, particle](lama::sdm::FrontierSet& s, const lama::sdm::FrontierOptions& fo) {
+        return particle < 0 ? h->pf->getFrontiers(s, fo) : h->pf->getParticleFrontiers((size_t)particle, s, fo); });
+}
+int lama_mapbuilder_frontiers(lama_mapbuilder* h, const lama_frontier_options* o, lama_frontier_set* out)
+{ return frontiers_of(h, o, out, [h](lama::sdm::FrontierSet& s, const lama::sdm::FrontierOptions& fo) { return h->b->getFrontiers(s, fo); }); }
+int lama_lo_frontiers(lama_lo* h, const lama_frontier_options* o, lama_frontier_set* out)
+{ return frontiers_of(h, o, out, [h](lama::sdm::FrontierSet& s, const lama::sdm::FrontierOptions& fo) { return h->l->getFrontiers(s, fo); }); }
+}   // extern "C"
 // ---- ray casts (include/lama/sdm/ray_cast.h) of the classes above ----
 namespace {
 // 1: cast (the arrays of *out that are not NULL are filled), 0: the object has no such map (yet / here), -2: failure

@@ -711,6 +711,19 @@ bool PFSlam2D::castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::P
     return has_first_scan && castParticleRays(getBestParticleIdx(), poses, surface, result, options);
 }
 
+bool PFSlam2D::getParticleFrontiers(size_t i, sdm::FrontierSet& set, const sdm::FrontierOptions& options) const
+{
+    if (!has_first_scan || i >= particles_.size()) return false;
+    if (group_) return ownerOf((uint32_t)i)->getParticleFrontiers(i, set, options);
+    if (!ownsParticle((uint32_t)i)) return false;
+    return dev_.frontiers((uint32_t)i - lo_, options_.resolution, set, options);
+}
+
+bool PFSlam2D::getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options) const
+{
+    return has_first_scan && getParticleFrontiers(getBestParticleIdx(), set, options);
+}
+
 std::shared_ptr<const FrequencyOccupancyMap> PFSlam2D::getParticleOccupancyMap(size_t i) const
 {
     sdm::HostMap m;
