@@ -8,6 +8,8 @@
 #include <memory>
 #include <vector>
 
+#include "types.h"
+
 struct lama_hip_ctx;
 struct lama_hip_cfg;
 
@@ -17,6 +19,7 @@ struct HipEngine;   // function table of include/lama_hip.h resolved with dlopen
 namespace sdm { struct GridOptions; struct OccupancyGrid; struct DistanceGrid; }      // include/lama/sdm/grid.h
 namespace sdm { struct RayCastOptions; struct RayCastResult; }                        // include/lama/sdm/ray_cast.h
 namespace sdm { struct FrontierOptions; struct FrontierSet; }                         // include/lama/sdm/frontier.h
+namespace sdm { struct TravelOptions; struct RouteSet; }                              // include/lama/sdm/travel.h
 struct Pose2D;
 struct PointCloudXYZ;
 
@@ -62,6 +65,12 @@ public:
     // occupancyGrid would take.  false without a context.  Throws std::runtime_error when the device library lacks the entry point
     // or refuses the call, std::invalid_argument as occupancyGrid does.  No map, pose or snapshot changes.
     bool frontiers(uint32_t particle, double resolution, sdm::FrontierSet& set, const sdm::FrontierOptions& options) const;
+    // Routes through one particle's device maps (lama_hip_map_travel, include/lama/sdm/travel.h) from the world points `from` to each
+    // of `goals`, over the box occupancyGrid would take -- or, with distance_only (a context whose only device map is the distance
+    // map: lama::Loc2D), the box distanceGrid would take.  false without a context.  Throws as frontiers does; a point of `from`
+    // outside the box is refused by the device library (std::runtime_error).  No map, pose or snapshot changes.
+    bool travel(uint32_t particle, double resolution, bool distance_only, const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals,
+                sdm::RouteSet& set, const sdm::TravelOptions& options) const;
 
 private:
     std::shared_ptr<HipEngine> eng_;

@@ -19,6 +19,7 @@
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
 #include "sdm/frontier.h"
+#include "sdm/travel.h"
 #include "sdm_io.h"
 
 namespace lama {
@@ -59,6 +60,10 @@ struct LidarOdometry2D {
     // The frontier clusters of the device occupancy map (lama/sdm/frontier.h), labelled on the device.  false before the first scan.
     bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
     { return device_initialised_ && dev_.frontiers(0, opt_.resolution, set, options); }
+    // Routes through the device maps (lama/sdm/travel.h) from the world points `from` to each of `goals`: reachability, cost and path,
+    // relaxed on the device; only the routes come down.  false where getFrontiers returns false.  No snapshot is made or dropped.
+    bool planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions()) const
+    { return device_initialised_ && dev_.travel(0, opt_.resolution, false, from, goals, set, options); }
     uint32_t getLastIterations() const { return last_iterations_; }
     uint32_t getLastDeletedPatches() const { return last_deleted_; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }

@@ -25,6 +25,7 @@
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
 #include "sdm/simple_occupancy_map.h"
+#include "sdm/travel.h"
 
 namespace lama {
 
@@ -87,6 +88,12 @@ public:
     // the map is stale), kRayNovel (it ends where the map has nothing: a person, a moved pallet -- points to drop before matching).
     // Empty while there is no device map yet.
     std::vector<uint8_t> checkScan(const PointCloudXYZ::Ptr& surface, int32_t tolerance_cells = 2);
+    // Routes over the floor plan (lama/sdm/travel.h) from the world points `from` to each of `goals`, relaxed on the device.  The
+    // DISTANCE map alone decides what is traversable (occupancy_map is a host map): a pixel at least the robot's radius away from every
+    // obstacle is, and a cell the distance map does not hold counts as max_distance away -- there is no "unknown" here, so bound the box
+    // with TravelOptions::world_min / world_max where the plan's outside must not be driven through.  Obstacles added since the last
+    // update() are brought in first.  false while there is no device map yet.
+    bool planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions());
     static sdm::RayCastOptions distanceRays() { sdm::RayCastOptions o; o.map = sdm::kRayDistanceMap; return o; }
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }

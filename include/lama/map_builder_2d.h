@@ -24,6 +24,7 @@
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
 #include "sdm/frontier.h"
+#include "sdm/travel.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -83,6 +84,10 @@ public:
     // The frontier clusters of the built occupancy map (lama/sdm/frontier.h), labelled on the device.  false before the first build.
     bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
     { return has_map_ && dev_.frontiers(0, opt_.resolution, set, options); }
+    // Routes through the device maps (lama/sdm/travel.h) from the world points `from` to each of `goals`: reachability, cost and path,
+    // relaxed on the device; only the routes come down.  false where getFrontiers returns false.  No snapshot is made or dropped.
+    bool planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions()) const
+    { return has_map_ && dev_.travel(0, opt_.resolution, false, from, goals, set, options); }
 
     lama_hip_ctx* deviceContext() const { return dev_.get(); }
     const HipEngine* engine() const { return dev_.engine().get(); }

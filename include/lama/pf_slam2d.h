@@ -34,6 +34,7 @@
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
 #include "sdm/frontier.h"
+#include "sdm/travel.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -200,6 +201,10 @@ public:
     // that holds the particle.  false where the grid methods return false.
     bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const;
     bool getParticleFrontiers(size_t i, sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const;
+    // Routes through the best particle's / particle i's device maps (lama/sdm/travel.h), relaxed on the shard that holds the particle.
+    // false where the grid methods return false.
+    bool planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions()) const;
+    bool planParticleRoutes(size_t i, const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions()) const;
 
     // ------------------------------------------------------------------ step-wise API (sharded operation)
     enum Phase { kNoUpdate = 0, kFirstScan = 1, kMatched = 2 };

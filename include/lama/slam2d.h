@@ -19,6 +19,7 @@
 #include "sdm/grid.h"
 #include "sdm/ray_cast.h"
 #include "sdm/frontier.h"
+#include "sdm/travel.h"
 #include "sdm_io.h"
 #include "sdm_maps.h"
 
@@ -121,6 +122,10 @@ public:
     // device; only the cluster list comes down.  false before the first scan.  No snapshot is made or dropped.
     bool getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& options = sdm::FrontierOptions()) const
     { return has_first_scan && dev_.frontiers(0, resolution_, set, options); }
+    // Routes through the device maps (lama/sdm/travel.h) from the world points `from` to each of `goals`: reachability, cost and path,
+    // relaxed on the device; only the routes come down.  false where getFrontiers returns false.  No snapshot is made or dropped.
+    bool planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options = sdm::TravelOptions()) const
+    { return has_first_scan && dev_.travel(0, resolution_, false, from, goals, set, options); }
     // include/lama/slam2d.h:157-161
     void saveOccImage(const std::string& name) const { const FrequencyOccupancyMap* m = getOccupancyMap(); if (m) sdm::export_to_png(m->snapshot(), name); }
     void saveDistImage(const std::string& name) const { const DynamicDistanceMap* m = getDistanceMap(); if (m) sdm::export_to_png(m->snapshot(), name); }

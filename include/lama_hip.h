@@ -431,6 +431,64 @@ int32_t lama_hip_map_frontiers(lama_hip_ctx* ctx, uint32_t particle, uint32_t x0
                                uint32_t stride, uint32_t min_pixels, uint32_t cap, lama_hip_frontier* out, uint32_t* n,
                                uint64_t* frontier_pixels, uint32_t* labels_out, double* kernel_ms);
 
+/* ROUTES through `particle`'s device maps inside a box: can the robot get from where it is to each of a list of goals, how far is it,
+ * and along which pixels (csrc/lama_travel.h) -- a travel-cost field from the source pixels over the traversable pixels, the best pixel
+ * near every goal, and the path to it.  Only the routes come down, not the grids.  The definition is exact, in integers, and
+ * independent of how the device schedules the work:
+ *   pixels       those of lama_hip_map_rasterize for the same x0, y0, width, height and stride (the same rules for them); pixel (i, j)
+ *                has the index j * width + i.  occ = the TRINARY layer, sq = the SQDIST layer (the smallest squared distance of the
+ *                block; max_sqdist where the cell is absent).  A context whose occupancy map has no patch while its distance map has
+ *                some (lama::Loc2D's) has no occ layer;
+ *   traversable  occ == 0 (free) and sq >= clearance_cells^2; without an occ layer the sq condition alone (that map knows no
+ *                "unknown").  Pixels outside the box do not exist: there is no halo;
+ *   entering     m(q) = near_factor where sq(q) < prefer_cells^2, else 1.  A step from p to an EDGE neighbour q costs 5 * m(q), to a
+ *                DIAGONAL neighbour 7 * m(q);
+ *   moves        a step may only enter a traversable pixel; a diagonal step needs in addition BOTH pixels that share an edge with p
+ *                and q to be traversable (no corner is cut), so reachability is 4-connected while paths are 8-connected;
+ *   sources      sources_xy [num_sources][2] in map CELL coordinates; every source pixel has cost 0 whatever its class (the robot is
+ *                where it is) and may be left by any legal move; a non-traversable source blocks diagonals like any such pixel;
+ *   field        F[q] = the least total cost of a move sequence from any source to q, 0xFFFFFFFF where there is none.  F is unique;
+ *   goal         goals_xy [num_goals][2] in map cell coordinates.  Among the goal's pixel and every pixel within Chebyshev distance
+ *                goal_reach of it, clipped to the box, the answer is the one with the smallest F, ties to the smallest index:
+ *                routes[g] = {status, pixel, cost = F[pixel], steps}.  LAMA_HIP_ROUTE_REACHED; LAMA_HIP_ROUTE_UNREACHED when none of
+ *                them has a finite F, LAMA_HIP_ROUTE_OUTSIDE when the goal's cell is not in the box (pixel = cost = 0xFFFFFFFF,
+ *                steps = 0 in both);
+ *   path         from the answer pixel p, until F[p] == 0: of p's 8 neighbours n in ascending pixel index the first with F[n]
+ *                finite, the move n -> p legal and F[n] + (5 or 7) * m(p) == F[p] is the next p.  steps = the number of moves, in
+ *                full.  paths[g][0 .. min(path_cap, steps + 1)) = the pixels counted FROM THE SOURCE END (the source first): the
+ *                moves to drive next are what a caller needs when the cap cuts the list.  Entries past that and the rows of goals
+ *                not reached are left alone.
+ * field_out (may be NULL) [height][width] = F.  rounds (may be NULL) = the relaxation rounds that ran a tile; a diagnostic that may
+ * differ from run to run.  kernel_ms (may be NULL) = the device time between the first and the last launch of the call, from events
+ * (the host's batched read-backs of the rounds' tile counts lie inside it).
+ * LAMA_HIP_E_INVALID, found before anything is written: the stride and origin rules of lama_hip_map_rasterize; width or height 0 or
+ * above 32768; width * height * 7 * near_factor >= 2^32 (a shortest path enters a pixel at most once, so below this no cost wraps);
+ * a particle out of range; num_sources == 0; sources_xy, goals_xy, routes or paths NULL where their count is not 0; a source outside
+ * the box; clearance_cells^2 > max_sqdist; prefer_cells < clearance_cells or above 65535; near_factor outside 1 .. 64; goal_reach
+ * above 16; num_goals * path_cap above 2^28.
+ * Neither map has a patch: no pixel is traversable, so the field is 0 at the sources and 0xFFFFFFFF elsewhere, a goal is REACHED only
+ * where its window holds a source, and nothing is rasterised or relaxed.
+ * No map, pose or counter of the context changes; like every entry point the call first waits for queued map updates.  Temporary
+ * device memory is grow-only and the context's: 8 bytes per pixel (the two rasters 3, the class 1, the field 4), 12 bytes per tile
+ * of 32 x 32 pixels, 8 bytes per source and per goal, 16 per goal and 8 per goal and path entry. */
+#define LAMA_HIP_ROUTE_REACHED   0u
+#define LAMA_HIP_ROUTE_UNREACHED 1u
+#define LAMA_HIP_ROUTE_OUTSIDE   2u
+#define LAMA_HIP_ROUTE_NONE 0xFFFFFFFFu     /* F of an unreached pixel; pixel and cost of a route that is not REACHED */
+typedef struct lama_hip_route {             /* 16 bytes */
+    uint32_t status;                        /* LAMA_HIP_ROUTE_* */
+    uint32_t pixel;                         /* the answer pixel j * width + i */
+    uint32_t cost;                          /* F[pixel]: 5 per edge step, 7 per diagonal step, near_factor times that close to obstacles */
+    uint32_t steps;                         /* moves from the source to the answer pixel; the path has steps + 1 pixels */
+} lama_hip_route;
+int32_t lama_hip_map_travel(lama_hip_ctx* ctx, uint32_t particle, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t stride,
+                            uint32_t clearance_cells, uint32_t prefer_cells, uint32_t near_factor, uint32_t num_sources, const uint32_t* sources_xy,
+                            uint32_t num_goals, const uint32_t* goals_xy, uint32_t goal_reach, lama_hip_route* routes, uint32_t path_cap,
+                            uint32_t* paths, uint32_t* field_out, uint32_t* rounds, double* kernel_ms);
+/* Diagnostics of the context's last lama_hip_map_travel (each may be NULL): the rounds, the tiles run over all rounds, the most tiles
+ * any round ran, and the blocking read-backs of the host loop. */
+int32_t lama_hip_map_travel_stats(lama_hip_ctx* ctx, uint32_t* rounds, uint64_t* tiles_run, uint32_t* max_tiles, uint32_t* readbacks);
+
 /* What a sensor at each of num_poses poses WOULD see in `particle`'s device map of `kind` (LAMA_HIP_MAP_*): per (pose, beam) the first
  * cell that stops the ray (csrc/lama_raycast_query.h), one lane each -- the expected ranges of a beam model, a scan check (which beams
  * of a real scan agree with the map, which pass through a mapped obstacle, which end in mapped free space), visibility gating of many

@@ -412,6 +412,46 @@ int lama_slam_frontiers(lama_slam* s, const lama_frontier_options* options, lama
 int lama_pf_frontiers(lama_pf* pf, int64_t particle, const lama_frontier_options* options, lama_frontier_set* out);
 int lama_mapbuilder_frontiers(lama_mapbuilder* b, const lama_frontier_options* options, lama_frontier_set* out);
 int lama_lo_frontiers(lama_lo* l, const lama_frontier_options* options, lama_frontier_set* out);
+/* ---- routes (include/lama/sdm/travel.h): planRoutes of the classes above -- from the world points from_xy [n_from][2] to each of
+ * goals_xy [n_goals][2] (metres) through the object's device maps: reachability, cost and path, relaxed on the device.  options NULL:
+ * the defaults (whole map, stride 1, a point robot, paths of up to 1024 points, no field).  Each call returns 1 when the routes were
+ * made -- the box and the counts in *out; the routes, the path points (world metres, source first, route after route) and the field
+ * ([height][width] uint32, 0xFFFFFFFF where no route leads; with options->field only) kept on the calling thread until its next route
+ * call --, 0 when the object has no map (before the first scan / build, a particle of another process), -2 on a failure (message
+ * through the object's last_error: a device library without lama_hip_map_travel, a start point outside the box, ...).
+ * lama_routes_fetch copies what was kept, each array when its pointer is not NULL and its capacity (in elements; path points count
+ * two doubles each) suffices, and returns the number of routes.  lama_pf_*: particle < 0 is the best particle.  lama_loc_*: the
+ * distance map alone decides what is traversable (its occupancy map is a host map). */
+typedef struct lama_travel_options {
+    uint32_t stride;
+    int32_t whole_map;
+    double world_min[2], world_max[2];
+    double robot_radius, preferred_clearance;        /* metres */
+    uint32_t near_factor, goal_reach, max_path_points;
+    int32_t field;
+} lama_travel_options;
+typedef struct lama_route {
+    uint32_t status, pixel, cost, steps;             /* status: 0 reached, 1 unreached, 2 the goal lies outside the box */
+    double length_m;                                 /* cost * cell_size / 5 */
+    uint64_t path_first;                             /* the route's first point among the kept path points */
+    uint32_t path_points, reserved;                  /* min(max_path_points, steps + 1); 0 unless reached */
+} lama_route;
+typedef struct lama_route_set {
+    uint32_t x0, y0, width, height, stride, count;   /* count: the routes, one per goal */
+    double resolution, cell_size;
+    double origin[3];                                /* Map::m2w of cell (x0, y0), z = 0 */
+    uint64_t path_points;                            /* of all routes together */
+    uint32_t rounds, has_field;
+} lama_route_set;
+void lama_travel_default_options(lama_travel_options* o);
+int64_t lama_routes_fetch(lama_route* routes, uint64_t cap_routes, double* path_xy, uint64_t cap_points, uint32_t* field, uint64_t cap_field);
+int lama_slam_plan_routes(lama_slam* s, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* options, lama_route_set* out);
+int lama_pf_plan_routes(lama_pf* pf, int64_t particle, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* options,
+                        lama_route_set* out);
+int lama_mapbuilder_plan_routes(lama_mapbuilder* b, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* options,
+                                lama_route_set* out);
+int lama_lo_plan_routes(lama_lo* l, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* options, lama_route_set* out);
+int lama_loc_plan_routes(lama_loc* l, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* options, lama_route_set* out);
 /* lama::random (include/lama/random.h) */
 void lama_random_set_seed(uint32_t seed);
 double lama_random_uniform(void);

@@ -21,6 +21,7 @@
 #include "lama_map_build.h"
 #include "lama_raster.h"
 #include "lama_frontier.h"
+#include "lama_travel.h"
 #include "lama_raycast_query.h"
 #include "lama_match_batch.h"
 #include "lama_correlative.h"
@@ -269,6 +270,10 @@ struct lama_hip_ctx {
     DevBuf<uint8_t> d_raster; PinVec<uint8_t> h_raster;
     // lama_hip_map_frontiers (lama_frontier.h): the compacted records, 40 bytes a reported cluster, grow-only (the rest is in d_raster)
     DevBuf<lama_dev::FrontierRec> d_frontier_rec;
+    // lama_hip_map_travel (lama_travel.h): rasters, classes, field, tile flags and lists, sources, goals, routes and paths in one
+    // grow-only buffer; what the last call's host loop did (lama_hip_map_travel_stats)
+    DevBuf<uint8_t> d_travel;
+    uint32_t travel_rounds = 0, travel_max_tiles = 0, travel_readbacks = 0; uint64_t travel_tiles = 0;
     // lama_hip_map_cast_rays (lama_raycast_query.h), grow-only: [points 3n | pose transforms 12K] and the outputs, 22 bytes a beam
     DevBuf<double> d_rq_in; DevBuf<uint8_t> d_rq_out; PinVec<double> h_rq_tfs;
     DevBuf<double> d_bposes, d_bout;  // batch evaluations: four pose doubles per entry, one output double (ensure_batch)
@@ -3154,6 +3159,161 @@ int32_t lama_hip_map_frontiers(lama_hip_ctx* c, uint32_t particle, uint32_t x0, 
     if (frontier_pixels) *frontier_pixels = head.pixels;
     if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
     if (out && head.n) std::memcpy(out, recs.data(), sizeof(FrontierRec) * (size_t)std::min(cap, head.n));
+    return LAMA_HIP_OK;
+}
+
+// ---- lama_travel.h: the travel-cost field of a box, the best pixel near every goal and the path to it ------------------------------
+static_assert(sizeof(lama_hip_route) == 16 && sizeof(TravelRoute) == 16 && offsetof(lama_hip_route, steps) == offsetof(TravelRoute, steps), "TravelRoute is lama_hip_route");
+int32_t lama_hip_map_travel(lama_hip_ctx* c, uint32_t particle, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t stride,
+                            uint32_t clearance_cells, uint32_t prefer_cells, uint32_t near_factor, uint32_t num_sources, const uint32_t* sources_xy,
+                            uint32_t num_goals, const uint32_t* goals_xy, uint32_t goal_reach, lama_hip_route* routes, uint32_t path_cap,
+                            uint32_t* paths, uint32_t* field_out, uint32_t* rounds_out, double* kernel_ms)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    ENTER(c);
+    // ---- everything that can refuse the call comes before anything is written ----
+    const std::string me = "lama_hip_map_travel: ";
+    if (particle >= c->P) return fail(c, LAMA_HIP_E_INVALID, me + "particle out of range");
+    uint32_t log2s = 0;
+    while (log2s < 6u && (1u << log2s) != stride) ++log2s;
+    if (log2s > 5u) return fail(c, LAMA_HIP_E_INVALID, me + "the stride must be 1, 2, 4, 8, 16 or 32");
+    if ((x0 & (stride - 1u)) || (y0 & (stride - 1u))) return fail(c, LAMA_HIP_E_INVALID, me + "the origin must be a multiple of the stride");
+    if (width < 1u || height < 1u || width > 32768u || height > 32768u) return fail(c, LAMA_HIP_E_INVALID, me + "width and height must be 1 .. 32768 pixels");
+    if (near_factor < 1u || near_factor > 64u) return fail(c, LAMA_HIP_E_INVALID, me + "near_factor must be 1 .. 64");
+    if ((uint64_t)width * height * 7u * near_factor >= (1ull << 32)) return fail(c, LAMA_HIP_E_INVALID, me + "width * height * 7 * near_factor must stay below 2^32");
+    if ((uint64_t)clearance_cells * clearance_cells > (uint64_t)c->max_sqdist)
+        return fail(c, LAMA_HIP_E_INVALID, me + "clearance_cells^2 exceeds the distance map's max_sqdist: no pixel could be traversable");
+    if (prefer_cells < clearance_cells || prefer_cells > 65535u) return fail(c, LAMA_HIP_E_INVALID, me + "prefer_cells must be clearance_cells .. 65535");
+    if (goal_reach > 16u) return fail(c, LAMA_HIP_E_INVALID, me + "goal_reach must be 0 .. 16");
+    if (num_sources == 0u || !sources_xy) return fail(c, LAMA_HIP_E_INVALID, me + "at least one source is needed");
+    if (num_goals != 0u && (!goals_xy || !routes)) return fail(c, LAMA_HIP_E_INVALID, me + "goals_xy or routes is NULL with num_goals != 0");
+    if (path_cap != 0u && num_goals != 0u && !paths) return fail(c, LAMA_HIP_E_INVALID, me + "paths is NULL with path_cap != 0");
+    if ((uint64_t)num_goals * path_cap > (1ull << 28)) return fail(c, LAMA_HIP_E_INVALID, me + "num_goals * path_cap must not exceed 2^28");
+    for (uint32_t k = 0; k < num_sources; ++k) {
+        const uint32_t sx = sources_xy[2 * k], sy = sources_xy[2 * k + 1];
+        if (sx < x0 || sy < y0 || ((sx - x0) >> log2s) >= width || ((sy - y0) >> log2s) >= height) return fail(c, LAMA_HIP_E_INVALID, me + "a source lies outside the box");
+    }
+    const bool has_dm = c->h_counts[2 * particle] != 0, has_occ = c->h_counts[2 * particle + 1] != 0, nothing = !has_dm && !has_occ;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    TravelBox tb;
+    tb.x0 = x0; tb.y0 = y0; tb.width = width; tb.height = height; tb.log2s = log2s; tb.near_factor = near_factor;
+    tb.tw = (width + 31u) >> 5; tb.th = (height + 31u) >> 5; tb.ntiles = tb.tw * tb.th;
+    const size_t npix = (size_t)width * height, cap_all = (size_t)num_goals * path_cap;
+    constexpr uint32_t HIST = 256;                                  // the rounds of one batch: their list lengths are read back together
+    auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+    // [field 4 npix | sq raster 2 npix | occ raster npix | class npix | two flag arrays and the list 12 ntiles | list lengths | sources |
+    //  goals | routes | ring | paths]
+    const size_t o_F = 0, o_sq = o_F + up16(4u * npix), o_occ = o_sq + up16(2u * npix), o_cls = o_occ + up16(npix), o_flags = o_cls + up16(npix);
+    const size_t o_list = o_flags + up16(8u * (size_t)tb.ntiles), o_hist = o_list + up16(4u * (size_t)tb.ntiles), o_src = o_hist + 4u * HIST;
+    const size_t o_goal = o_src + up16(8u * (size_t)num_sources), o_route = o_goal + up16(8u * (size_t)num_goals), o_ring = o_route + up16(16u * (size_t)num_goals);
+    const size_t o_path = o_ring + up16(4u * cap_all), bytes = o_path + up16(4u * cap_all);
+    HIPCHK(c, c->d_travel.grow(bytes, (size_t)1 << 16));
+    uint8_t* const base = c->d_travel;
+    uint32_t* const d_F = reinterpret_cast<uint32_t*>(base + o_F);
+    uint16_t* const d_sq = reinterpret_cast<uint16_t*>(base + o_sq);
+    int8_t* const d_occ = reinterpret_cast<int8_t*>(base + o_occ);
+    uint8_t* const d_cls = base + o_cls;
+    uint32_t* const d_flags = reinterpret_cast<uint32_t*>(base + o_flags);
+    uint32_t* const d_list = reinterpret_cast<uint32_t*>(base + o_list);
+    uint32_t* const d_hist = reinterpret_cast<uint32_t*>(base + o_hist);
+    uint32_t* const d_src = reinterpret_cast<uint32_t*>(base + o_src);
+    uint32_t* const d_goal = reinterpret_cast<uint32_t*>(base + o_goal);
+    TravelRoute* const d_route = reinterpret_cast<TravelRoute*>(base + o_route);
+    uint32_t* const d_ring = reinterpret_cast<uint32_t*>(base + o_ring);
+    uint32_t* const d_path = reinterpret_cast<uint32_t*>(base + o_path);
+    // page-locked staging: [list lengths | sources, later routes | goals | paths]
+    const size_t s_hist = 0, s_src = 4u * HIST, s_goal = s_src + std::max(up16(8u * (size_t)num_sources), up16(16u * (size_t)num_goals));
+    const size_t s_path = s_goal + up16(8u * (size_t)num_goals);
+    c->h_raster.reserve(s_path + 4u * cap_all);
+    uint8_t* const hs = c->h_raster.data();
+    std::memcpy(hs + s_src, sources_xy, 8u * (size_t)num_sources);
+    if (num_goals) std::memcpy(hs + s_goal, goals_xy, 8u * (size_t)num_goals);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_src, hs + s_src, 8u * (size_t)num_sources, hipMemcpyHostToDevice, c->stream));
+    if (num_goals) HIPCHK(c, hipMemcpyAsync(d_goal, hs + s_goal, 8u * (size_t)num_goals, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, 8u * (size_t)tb.ntiles, c->stream));
+    if (!nothing) {
+        const RasterBox box{x0, y0, width, height, stride, log2s};
+        const uint64_t xe = (uint64_t)x0 + (uint64_t)width * stride - 1u, ye = (uint64_t)y0 + (uint64_t)height * stride - 1u;
+        const dim3 rgrid((unsigned)((xe >> 5) - (x0 >> 5) + 1u), (unsigned)((ye >> 5) - (y0 >> 5) + 1u));
+        const DevParams prm = make_params(c);
+        if (has_occ) hipLaunchKernelGGL(k_raster<RASTER_TRINARY>, rgrid, dim3(256), 0, c->stream, prm, (int)particle, box, d_occ);
+        if (has_dm) hipLaunchKernelGGL(k_raster<RASTER_SQDIST>, rgrid, dim3(256), 0, c->stream, prm, (int)particle, box, d_sq);
+    }
+    hipLaunchKernelGGL(k_travel_classify, dim3((unsigned)((npix + 255u) / 256u)), dim3(256), 0, c->stream, tb, has_occ ? (const int8_t*)d_occ : (const int8_t*)nullptr,
+                       has_dm ? (const uint16_t*)d_sq : (const uint16_t*)nullptr, (uint32_t)c->max_sqdist, clearance_cells * clearance_cells, prefer_cells * prefer_cells,
+                       nothing ? 1 : 0, d_cls, d_F);
+    hipLaunchKernelGGL(k_travel_seed, dim3((num_sources + 255u) / 256u), dim3(256), 0, c->stream, tb, num_sources, (const uint32_t*)d_src, d_F, d_flags);
+    HIPCHK(c, hipGetLastError());
+    // Rounds: compact the marked tiles, relax them; the marks for the next round go into the other flag array.  The host does not
+    // know a round's list length when it launches it (the relax grid is sized for the box and workgroups beyond the list leave at
+    // once), and learns only in batches whether the field has settled: a blocking read-back costs several launches' worth of time,
+    // a round without a tile two nearly empty launches.  Batches double from 8 to 256 rounds, so at most as many empty rounds are
+    // launched as rounds had run before, with log2 as many read-backs.  After round k every pixel whose best path crosses at most k
+    // tile rims is final, so width * height + 1 rounds are the hard bound.
+    c->travel_rounds = 0; c->travel_max_tiles = 0; c->travel_readbacks = 0; c->travel_tiles = 0;
+    if (!nothing) {
+        const uint64_t max_rounds = (uint64_t)npix + 1u;
+        const dim3 cgrid((tb.ntiles + 255u) / 256u), xgrid(std::min(tb.ntiles, 2048u));
+        uint64_t launched = 0;
+        uint32_t batch = 8, cur = 0;
+        for (bool settled = false; !settled;) {
+            if (launched >= max_rounds) return fail(c, LAMA_HIP_E_STATE, me + "internal error: the field did not settle within width * height + 1 rounds");
+            const uint32_t b = (uint32_t)std::min<uint64_t>(batch, max_rounds - launched);
+            HIPCHK(c, hipMemsetAsync(d_hist, 0, 4u * (size_t)b, c->stream));
+            for (uint32_t r = 0; r < b; ++r, cur ^= 1u) {
+                hipLaunchKernelGGL(k_travel_compact, cgrid, dim3(256), 0, c->stream, tb.ntiles, d_flags + (size_t)cur * tb.ntiles, d_list, d_hist + r);
+                hipLaunchKernelGGL(k_travel_relax, xgrid, dim3(256), 0, c->stream, tb, (const uint8_t*)d_cls, d_F, (const uint32_t*)d_list, (const uint32_t*)(d_hist + r),
+                                   d_flags + (size_t)(cur ^ 1u) * tb.ntiles);
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(hs + s_hist, d_hist, 4u * (size_t)b, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            ++c->travel_readbacks;
+            const uint32_t* const hist = reinterpret_cast<const uint32_t*>(hs + s_hist);
+            for (uint32_t r = 0; r < b && !settled; ++r) {
+                if (hist[r] == 0u) { settled = true; break; }       // nothing was marked: every later round of the batch was empty too
+                ++c->travel_rounds; c->travel_tiles += hist[r]; c->travel_max_tiles = std::max(c->travel_max_tiles, hist[r]);
+            }
+            launched += b;
+            batch = std::min(batch * 2u, HIST);
+        }
+    }
+    if (num_goals) {
+        hipLaunchKernelGGL(k_travel_answer, dim3(num_goals), dim3(64), 0, c->stream, tb, num_goals, (const uint32_t*)d_goal, goal_reach, (const uint32_t*)d_F, d_route);
+        hipLaunchKernelGGL(k_travel_trace, dim3(num_goals), dim3(64), 0, c->stream, tb, num_goals, (const uint8_t*)d_cls, (const uint32_t*)d_F, d_route, path_cap, d_ring, d_path);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    if (num_goals) HIPCHK(c, hipMemcpyAsync(hs + s_src, d_route, 16u * (size_t)num_goals, hipMemcpyDeviceToHost, c->stream));
+    if (cap_all) HIPCHK(c, hipMemcpyAsync(hs + s_path, d_path, 4u * cap_all, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const TravelRoute* const got = reinterpret_cast<const TravelRoute*>(hs + s_src);
+    for (uint32_t g = 0; g < num_goals; ++g)
+        if (got[g].status == TRAVEL_BROKEN) return fail(c, LAMA_HIP_E_STATE, me + "internal error: a path left the field");
+    // ---- nothing can fail the call any more except the field's copy: the outputs
+    if (field_out) {
+        HIPCHK(c, hipMemcpyAsync(field_out, d_F, 4u * npix, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    float ms = 0;
+    if (kernel_ms) { HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1)); *kernel_ms = (double)ms; }
+    if (rounds_out) *rounds_out = c->travel_rounds;
+    if (num_goals) std::memcpy(routes, got, 16u * (size_t)num_goals);
+    if (cap_all)
+        for (uint32_t g = 0; g < num_goals; ++g)
+            if (got[g].status == TRAVEL_REACHED)
+                std::memcpy(paths + (size_t)g * path_cap, hs + s_path + 4u * (size_t)g * path_cap, 4u * (size_t)std::min<uint64_t>(path_cap, (uint64_t)got[g].steps + 1u));
+    return LAMA_HIP_OK;
+}
+
+int32_t lama_hip_map_travel_stats(lama_hip_ctx* c, uint32_t* rounds, uint64_t* tiles_run, uint32_t* max_tiles, uint32_t* readbacks)
+{
+    if (!c) return LAMA_HIP_E_INVALID;
+    if (rounds) *rounds = c->travel_rounds;
+    if (tiles_run) *tiles_run = c->travel_tiles;
+    if (max_tiles) *max_tiles = c->travel_max_tiles;
+    if (readbacks) *readbacks = c->travel_readbacks;
     return LAMA_HIP_OK;
 }
 

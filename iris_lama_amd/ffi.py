@@ -82,6 +82,8 @@ def _hip_signatures():
         {"lama_hip_map_bounds": [vp, u32, i32, vp, vp, vp], "lama_hip_map_rasterize": [vp, u32, i32, u32, u32, u32, u32, u32, vp, u64]},
         {"lama_hip_map_cast_rays": [vp, u32, i32, u32, vp, vp, u32, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]},
         {"lama_hip_map_frontiers": [vp, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp]},
+        {"lama_hip_map_travel": [vp, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp],
+         "lama_hip_map_travel_stats": [vp, vp, vp, vp, vp]},
         {"lama_hip_match_solve_batch": [vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, i32, d, vp, vp, vp]},
         {"lama_hip_match_search_lattice": [vp, u32, vp, u32, vp, vp, u32, vp, u32, d, d, u32, u32, u32, u32, vp, vp]},
         {"lama_hip_pf_map_checksums": [vp, i32, vp]},                                            # device-only diagnostic
@@ -311,6 +313,57 @@ class FrontierSet:
         self.frontiers, self.labels = frontiers, labels
 
 
+# lama_hip_route (include/lama_hip.h), 16 bytes
+ROUTE_T = np.dtype([("status", "<u4"), ("pixel", "<u4"), ("cost", "<u4"), ("steps", "<u4")])
+ROUTE_REACHED, ROUTE_UNREACHED, ROUTE_OUTSIDE = 0, 1, 2
+NO_ROUTE = 0xFFFFFFFF                                               # the field at an unreached pixel; pixel and cost of a route not REACHED
+
+
+class Travel:
+    """What lama_hip_map_travel returned: routes (ROUTE_T, one per goal), paths ((goals, path_cap) uint32 pixel indices, SOURCE
+    first; row g holds min(path_cap, steps + 1) entries, the rest is NO_ROUTE; None with path_cap 0), field ((height, width) uint32,
+    NO_ROUTE where unreached; None unless asked for), rounds and kernel_ms (diagnostics)."""
+
+    def __init__(self, routes, paths, field, rounds, kernel_ms):
+        self.routes, self.paths, self.field, self.rounds, self.kernel_ms = routes, paths, field, rounds, kernel_ms
+
+    def path(self, g):
+        """the pixels of goal g's path that were written, source first"""
+        r = self.routes[g]
+        return self.paths[g, :min(self.paths.shape[1], int(r["steps"]) + 1)] if r["status"] == ROUTE_REACHED else self.paths[g, :0]
+
+
+class TravelOptions(C.Structure):
+    """lama_travel_options (include/lama_host.h): lama::sdm::TravelOptions"""
+    _fields_ = [("stride", C.c_uint32), ("whole_map", C.c_int32), ("world_min", C.c_double * 2), ("world_max", C.c_double * 2),
+                ("robot_radius", C.c_double), ("preferred_clearance", C.c_double), ("near_factor", C.c_uint32), ("goal_reach", C.c_uint32),
+                ("max_path_points", C.c_uint32), ("field", C.c_int32)]
+
+
+class RouteSetHeader(C.Structure):
+    """lama_route_set (include/lama_host.h)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("count", C.c_uint32),
+                ("resolution", C.c_double), ("cell_size", C.c_double), ("origin", C.c_double * 3), ("path_points", C.c_uint64), ("rounds", C.c_uint32),
+                ("has_field", C.c_uint32)]
+
+
+# lama_route (include/lama_host.h), 40 bytes
+HOST_ROUTE_T = np.dtype(ROUTE_T.descr + [("length_m", "<f8"), ("path_first", "<u8"), ("path_points", "<u4"), ("reserved", "<u4")])
+
+
+class RouteSet:
+    """lama::sdm::RouteSet: the box (x0, y0, width, height, stride, resolution, cell_size, origin as in Grid), `routes` (HOST_ROUTE_T,
+    one per goal), `paths` (per route an (n, 2) array of world points, source first; empty unless reached), `field` ((height, width)
+    uint32, NO_ROUTE where no route leads, or None), rounds."""
+
+    def __init__(self, hdr, routes, points, field):
+        for name, _ in RouteSetHeader._fields_:
+            setattr(self, name, getattr(hdr, name))
+        self.origin = np.array(list(hdr.origin))
+        self.routes, self.field = routes, field
+        self.paths = [points[int(r["path_first"]):int(r["path_first"]) + int(r["path_points"])] for r in routes]
+
+
 class RayOptions(C.Structure):
     """lama_ray_options (include/lama_host.h): lama::sdm::RayCastOptions"""
     _fields_ = [("map", C.c_int32), ("stop_at_unknown", C.c_int32), ("tolerance_cells", C.c_int32)]
@@ -405,6 +458,32 @@ class _Handle:
         lab = np.full((hdr.height, hdr.width), NO_FRONTIER, dtype=np.uint32) if labels else None
         assert self.L.lama_frontiers_fetch(_p(recs), len(recs), _p(lab), 0 if lab is None else lab.size) == hdr.count
         return FrontierSet(hdr, recs, lab)
+
+    def routes(self, from_xy, goals_xy, stride=1, robot_radius=0.0, preferred_clearance=0.0, near_factor=1, goal_reach=0, max_path_points=1024, field=False,
+               world_box=None, _args=()):
+        """planRoutes: from the world points from_xy ((n, 2) metres, or one point) to each of goals_xy ((m, 2)) through the object's
+        device maps -- reachability, cost and path, relaxed on the device -> RouteSet, or None while there is no map.  world_box as
+        for occupancy_grid."""
+        o = TravelOptions()
+        self.L.lama_travel_default_options(C.byref(o))
+        o.stride, o.robot_radius, o.preferred_clearance = int(stride), float(robot_radius), float(preferred_clearance)
+        o.near_factor, o.goal_reach, o.max_path_points, o.field = int(near_factor), int(goal_reach), int(max_path_points), 1 if field else 0
+        if world_box is not None:
+            o.whole_map = 0
+            o.world_min[0], o.world_min[1], o.world_max[0], o.world_max[1] = (float(v) for v in world_box)
+        src = np.ascontiguousarray(np.asarray(from_xy, dtype=np.float64).reshape(-1, 2))
+        gl = np.ascontiguousarray(np.asarray(goals_xy, dtype=np.float64).reshape(-1, 2))
+        hdr = RouteSetHeader()
+        rc = getattr(self.L, f"{self._grid_prefix}_plan_routes")(self.h, *_args, _p(src), len(src), _p(gl), len(gl), C.byref(o), C.byref(hdr))
+        if rc < 0:
+            raise LamaError(self._error())
+        if rc == 0:
+            return None
+        recs = np.zeros(hdr.count, dtype=HOST_ROUTE_T)
+        pts = np.zeros((hdr.path_points, 2))
+        fld = np.zeros((hdr.height, hdr.width), dtype=np.uint32) if hdr.has_field else None
+        assert self.L.lama_routes_fetch(_p(recs), len(recs), _p(pts), len(pts), _p(fld), 0 if fld is None else fld.size) == hdr.count
+        return RouteSet(hdr, recs, pts, fld)
 
     def cast_rays(self, poses4, pts, origin=None, quat=None, distance_map=False, stop_at_unknown=False, tolerance_cells=-1, _args=()):
         """castRays: what a sensor at each pose {c, s, tx, ty} of poses4 (K, 4) would see in the object's device map -- the
@@ -673,6 +752,30 @@ class HipContext(_Handle):
             want = n.value
         return Frontiers(rec[:min(want, n.value)], int(n.value), int(fp.value), lab, ms.value)
 
+    def travel(self, particle, x0, y0, width, height, sources, goals=(), stride=1, clearance_cells=0, prefer_cells=None, near_factor=1, goal_reach=0,
+               path_cap=0, field=False):
+        """lama_hip_map_travel: the travel-cost field of a box of `particle`'s maps from `sources` ((n, 2) map cells), the best pixel
+        within goal_reach of each of `goals` ((m, 2) map cells) and the path to it -> Travel.  prefer_cells=None: clearance_cells."""
+        if not hasattr(self.L, "lama_hip_map_travel"):
+            raise LamaError("the device library has no lama_hip_map_travel (routes through device maps)")
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.uint32).reshape(-1, 2))
+        gl = np.ascontiguousarray(np.asarray(goals, dtype=np.uint32).reshape(-1, 2))
+        routes = np.zeros(len(gl), dtype=ROUTE_T)
+        paths = np.full((len(gl), int(path_cap)), NO_ROUTE, dtype=np.uint32) if path_cap else None
+        fld = np.zeros((int(height), int(width)), dtype=np.uint32) if field else None
+        rounds, ms = C.c_uint32(0), C.c_double(0.0)
+        self._chk(self.L.lama_hip_map_travel(self.h, int(particle), int(x0), int(y0), int(width), int(height), int(stride), int(clearance_cells),
+                                             int(clearance_cells if prefer_cells is None else prefer_cells), int(near_factor), len(src), _p(src) if len(src) else None,
+                                             len(gl), _p(gl) if len(gl) else None, int(goal_reach), _p(routes) if len(gl) else None, int(path_cap),
+                                             _p(paths) if paths is not None and paths.size else None, _p(fld), C.byref(rounds), C.byref(ms)))
+        return Travel(routes, paths, fld, int(rounds.value), ms.value)
+
+    def travel_stats(self):
+        """lama_hip_map_travel_stats -> dict(rounds, tiles_run, max_tiles, readbacks) of the context's last travel call"""
+        r, t, m, b = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.L.lama_hip_map_travel_stats(self.h, C.byref(r), C.byref(t), C.byref(m), C.byref(b)))
+        return {"rounds": int(r.value), "tiles_run": int(t.value), "max_tiles": int(m.value), "readbacks": int(b.value)}
+
     def cast_rays(self, particle, kind, poses4, pts, origin=None, quat=None, stop_at_unknown=False, tolerance_cells=-1, resolution=None):
         """lama_hip_map_cast_rays: per pose of poses4 (K, 4) and point of pts (n, 3) the first cell of `particle`'s map of `kind`
         (MAP_DISTANCE / MAP_OCCUPANCY) that stops the beam -> RayCast (range from `resolution`, default the context's cfg)."""
@@ -887,6 +990,8 @@ HOST_SYMBOLS = [
     "lama_loc_global_localization_active", "lama_loc_gloc_candidates", "lama_loc_sampling_likelihoods",
     "lama_random_set_seed", "lama_random_uniform",
     "lama_frontier_default_options", "lama_frontiers_fetch", "lama_slam_frontiers", "lama_pf_frontiers", "lama_mapbuilder_frontiers", "lama_lo_frontiers",
+    "lama_travel_default_options", "lama_routes_fetch", "lama_slam_plan_routes", "lama_pf_plan_routes", "lama_mapbuilder_plan_routes", "lama_lo_plan_routes",
+    "lama_loc_plan_routes",
     "lama_sdm_write", "lama_sdm_read", "lama_sdm_image", "lama_sdm_export_png", "lama_dm_build", "lama_dm_build_fetch",
     "lama_lo_create", "lama_lo_destroy", "lama_lo_last_error", "lama_lo_engine_origin", "lama_lo_update", "lama_lo_get_odom",
     "lama_lo_iterations", "lama_lo_deleted_patches", "lama_lo_device_context",
@@ -979,6 +1084,10 @@ def _bind_host(L):
         "lama_frontier_default_options": (None, [vp]), "lama_frontiers_fetch": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64]),
         "lama_slam_frontiers": (i32, [vp, vp, vp]), "lama_pf_frontiers": (i32, [vp, C.c_int64, vp, vp]),
         "lama_mapbuilder_frontiers": (i32, [vp, vp, vp]), "lama_lo_frontiers": (i32, [vp, vp, vp]),
+        "lama_travel_default_options": (None, [vp]), "lama_routes_fetch": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64]),
+        "lama_slam_plan_routes": (i32, [vp, vp, u32, vp, u32, vp, vp]), "lama_pf_plan_routes": (i32, [vp, C.c_int64, vp, u32, vp, u32, vp, vp]),
+        "lama_mapbuilder_plan_routes": (i32, [vp, vp, u32, vp, u32, vp, vp]), "lama_lo_plan_routes": (i32, [vp, vp, u32, vp, u32, vp, vp]),
+        "lama_loc_plan_routes": (i32, [vp, vp, u32, vp, u32, vp, vp]),
         "lama_slam_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_pf_cast_rays": (i32, [vp, C.c_int64, vp, u32, vp, u32, vp, vp, vp, vp]),
         "lama_mapbuilder_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]), "lama_lo_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
         "lama_loc_cast_rays": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, vp]),
@@ -1044,6 +1153,10 @@ class PFSlam2D(_Handle):
     def frontiers(self, particle=None, **kw):
         """getFrontiers (the best particle's) / getParticleFrontiers(particle) -> FrontierSet, or None"""
         return _Handle.frontiers(self, _args=(-1 if particle is None else int(particle),), **kw)
+
+    def routes(self, from_xy, goals_xy, particle=None, **kw):
+        """planRoutes (the best particle's maps) / planParticleRoutes(particle) -> RouteSet, or None"""
+        return _Handle.routes(self, from_xy, goals_xy, _args=(-1 if particle is None else int(particle),), **kw)
 
     def cast_rays(self, poses4, pts, origin=None, quat=None, particle=None, **kw):
         """castRays (the best particle's maps) / castParticleRays(particle) -> RayCast, or None (no map yet, or the particle lives

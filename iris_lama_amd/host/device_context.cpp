@@ -10,6 +10,7 @@
 #include "lama/sdm/grid.h"
 #include "lama/sdm/ray_cast.h"
 #include "lama/sdm/frontier.h"
+#include "lama/sdm/travel.h"
 #include "scan_arrays.hpp"
 #include "lama/sdm_maps.h"
 
@@ -163,6 +164,57 @@ bool DeviceContext::frontiers(uint32_t particle, double resolution, sdm::Frontie
         const double ci = (double)r.sum_i / (double)r.pixels, cj = (double)r.sum_j / (double)r.pixels;
         f.centroid = Vector2d(set.origin[0] + resolution * (s * ci + half), set.origin[1] + resolution * (s * cj + half));
         f.seed = Vector2d(set.origin[0] + resolution * (s * (double)(r.label % set.width) + half), set.origin[1] + resolution * (s * (double)(r.label / set.width) + half));
+    }
+    return true;
+}
+
+// ---- routes (include/lama/sdm/travel.h) -----------------------------------------------------------------------------------------
+bool DeviceContext::travel(uint32_t particle, double resolution, bool distance_only, const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals,
+                           sdm::RouteSet& set, const sdm::TravelOptions& o) const
+{
+    if (!ctx_) return false;
+    if (!eng_->map_travel)
+        throw std::runtime_error(std::string(owner_) + ": the device library " + eng_->origin + " has no lama_hip_map_travel (routes through device maps)");
+    if (from.empty()) throw std::invalid_argument(std::string(owner_) + ": planRoutes needs at least one point to start from");
+    if (!(o.robot_radius >= 0.0) || !(o.preferred_clearance >= 0.0)) throw std::invalid_argument(std::string(owner_) + ": planRoutes needs a robot radius and a preferred clearance >= 0");
+    set = sdm::RouteSet();
+    set.routes.resize(goals.size());
+    sdm::GridOptions go;
+    go.stride = o.stride; go.whole_map = o.whole_map; go.world_min = o.world_min; go.world_max = o.world_max;
+    if (!grid_box(*eng_, ctx_, owner_, particle, distance_only ? LAMA_HIP_MAP_DISTANCE : LAMA_HIP_MAP_OCCUPANCY, resolution, go, set)) return true;   // a map without patches: nothing is reached
+    const Map frame(resolution, sdm::kDistanceMap);                 // w2m of every map of this resolution
+    auto cells = [&frame](const std::vector<Vector2d>& pts) {
+        std::vector<uint32_t> xy(2 * pts.size());
+        for (size_t k = 0; k < pts.size(); ++k) {
+            const Vector3ui c = frame.w2m(Vector3d(pts[k][0], pts[k][1], 0.0));
+            xy[2 * k] = c(0); xy[2 * k + 1] = c(1);
+        }
+        return xy;
+    };
+    const std::vector<uint32_t> src = cells(from), dst = cells(goals);
+    const double inv = 1.0 / resolution;
+    const double clear = std::ceil(o.robot_radius * inv), prefer = std::max(clear, std::ceil(o.preferred_clearance * inv));
+    if (prefer > 65535.0) throw std::invalid_argument(std::string(owner_) + ": the preferred clearance of planRoutes exceeds 65535 cells");
+    const uint32_t ng = (uint32_t)goals.size(), cap = o.max_path_points;
+    std::vector<lama_hip_route> routes(ng);
+    std::vector<uint32_t> paths((size_t)ng * cap);
+    if (o.field) set.field.assign((size_t)set.width * set.height, 0xFFFFFFFFu);
+    check(eng_->map_travel(ctx_, particle, set.x0, set.y0, set.width, set.height, set.stride, (uint32_t)clear, (uint32_t)prefer, o.near_factor, (uint32_t)from.size(),
+                           src.data(), ng, ng ? dst.data() : nullptr, o.goal_reach, ng ? routes.data() : nullptr, cap, paths.empty() ? nullptr : paths.data(),
+                           o.field ? set.field.data() : nullptr, &set.rounds, nullptr),
+          "lama_hip_map_travel");
+    const double s = (double)set.stride, half = ((double)set.stride - 1.0) / 2.0;
+    for (uint32_t g = 0; g < ng; ++g) {
+        sdm::Route& r = set.routes[g];
+        r.status = routes[g].status; r.pixel = routes[g].pixel; r.cost = routes[g].cost; r.steps = routes[g].steps;
+        if (r.status != sdm::kRouteReached) continue;
+        r.length_m = (double)r.cost * set.cell_size / 5.0;
+        const size_t n = (size_t)std::min<uint64_t>(cap, (uint64_t)r.steps + 1u);
+        r.path.resize(n);
+        for (size_t k = 0; k < n; ++k) {
+            const uint32_t p = paths[(size_t)g * cap + k];
+            r.path[k] = Vector2d(set.origin[0] + resolution * (s * (double)(p % set.width) + half), set.origin[1] + resolution * (s * (double)(p / set.width) + half));
+        }
     }
     return true;
 }

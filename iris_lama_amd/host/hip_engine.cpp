@@ -104,6 +104,7 @@ std::shared_ptr<HipEngine> loadHipEngine(const std::string& explicit_path)
     e->map_bounds = reinterpret_cast<decltype(e->map_bounds)>(dlsym(dl, "lama_hip_map_bounds"));
     e->map_rasterize = reinterpret_cast<decltype(e->map_rasterize)>(dlsym(dl, "lama_hip_map_rasterize"));
     e->map_frontiers = reinterpret_cast<decltype(e->map_frontiers)>(dlsym(dl, "lama_hip_map_frontiers"));
+    e->map_travel = reinterpret_cast<decltype(e->map_travel)>(dlsym(dl, "lama_hip_map_travel"));
     e->map_cast_rays = reinterpret_cast<decltype(e->map_cast_rays)>(dlsym(dl, "lama_hip_map_cast_rays"));
     return e;
 }

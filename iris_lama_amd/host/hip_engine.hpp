@@ -66,6 +66,7 @@ struct HipEngine {
     decltype(&lama_hip_map_bounds) map_bounds = nullptr;
     decltype(&lama_hip_map_rasterize) map_rasterize = nullptr;
     decltype(&lama_hip_map_frontiers) map_frontiers = nullptr;
+    decltype(&lama_hip_map_travel) map_travel = nullptr;
     // ray casts through a map (castRays of the host classes, Loc2D::checkScan); optional in the same way: those methods throw on a
     // library without it
     decltype(&lama_hip_map_cast_rays) map_cast_rays = nullptr;

@@ -1214,6 +1214,77 @@ int lama_mapbuilder_frontiers(lama_mapbuilder* h, const lama_frontier_options* o
 int lama_lo_frontiers(lama_lo* h, const lama_frontier_options* o, lama_frontier_set* out)
 { return frontiers_of(h, o, out, [h](lama::sdm::FrontierSet& s, const lama::sdm::FrontierOptions& fo) { return h->l->getFrontiers(s, fo); }); }
 }   // extern "C"
+// ---- routes (include/lama/sdm/travel.h) of the classes above ----
+namespace {
+thread_local std::vector<lama_route> g_routes;               // the result of the last route call on this thread (lama_routes_fetch)
+thread_local std::vector<double> g_route_points;
+thread_local std::vector<uint32_t> g_route_field;
+// 1: made (box and counts in *out, routes, points and field kept), 0: the object has no map (yet / here), -2: failure
+template <class H, class F>
+int routes_of(H* h, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o, lama_route_set* out, F&& plan)
+{
+    try {
+        lama::sdm::TravelOptions to;
+        if (o) {
+            to.stride = o->stride; to.whole_map = o->whole_map != 0; to.robot_radius = o->robot_radius; to.preferred_clearance = o->preferred_clearance;
+            to.near_factor = o->near_factor; to.goal_reach = o->goal_reach; to.max_path_points = o->max_path_points; to.field = o->field != 0;
+            to.world_min = Vector2d(o->world_min[0], o->world_min[1]); to.world_max = Vector2d(o->world_max[0], o->world_max[1]);
+        }
+        std::vector<Vector2d> from(n_from), goals(n_goals);
+        for (uint32_t k = 0; k < n_from; ++k) from[k] = Vector2d(from_xy[2 * k], from_xy[2 * k + 1]);
+        for (uint32_t k = 0; k < n_goals; ++k) goals[k] = Vector2d(goals_xy[2 * k], goals_xy[2 * k + 1]);
+        lama::sdm::RouteSet s;
+        if (!plan(from, goals, s, to)) return 0;
+        out->x0 = s.x0; out->y0 = s.y0; out->width = s.width; out->height = s.height; out->stride = s.stride; out->count = (uint32_t)s.routes.size();
+        out->resolution = s.resolution; out->cell_size = s.cell_size;
+        for (int k = 0; k < 3; ++k) out->origin[k] = s.origin[k];
+        out->rounds = s.rounds; out->has_field = s.field.empty() ? 0u : 1u;
+        g_routes.resize(s.routes.size());
+        g_route_points.clear();
+        for (size_t k = 0; k < s.routes.size(); ++k) {
+            const lama::sdm::Route& r = s.routes[k];
+            g_routes[k] = lama_route{r.status, r.pixel, r.cost, r.steps, r.length_m, (uint64_t)(g_route_points.size() / 2), (uint32_t)r.path.size(), 0u};
+            for (const Vector2d& p : r.path) { g_route_points.push_back(p[0]); g_route_points.push_back(p[1]); }
+        }
+        out->path_points = (uint64_t)(g_route_points.size() / 2);
+        g_route_field.swap(s.field);
+        return 1;
+    } catch (const std::exception& e) { h->error = e.what(); return -2; }
+}
+}
+extern "C" {
+void lama_travel_default_options(lama_travel_options* o)
+{
+    const lama::sdm::TravelOptions d;
+    o->stride = d.stride; o->whole_map = d.whole_map ? 1 : 0; o->robot_radius = d.robot_radius; o->preferred_clearance = d.preferred_clearance;
+    o->near_factor = d.near_factor; o->goal_reach = d.goal_reach; o->max_path_points = d.max_path_points; o->field = d.field ? 1 : 0;
+    o->world_min[0] = o->world_min[1] = o->world_max[0] = o->world_max[1] = 0.0;
+}
+int64_t lama_routes_fetch(lama_route* routes, uint64_t cap_routes, double* path_xy, uint64_t cap_points, uint32_t* field, uint64_t cap_field)
+{
+    if (routes && cap_routes >= g_routes.size() && !g_routes.empty()) std::memcpy(routes, g_routes.data(), g_routes.size() * sizeof(lama_route));
+    if (path_xy && 2 * cap_points >= g_route_points.size() && !g_route_points.empty()) std::memcpy(path_xy, g_route_points.data(), g_route_points.size() * sizeof(double));
+    if (field && cap_field >= g_route_field.size() && !g_route_field.empty()) std::memcpy(field, g_route_field.data(), g_route_field.size() * sizeof(uint32_t));
+    return (int64_t)g_routes.size();
+}
+#define LAMA_PLAN_ARGS const std::vector<Vector2d>& f, const std::vector<Vector2d>& g, lama::sdm::RouteSet& s, const lama::sdm::TravelOptions& to
+int lama_slam_plan_routes(lama_slam* h, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o, lama_route_set* out)
+{ return routes_of(h, from_xy, n_from, goals_xy, n_goals, o, out, [h](LAMA_PLAN_ARGS) { return h->s->planRoutes(f, g, s, to); }); }
+int lama_pf_plan_routes(lama_pf* h, int64_t particle, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o,
+                        lama_route_set* out)
+{
+    return routes_of(h, from_xy, n_from, goals_xy, n_goals, o, out, [h, particle](LAMA_PLAN_ARGS) {
+        return particle < 0 ? h->pf->planRoutes(f, g, s, to) : h->pf->planParticleRoutes((size_t)particle, f, g, s, to); });
+}
+int lama_mapbuilder_plan_routes(lama_mapbuilder* h, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o,
+                                lama_route_set* out)
+{ return routes_of(h, from_xy, n_from, goals_xy, n_goals, o, out, [h](LAMA_PLAN_ARGS) { return h->b->planRoutes(f, g, s, to); }); }
+int lama_lo_plan_routes(lama_lo* h, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o, lama_route_set* out)
+{ return routes_of(h, from_xy, n_from, goals_xy, n_goals, o, out, [h](LAMA_PLAN_ARGS) { return h->l->planRoutes(f, g, s, to); }); }
+int lama_loc_plan_routes(lama_loc* h, const double* from_xy, uint32_t n_from, const double* goals_xy, uint32_t n_goals, const lama_travel_options* o, lama_route_set* out)
+{ return routes_of(h, from_xy, n_from, goals_xy, n_goals, o, out, [h](LAMA_PLAN_ARGS) { return h->l.planRoutes(f, g, s, to); }); }
+#undef LAMA_PLAN_ARGS
+}   // extern "C"
 // ---- ray casts (include/lama/sdm/ray_cast.h) of the classes above ----
 namespace {
 // 1: cast (the arrays of *out that are not NULL are filled), 0: the object has no such map (yet / here), -2: failure

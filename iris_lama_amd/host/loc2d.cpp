@@ -161,6 +161,12 @@ bool Loc2D::castRays(const std::vector<Pose2D>& poses, const PointCloudXYZ::Ptr&
     return dev_ && surface && dev_.castRays(0, opt_.resolution, poses, *surface, result, options);
 }
 
+bool Loc2D::planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options)
+{
+    if (distance_map && distance_map->hasPending()) distance_map->update();
+    return dev_ && dev_.travel(0, opt_.resolution, true, from, goals, set, options);
+}
+
 std::vector<uint8_t> Loc2D::checkScan(const PointCloudXYZ::Ptr& surface, int32_t tolerance_cells)
 {
     if (tolerance_cells < 0) throw std::invalid_argument("lama::Loc2D::checkScan: tolerance_cells must not be negative");

@@ -724,6 +724,19 @@ bool PFSlam2D::getFrontiers(sdm::FrontierSet& set, const sdm::FrontierOptions& o
     return has_first_scan && getParticleFrontiers(getBestParticleIdx(), set, options);
 }
 
+bool PFSlam2D::planParticleRoutes(size_t i, const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options) const
+{
+    if (!has_first_scan || i >= particles_.size()) return false;
+    if (group_) return ownerOf((uint32_t)i)->planParticleRoutes(i, from, goals, set, options);
+    if (!ownsParticle((uint32_t)i)) return false;
+    return dev_.travel((uint32_t)i - lo_, options_.resolution, false, from, goals, set, options);
+}
+
+bool PFSlam2D::planRoutes(const std::vector<Vector2d>& from, const std::vector<Vector2d>& goals, sdm::RouteSet& set, const sdm::TravelOptions& options) const
+{
+    return has_first_scan && planParticleRoutes(getBestParticleIdx(), from, goals, set, options);
+}
+
 std::shared_ptr<const FrequencyOccupancyMap> PFSlam2D::getParticleOccupancyMap(size_t i) const
 {
     sdm::HostMap m;
